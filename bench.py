@@ -11,11 +11,17 @@ region.
 
 --gpus N > 1: BASELINE.json configs[3] -- a 100 000 001-item table row-sharded over the N ranks, n = 1024
 negatives, B = 4096 queries per GPU per step (weak scaling), ids out / scores back by RCCL all-to-all.  Started
-without a launcher (WORLD_SIZE unset) the script re-executes itself under torch.distributed.run with N ranks;
-under the driver's own torchrun it checks that the world size is N.
+without a launcher (WORLD_SIZE unset) the script runs itself under torch.distributed.run with N ranks as a child process
+(signals passed on, the child ended with the parent); under the driver's own torchrun it checks that the world size is N.
 
-Prints ONE JSON line (rank 0).  Extra keys beyond the driver contract: roofline, cpu_baseline,
-train_step (forward + loss + row-sparse gradient scatter), sweep.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K headline steps and prints the line; every
+other figure runs only with --full: per-kernel roofline, placement and tracked-profile figures, cpu_baseline, train_step
+(forward + loss + row-sparse gradient scatter), sweep, fit, fullscore, seq_softmax, table_100M, sharded_world1, and for
+--gpus N > 1 the in-job world-1 reference and the side figures.
+
+--dump-outputs DIR: after the timed steps, the arrays the last timed step returned, as DIR/<name>.npy (float32; integer
+ids as float64), at most 64 MB in all (a fixed, seeded sample of query rows when larger).  The same arguments give the
+same inputs and the same generator state for that step in every run, so that two builds can be compared output for output.
 """
 import argparse
 import threading
@@ -68,7 +74,25 @@ def zipf_counts(n_items, n_inter, seed=1):
     return counts
 
 
+def draw_positives(n_items, counts, shape, dev, generator):
+    """Positive item ids, uniform over the items the interaction stream holds (count > 0; over every item when there are
+    no counts).  A positive is itself an interaction, so its popularity is never zero: a zero-count positive would have
+    pos_logp = log 0 = -inf, and the reference's sampled-softmax loss is NaN for it."""
+    if counts is None:
+        return torch.randint(1, n_items, shape, device=dev, generator=generator)
+    seen = torch.nonzero(counts[1:] > 0).squeeze(1).add_(1).to(dev)
+    return seen[torch.randint(0, seen.numel(), shape, device=dev, generator=generator)]
+
+
+def headline_roofline(alg_bytes, **figures):
+    """`roofline` of the single-GPU headline line: the byte model's constants plus `figures` -- `achieved` / `frac` from the
+    event-timed fused kernel alone (--full), `step_achieved` / `step_frac` from the whole timed step (launch + loss mean)."""
+    return {'bound': 'hbm', 'kernel': 'rsa::fused_fwd_kernel<32,false,false,true,true> (sample+gather+score+BPR epilogue)',
+            'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'traffic': None, 'alg_bytes_per_launch': int(alg_bytes), **figures}
+
+
 PREWARM_S = 1.5
+HEADLINE_BATCHES = 1024     # distinct (user, positive) batches of the headline, cycled
 
 
 def prewarm(fn, seconds=None):
@@ -111,9 +135,14 @@ def time_gpu_best(fn, steps, warmup, repeats=3):
 
 
 def self_launch(n_gpus):
-    """`python bench.py --gpus N` without a launcher: become `python -m torch.distributed.run ... bench.py --gpus N`
-    (one rank per GPU over RCCL, rendezvous on 127.0.0.1)."""
+    """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run ... bench.py --gpus N` as a child
+    process (one rank per GPU over RCCL, rendezvous on 127.0.0.1) and exit with its status.  SIGINT / SIGTERM / SIGHUP sent
+    to this process are passed on to the launcher, which ends its ranks; should this process die without passing them on
+    (SIGKILL), the kernel sends the launcher SIGTERM (PR_SET_PDEATHSIG)."""
+    import ctypes
+    import signal
     import socket
+    import subprocess
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
     port = s.getsockname()[1]
@@ -122,7 +151,39 @@ def self_launch(n_gpus):
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    os.execvpe(cmd[0], cmd, env)
+
+    def die_with_parent():
+        ctypes.CDLL(None, use_errno=True).prctl(1, int(signal.SIGTERM))      # PR_SET_PDEATHSIG
+    child = subprocess.Popen(cmd, env=env, preexec_fn=die_with_parent)
+    for sig in (signal.SIGINT, signal.SIGTERM, signal.SIGHUP):
+        signal.signal(sig, lambda signum, frame: child.send_signal(signum))
+    raise SystemExit(child.wait())
+
+
+DUMP_BUDGET_BYTES = 60_000_000      # --dump-outputs: below the 64 MB allowed in all
+
+
+def dump_outputs(out_dir, outputs, suffix='', budget=DUMP_BUDGET_BYTES):
+    """Write the tensors of one step's result dict as <out_dir>/<name><suffix>.npy: floating point as float32, integer ids as
+    float64 (exact below 2^53).  If the whole set exceeds `budget` bytes, every array with one row per query is cut to the
+    same fixed, seeded sample of rows (sorted; their indices in sample_rows<suffix>.npy)."""
+    import numpy as np
+    arrays = {k: v.detach() for k, v in outputs.items() if torch.is_tensor(v)}
+    size = {k: v.numel() * (4 if v.is_floating_point() else 8) for k, v in arrays.items()}
+    rows = max((v.shape[0] for v in arrays.values() if v.dim() > 0), default=0)
+    per_row = {k: size[k] // rows for k, v in arrays.items() if rows and v.dim() > 0 and v.shape[0] == rows}
+    keep = None
+    if sum(size.values()) > budget and per_row:
+        k_rows = (budget - sum(s for k, s in size.items() if k not in per_row)) // (sum(per_row.values()) + 8)
+        keep = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:k_rows].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if keep is not None and name in per_row:
+            v = v[keep.to(v.device)]
+        v = v.to(torch.float32 if v.is_floating_point() else torch.float64).cpu().numpy()
+        np.save(os.path.join(out_dir, f'{name}{suffix}.npy'), v)
+    if keep is not None:
+        np.save(os.path.join(out_dir, f'sample_rows{suffix}.npy'), keep.numpy().astype(np.float64))
 
 
 def _cpu_model():
@@ -419,9 +480,14 @@ def main():
                     help='inverse-CDF structure of the popularity sampler (experiments)')
     ap.add_argument('--shard-layout', default='block', choices=['block', 'interleaved'],
                     help='row ownership of the sharded table (--gpus N > 1): contiguous blocks, or rows r, r + N, ...')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-sweep', action='store_true')
-    ap.add_argument('--no-fit', action='store_true', help='skip the BaseRetriever.fit figures (tools/bench_fit.py)')
+    ap.add_argument('--full', action='store_true',
+                    help='every figure besides the headline (side figures, roofline, CPU baseline, world-1 reference); '
+                         'a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-sweep', action='store_true', help='with --full: skip the sweep and the other side figures it gates')
+    ap.add_argument('--no-fit', action='store_true', help='with --full: skip the BaseRetriever.fit figures (tools/bench_fit.py)')
     args = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -474,7 +540,7 @@ def main():
     counts = zipf_counts(args.items, 100_000_000) if (popular or not sharded_run) else None
     gen = torch.Generator(device=dev).manual_seed(100 + rank)
     uid = torch.randint(1, args.users, (B,), device=dev, generator=gen)
-    pos = torch.randint(1, args.items, (B,), device=dev, generator=gen)
+    pos = draw_positives(args.items, counts, (B,), dev, gen)
     torch.manual_seed(2022 + rank)       # basemodel.yaml:63 seed
 
     extra = {}
@@ -509,7 +575,7 @@ def main():
     if world == 1 and not force_shard:
         # FIRST (a fresh process, like a user's): the thing users run, BaseRetriever.fit end to end (tools/bench_fit.py) -- configs[0] on the committed ml-100k
         # fixture next to the reference's published epoch times, and configs[1]-shaped fit through loader + stepper
-        if not args.no_sweep and not args.no_fit and args.dim == 128:
+        if args.full and not args.no_sweep and not args.no_fit and args.dim == 128:
             try:
                 torch.cuda.empty_cache()
                 sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -526,6 +592,52 @@ def main():
         kw = dict(query_index=uid, pos_ids=pos, sampler=kind)
         if popular:
             kw.update(sampler.lookup_kwargs())
+        parallelism = 'single'
+        workload = (f'BPR two-tower d={d}, synthetic {args.items} items / {args.users} users / 1e8-interaction Zipf '
+                    f'popularity, positives uniform over the items it holds, {args.sampler} sampler neg={n}, InnerProduct + '
+                    f'BPR loss, B={B} queries/step (BASELINE.json configs[1])')
+
+        # ---- the headline: exactly K steps after W warm-up steps
+        hb, head_tick = {}, {'i': 0}
+
+        def fresh_kw():
+            i = head_tick['i'] % hb['n_batches']
+            head_tick['i'] += 1
+            return dict(kw, query_index=hb['uid_all'][i], pos_ids=hb['pos_all'][i])
+
+        def headline_step():      # sample + gather + score + BPR loss (value, d loss/d score, mean): ONE kernel
+            hb['step'] = ra.ops.fused_forward(item, user, n, out=hb.get('step'), fused_bpr=True, **fresh_kw())
+            return hb['step']
+
+        def run_headline():
+            # a FRESH (user, positive) batch every step (one batch reused for every timed step keeps its
+            # 67 MB of user / positive rows Infinity-Cache resident): drawn before the clock starts, one row per step -- a
+            # row of the id matrix is a view, so the timed region holds exactly the kernels it held before.  Past
+            # HEADLINE_BATCHES steps the batches repeat (each step streams GBs of rows: a batch is long evicted when it returns)
+            hb['n_batches'] = n_batches = min(args.steps + args.warmup, HEADLINE_BATCHES)
+            g_b = torch.Generator(device=dev).manual_seed(4242 + rank)
+            hb['uid_all'] = torch.randint(1, args.users, (n_batches, B), device=dev, generator=g_b)
+            hb['pos_all'] = draw_positives(args.items, counts, (n_batches, B), dev, g_b)
+            head_tick['i'] = 0
+            prewarm(headline_step)
+            # the time-based pre-warm runs a varying number of steps: restart the batch cycle and the device generator after
+            # it, so that the warm-up and timed steps -- and the outputs of the last one -- are the same in every run
+            head_tick['i'] = 0
+            torch.cuda.manual_seed(2022 + rank)
+            ms = time_gpu(headline_step, args.steps, args.warmup, warm_s=0.0) * 1e3
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, hb['step'])
+            return ms
+
+        if not args.full:
+            # a plain run: the headline alone, measured right after the set-up (prewarm() brings the clocks up)
+            ms_step = run_headline()
+            alg = bytes_per_triplet(d, n, popular, fused_loss=True) * B * n
+            step_gbs = alg / (ms_step * 1e-3) / 1e9
+            # whole-step figures under their own keys: `achieved` / `frac` (the fused kernel alone, event-timed) need --full
+            roofline = headline_roofline(alg, step_achieved=round(step_gbs, 1), step_frac=round(step_gbs / HBM_PEAK_GBS, 4))
+            print(json.dumps(headline_line(B * n / ms_step / 1e3, ms_step, workload, parallelism, roofline, extra)), flush=True)
+            return
         bufs = {}
 
         def fwd(b=B, u=uid, p=pos, key='main'):
@@ -682,7 +794,7 @@ def main():
                     S_q = max(2, 65536 // b2)
                     gq = torch.Generator(device=dev).manual_seed(77)
                     uq = torch.randint(1, args.users, (S_q * b2,), device=dev, generator=gq)
-                    pq = torch.randint(1, args.items, (S_q * b2,), device=dev, generator=gq)
+                    pq = draw_positives(args.items, counts, (S_q * b2,), dev, gq)
                     stq = ra.ops.FusedStep(item, user, n, fused_bpr=True, n_batches=S_q, **dict(kw, query_index=uq, pos_ids=pq))
                     tq = time_gpu(stq, max(5, args.steps // 2), 5) * 1e3 / S_q
                     sweep[f'B={b2}']['queue'] = with_profile(
@@ -727,7 +839,7 @@ def main():
             t_seg = time_gpu_best(lambda: ra.ops.seg_gather(it3, flat, start, end, L3), 50, 5) * 1e3
             seg_bytes = float(end[-1]) * (4 * d + 8) + b3 * L3 * 4 * d + b3 * L3 * 8
             q3 = user[1:b3 + 1].contiguous()
-            pos3 = torch.randint(1, n_it3, (b3,), device=dev, generator=g3)
+            pos3 = draw_positives(n_it3, counts[:n_it3], (b3,), dev, g3)
             ps3 = ra.PopularSamplerModel(counts[:n_it3]).to(dev)
             kw3 = dict(pos_ids=pos3, sampler=nat.SAMPLER_POPULAR, **ps3.lookup_kwargs())
             buf3 = {}
@@ -849,34 +961,15 @@ def main():
             del w5, qq5
         except Exception as e:
             extra['fullscore']['softmax_train_step_error'] = repr(e)[:200]
-        # ---- the headline line: exactly K steps after W warm-up steps, measured after the secondary figures so that the
-        # GPU is at steady-state clocks (boxes of the pool differ by several per cent either way)
-        hb = {}
-        # a FRESH (user, positive) batch every step (one batch reused for every timed step keeps its
-        # 67 MB of user / positive rows Infinity-Cache resident): drawn before the clock starts, one row per step -- a
-        # row of the id matrix is a view, so the timed region holds exactly the kernels it held before
-        n_batches = args.steps + args.warmup
-        g_b = torch.Generator(device=dev).manual_seed(4242 + rank)
-        uid_all = torch.randint(1, args.users, (n_batches, B), device=dev, generator=g_b)
-        pos_all = torch.randint(1, args.items, (n_batches, B), device=dev, generator=g_b)
-        tick = {'i': 0}
-
-        def fresh_kw():
-            i = tick['i'] % n_batches
-            tick['i'] += 1
-            return dict(kw, query_index=uid_all[i], pos_ids=pos_all[i])
-
-        def step():          # sample + gather + score + BPR loss (value, d loss/d score, mean): ONE kernel
-            hb['step'] = ra.ops.fused_forward(item, user, n, out=hb.get('step'), fused_bpr=True, **fresh_kw())
-            return hb['step']
+        # ---- the headline line (run_headline above), measured after the secondary figures so that the GPU is at steady-state
+        # clocks (boxes of the pool differ by several per cent either way)
+        ms_step = run_headline()
 
         def step_unfused():  # the same with the loss as its own kernel
             hb['fwd'] = ra.ops.fused_forward(item, user, n, out=hb.get('fwd'), **fresh_kw())
             o = hb['fwd']
             return ra.ops.pairwise_loss(nat.LOSS_BPR, o['pos_score'], o['neg_score'], want_grad=True)
 
-        tick['i'] = 0
-        ms_step = time_gpu(step, args.steps, args.warmup) * 1e3
         extra['unfused_loss_ms_per_step'] = round(time_gpu(step_unfused, args.steps, args.warmup) * 1e3, 4)
 
         # dominant kernel alone, timed with events on the launch stream
@@ -891,11 +984,8 @@ def main():
         k_avg = sum(k_ms) / len(k_ms)
         alg = bytes_per_triplet(d, n, popular, fused_loss=True) * B * n
         achieved = alg / (k_avg * 1e-3) / 1e9
-        roofline = {'bound': 'hbm', 'kernel': 'rsa::fused_fwd_kernel<32,false,false,true,true> (sample+gather+score+BPR epilogue)',
-                    'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                    'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': None,
-                    'alg_bytes_per_launch': int(alg), 'avg_kernel_ms': round(k_avg, 4),
-                    'median_kernel_ms': round(k_ms[len(k_ms) // 2], 4)}
+        roofline = headline_roofline(alg, achieved=round(achieved, 1), frac=round(achieved / HBM_PEAK_GBS, 4),
+                                     avg_kernel_ms=round(k_avg, 4), median_kernel_ms=round(k_ms[len(k_ms) // 2], 4))
         # The same launch on OTHER allocations of its output buffers (on some boxes certain allocations are 10-15 % slower
         # to write into under read load -- bimodal, stable for the life of the allocation).  The headline ran on a PLAIN torch
         # allocation (recstudio_amd.placement is opt-in since round 6); three more plain ones, all kept alive so that each is a
@@ -971,12 +1061,14 @@ def main():
                                                'frac_of_hbm_peak': round(alg8 / t8 / 1e6 / HBM_PEAK_GBS, 4)},
                                               f'N1e8_uniform_n{n_neg}_B{b_q}', alg8)
                 try:          # the popularity sampler on the same table (2^25-bucket lookup table, 537 MB)
-                    ps8 = ra.PopularSamplerModel(zipf_counts(n8, 100_000_000), lookup=args.pop_lookup).to(dev)
+                    counts8 = zipf_counts(n8, 100_000_000)
+                    ps8 = ra.PopularSamplerModel(counts8, lookup=args.pop_lookup).to(dev)
+                    pos8p = draw_positives(n8, counts8, (B,), dev, gen)
                     b8p = {}
 
                     def st8p():
                         b8p['o'] = ra.ops.fused_forward(item8, user, n, out=b8p.get('o'), fused_bpr=True, want_mean=False,
-                                                       query_index=uid, pos_ids=pos8, sampler=nat.SAMPLER_POPULAR,
+                                                       query_index=uid, pos_ids=pos8p, sampler=nat.SAMPLER_POPULAR,
                                                        **ps8.lookup_kwargs())
                     t8p = time_gpu_best(st8p, 50, 5) * 1e3
                     alg8p = bytes_per_triplet(d, n, True, fused_loss=True) * B * n
@@ -985,7 +1077,7 @@ def main():
                          'frac_of_hbm_peak': round(alg8p / t8p / 1e6 / HBM_PEAK_GBS, 4),
                          'lookup': 'bucket lines 2^%d x 128 B' % ps8.lines_log2 if ps8.lines_log2 else 'lut 2^%d' % ps8.guide_log2},
                         'N1e8_popular_n64_B65536', alg8p)
-                    del ps8, b8p
+                    del ps8, b8p, pos8p, counts8
                 except Exception as e:
                     res8['popular,n=64,B=65536'] = {'error': repr(e)[:200]}
                 extra['table_100M'] = {'workload': f'uniform (and popularity) sampler + gather + score + fused BPR, N={n8} items (51.2 GB table), d={d} '
@@ -1109,10 +1201,6 @@ def main():
             except Exception as e:
                 extra['sharded_world1'] = {'error': repr(e)[:200]}
         value = B * n / ms_step / 1e3
-        parallelism = 'single'
-        workload = (f'BPR two-tower d={d}, synthetic {args.items} items / {args.users} users / 1e8-interaction Zipf '
-                    f'popularity, {args.sampler} sampler neg={n}, InnerProduct + BPR loss, B={B} queries/step '
-                    f'(BASELINE.json configs[1])')
         # box state under load + the side figures the claims rest on, numbers only, INSIDE `roofline` (the driver's record
         # keeps that object whole and only the names of the other extra keys)
         try:
@@ -1147,9 +1235,12 @@ def main():
         user = torch.empty(args.users, d, device=dev).normal_(0, 0.02, generator=torch.Generator(device=dev).manual_seed(3))
         sampler = (ra.PopularSamplerModel(counts, lookup=args.pop_lookup) if popular else ra.UniformSampler(args.items)).to(dev)
 
+        last = {}
+
         def make_step(tbl, smp, u, p, nn):
             def step():      # sample + route, key exchange, owner-side score, score exchange, gather home + BPR loss + gradient
-                return tbl.sample_and_score(user, u, p, nn, smp, fused_loss='bpr', want_ids=False, want_grad=True)
+                last['out'] = tbl.sample_and_score(user, u, p, nn, smp, fused_loss='bpr', want_ids=False, want_grad=True)
+                return last['out']
             return step
 
         def max_over_ranks(ms):
@@ -1157,16 +1248,18 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             return float(t.item())
 
-        # ---- the world-1 reference, in this job: every rank alone on its own block (rows re-based to a one-rank plan)
-        solo_plan = shard.RowShardPlan(n_loc, 1)
-        solo_pos = (pos % (n_loc - 1)) + 1
-        solo_sampler = (ra.PopularSamplerModel(plan.take(counts, rank), lookup=args.pop_lookup) if popular else ra.UniformSampler(n_loc)).to(dev)
-        solo_tbl = shard.ShardedItemTable(item_local, solo_plan, 0, dist, check_every=0)
-        solo_step = make_step(solo_tbl, solo_sampler, uid, solo_pos, n)
-        solo_step()
-        ms_solo = max_over_ranks(time_gpu(solo_step, args.steps, args.warmup, dist) * 1e3)
-        solo_tbl.check_overflow()
-        del solo_tbl, solo_sampler
+        # ---- the world-1 reference (--full), in this job: every rank alone on its own block (rows re-based to a one-rank plan)
+        if args.full:
+            solo_pos = ((pos % (n_loc - 1)) + 1 if counts is None else
+                        draw_positives(n_loc, plan.take(counts, rank), (B,), dev, gen))
+            solo_plan = shard.RowShardPlan(n_loc, 1)
+            solo_sampler = (ra.PopularSamplerModel(plan.take(counts, rank), lookup=args.pop_lookup) if popular else ra.UniformSampler(n_loc)).to(dev)
+            solo_tbl = shard.ShardedItemTable(item_local, solo_plan, 0, dist, check_every=0)
+            solo_step = make_step(solo_tbl, solo_sampler, uid, solo_pos, n)
+            solo_step()
+            ms_solo = max_over_ranks(time_gpu(solo_step, args.steps, args.warmup, dist) * 1e3)
+            solo_tbl.check_overflow()
+            del solo_tbl, solo_sampler
 
         def measure(chunks):
             """K timed steps (barrier + synchronize on both sides, MAX over ranks) of the sharded step with the step's
@@ -1187,6 +1280,8 @@ def main():
             return max_over_ranks(ms), tbl
 
         ms_step, table = measure(1)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last['out'], suffix=f'_rank{rank}' if rank else '', budget=DUMP_BUDGET_BYTES // world)
         alg = bytes_per_triplet(d, n, popular) * B * n
         achieved = alg / (ms_step * 1e-3) / 1e9
         value = world * B * n / ms_step / 1e3
@@ -1198,12 +1293,14 @@ def main():
             rccl = '.'.join(str(v) for v in torch.cuda.nccl.version())
         except Exception:
             rccl = 'unknown'
+        if args.full:
+            extra.update({
+                'world1_reference': {'ms_per_step': round(ms_solo, 4), 'per_gpu_M_triplets_s': round(B * n / ms_solo / 1e3, 2),
+                                     'what': 'the same per-GPU shape (own row block, same B and n, same step) on every rank ALONE, '
+                                             'timed in this job before the N-rank measurement, MAX over ranks'},
+                'efficiency_vs_world1': round(ms_solo / ms_step, 4)})
         extra.update({
             'per_gpu_M_triplets_s': round(B * n / ms_step / 1e3, 2),
-            'world1_reference': {'ms_per_step': round(ms_solo, 4), 'per_gpu_M_triplets_s': round(B * n / ms_solo / 1e3, 2),
-                                 'what': 'the same per-GPU shape (own row block, same B and n, same step) on every rank ALONE, '
-                                         'timed in this job before the N-rank measurement, MAX over ranks'},
-            'efficiency_vs_world1': round(ms_solo / ms_step, 4),
             'ranks_seen': int(dist.get_world_size()), 'backend': 'staged-gloo (test harness)' if staged else 'nccl (RCCL)',
             'rccl_version': rccl,
             'exchange': {'mode': table.exchange, 'layout': plan.layout, 'slack': table.slack, 'capacity_per_segment': table._cap.get((B, n, 1)),
@@ -1212,7 +1309,8 @@ def main():
                                  '8-byte keys); no split sizes on the host (one calibration launch before the timed region)'}})
         parallelism = f'item-table row-sharded x{world} + RCCL all-to-all (ids out, scores back)'
         workload = (f'two-tower d={d}, {args.items}-item table row-sharded over {world} GPUs, {args.sampler} sampler '
-                    f'neg={n}, InnerProduct + BPR loss, B={B} queries/step/GPU (BASELINE.json configs[3])')
+                    f'neg={n}, InnerProduct + BPR loss, B={B} queries/step/GPU, positives uniform over '
+                    f'{"the items of the Zipf stream" if counts is not None else "all items"} (BASELINE.json configs[3])')
 
         def emit():
             with emit_lock:
@@ -1245,6 +1343,10 @@ def main():
                     put('sharded_n64_ms_per_step', 'sharded_n64', 'ms_per_step')
                     put('other_sampler_ms_per_step', 'other_sampler', 'ms_per_step')
                     print(json.dumps(headline_line(value, ms_step, workload, parallelism, roofline, extra)), flush=True)
+        if not args.full:
+            emit()
+            getattr(dist, 'd', dist).destroy_process_group()
+            return
         # The side figures below run collectives: should one of them stall (a rank that failed alone leaves the others
         # waiting), the measured headline must still come out -- a watchdog thread prints the line and ends the rank.
 
@@ -1381,7 +1483,7 @@ def main():
             n4, b4 = 64, 65536
             g4 = torch.Generator(device=dev).manual_seed(200 + rank)
             uid4 = torch.randint(1, args.users, (b4,), device=dev, generator=g4)
-            pos4 = torch.randint(1, args.items, (b4,), device=dev, generator=g4)
+            pos4 = draw_positives(args.items, counts, (b4,), dev, g4)
             ms4 = timed_max(make_step(table, sampler, uid4, pos4, n4), max(10, args.steps // 4), 5)
             table.check_overflow()
             extra['sharded_n64'] = {'workload': f'same sharded table, neg={n4}, B={b4} queries/step/GPU',

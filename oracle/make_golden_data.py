@@ -4,6 +4,8 @@ Records the reference's outputs (ids, splits, histories, first batches) plus the
 columns of its bundled demo file (recstudio/dataset_demo/ml-100k, a data file the reference ships)
 in compact integer form, so that the product loaders can be checked on any machine."""
 import os
+import shutil
+import zipfile
 
 import numpy as np
 import torch
@@ -75,4 +77,13 @@ def gen_data(out_dir):
         out[f's_trainbatch{i}_keys'] = np.array(sorted(b.keys()))
         for k in ('user_id', 'seqlen', 'in_item_id', 'item_id', 'in_rating', 'rating'):
             out[f's_trainbatch{i}_{k}'] = np_(b[k])
-    np.savez_compressed(os.path.join(out_dir, 'data_ml100k.npz'), **out)
+    # LZMA-compressed members (np.load reads them): with deflate the file would exceed 1 MiB
+    path = os.path.join(out_dir, 'data_ml100k.npz')
+    np.savez(path, **out)
+    with zipfile.ZipFile(path) as z:
+        members = [(i.filename, z.read(i.filename)) for i in z.infolist()]
+    with zipfile.ZipFile(path, 'w', compression=zipfile.ZIP_LZMA) as z:
+        for name, data in members:
+            z.writestr(name, data)
+    # the demo's user file as it ships (tests/test_dataset_golden.py rebuilds the interaction file from the columns above)
+    shutil.copy(os.path.join(demo, 'ml-100k.user'), out_dir)

@@ -1,7 +1,10 @@
 """CPU: the product loaders (recstudio_amd/dataset.py) against fixtures recorded from the
 reference's TripletDataset / SeqDataset on its bundled ml-100k demo file."""
+import hashlib
+import os
+import shutil
+
 import numpy as np
-import pytest
 import torch
 
 from recstudio_amd.dataset import DataSampler, SeqDataset, SortedDataSampler, TripletDataset, synthetic_interactions
@@ -182,12 +185,20 @@ def test_atomic_file_reader_equals_injected_interactions(golden, tmp_path):
     assert len(c.inter_feat['user_id']) == len(d.inter_feat['user_id'])
 
 
-@pytest.mark.skipif(not __import__('os').path.exists('/root/reference/recstudio/dataset_demo/ml-100k/ml-100k.inter'),
-                    reason='the reference checkout is only present in the build container')
-def test_atomic_file_reader_on_the_reference_demo_files(golden):
-    """The reference's own bundled ml-100k atomic files through the product reader == the recorded fixture."""
+# sha256 of the reference's recstudio/dataset_demo/ml-100k/ml-100k.inter
+ML100K_INTER_SHA256 = 'ecb4025ec09d52830e65854de08fd07a79ff7bb9201f7067d753c2f0516e5674'
+
+
+def test_atomic_file_reader_on_the_reference_demo_files(golden, tmp_path):
+    """The reference's own bundled ml-100k atomic files through the product reader == the recorded fixture.  The
+    interaction file is rebuilt from the fixture's raw columns, byte for byte (its digest is the reference file's); the
+    user file is the reference's, kept as tests/golden/ml-100k.user."""
     g = golden('data_ml100k')
-    cfg = {'data_dir': '/root/reference/recstudio/dataset_demo/ml-100k', 'inter_feat_name': 'ml-100k.inter',
+    _write_atomic(tmp_path, g, user_feat=False)
+    (tmp_path / 'demo.inter').rename(tmp_path / 'ml-100k.inter')
+    assert hashlib.sha256((tmp_path / 'ml-100k.inter').read_bytes()).hexdigest() == ML100K_INTER_SHA256
+    shutil.copy(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ml-100k.user'), tmp_path)
+    cfg = {'data_dir': str(tmp_path), 'inter_feat_name': 'ml-100k.inter',
            'inter_feat_header': 0, 'field_separator': '\t', 'user_feat_name': ['ml-100k.user'], 'user_feat_header': 0,
            'low_rating_thres': 3.0}
     seed_everything(2022)

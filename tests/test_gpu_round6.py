@@ -195,7 +195,7 @@ def test_bench_multi_rank_branch_runs_staged_world2():
     env = dict(os.environ, RSA_BENCH_STAGED='1', RSA_BENCH_EXTRAS_DEADLINE_S='240', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-           '--items', '200001', '--users', '20001', '--batch', '512', '--neg', '64']
+           '--items', '200001', '--users', '20001', '--batch', '512', '--neg', '64', '--full']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]

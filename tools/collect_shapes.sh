@@ -2,14 +2,14 @@
 # Run ON THE GPU BOX (through gpurun) from the repo root: for every bench figure that quotes a fraction of a peak, three
 # rocprofv3 passes of that figure alone (tools/prof_shapes.py) -- --kernel-trace --stats, --pmc FETCH_SIZE, --pmc
 # WRITE_SIZE (separate passes: the two counters do not fit one) -- summarised into
-# gpurun_out/profiles_$ROUND/${ROUND}_kernel_profiles.{json,txt} (copy those to profiles/).  PASSES="trace" collects the
+# $RESULTS_DIR/profiles_$ROUND/${ROUND}_kernel_profiles.{json,txt} (default collect_out/; copy those to profiles/).  PASSES="trace" collects the
 # kernel times only.  tools/summarize_shapes.py deletes the rocpd databases of a shape once it has read them.
 export ROUND=${ROUND:-r06}
 SHAPES=${SHAPES:-"headline_N1e7_popular_n64_B65536 N1e7_popular_n64_B4096 N1e7_popular_n64_B16384 N1e8_uniform_n64_B65536 N1e8_uniform_n1024_B4096 N1e8_popular_n64_B65536 ssm_N1e6_popular_n256_B8192 sharded_world1_step sharded_world1_train sgd_step_N1e7_popular_n64_B65536 adam_step_N1e7_popular_n64_B65536 train_step_N1e7_popular_n64_B65536 fullscore_lse_B2048_N1e6 fullscore_top100_B2048_N1e6 softmax_dx_B2048_N1e6 softmax_flash_fwd_B2048_N1e6 softmax_dw_B2048_N1e6 softmax_dq_nowrite_B2048_N1e6 softmax_train_B2048_N1e6 seg_gather_B8192_L50 queue_N1e7_popular_n64_B4096x16 queue_N1e7_popular_n64_B16384x4 sharded_world1_train_ssm sharded_world1_train_nondet"}
 PASSES=${PASSES:-"trace fetch write"}
 REPO=$(pwd)
-OUT=$REPO/gpurun_out/prof_$ROUND
-DST=$REPO/gpurun_out/profiles_$ROUND
+OUT=$REPO/${RESULTS_DIR:-collect_out}/prof_$ROUND
+DST=$REPO/${RESULTS_DIR:-collect_out}/profiles_$ROUND
 mkdir -p $OUT $DST
 export TMPDIR=/tmp
 # (the counter passes need bytes, not times: no output-set selection, no placement probes -- every launch is serialised there)

@@ -30,7 +30,7 @@ out = {}
 lines = []
 c = db('trace')
 if c is not None:
-    lines.append('# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-sweep --steps 100 --warmup 10')
+    lines.append('# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-sweep --steps 100 --warmup 10')
     lines.append(f'{"kernel":96s} {"calls":>6s} {"total_ms":>10s} {"avg_us":>10s} {"pct":>6s}')
     for name, calls, total, avg, pct in c.execute('select name,total_calls,total_duration,average,percentage from top_kernels'):
         lines.append(f'{short(name):96s} {calls:6d} {total / 1e3:10.3f} {avg:10.2f} {pct:6.2f}')
