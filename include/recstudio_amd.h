@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define RSA_ABI_VERSION 11  /* 11: rsa_bpr_sgd_prepare / _apply sort the step's user rows WITH its item rows (one radix sort; item_workspace = rsa_scatter_rows_sorted_workspace_bytes(n_queries, num_neg + 1, n_items), user_workspace unused) and draw the negatives inside that sort's first launch; sampler RSA_SAMPLER_GIVEN accepted (neg_ids is an input);
+#define RSA_ABI_VERSION 12  /* 12: rsa_rows_update_args.lr / beta1 / beta2 / eps are DOUBLES (the caller's own values: 1 - beta and the bias corrections are derived from them in double and rounded to fp32 once; as floats, 1 - float(0.999) was 1.29e-5 short of 0.001 on every touched row);
+                               11: rsa_bpr_sgd_prepare / _apply sort the step's user rows WITH its item rows (one radix sort; item_workspace = rsa_scatter_rows_sorted_workspace_bytes(n_queries, num_neg + 1, n_items), user_workspace unused) and draw the negatives inside that sort's first launch; sampler RSA_SAMPLER_GIVEN accepted (neg_ids is an input);
                                10: rsa_fullscore_lse_grad (flash forward: logsumexp + d/d query in one pass); rsa_fullscore_softmax_dw (d/d items of the full softmax with the softmax tile recomputed on the matrix cores: no
                                [B, N] matrix anywhere in the backward); rsa_fullscore_softmax_dq: probs may be NULL (not written);
                                9: every entry point that took more than 12 positional arguments takes ONE argument block whose first field is its
@@ -402,7 +403,7 @@ typedef struct rsa_rows_update_args {
   float* target;               /* [n_items, dim]: a zeroed dense gradient, or the weight table (upstream = -lr: SGD in place) */
   float* exp_avg;              /* nullable: lazy Adam state (then target = the weights) */
   float* exp_avg_sq;
-  float lr, beta1, beta2, eps;
+  double lr, beta1, beta2, eps; /* as the caller holds them (ABI 12): 1 - beta and the bias corrections are computed in double, rounded to fp32 once */
   int64_t step;
   uint8_t* solo;               /* rsa_sort_step_elements: nullable [n_queries * (num_neg + has_pos)] out */
   void* workspace;

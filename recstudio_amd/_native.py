@@ -7,7 +7,7 @@ fallback: if the library is missing or a symbol is absent, loading raises.
 import ctypes
 import os
 import subprocess
-from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p)
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RSA_LIB: load another build of the same sources (tools/build_variant.sh writes librecstudio_amd_<name>.so next to the
@@ -141,8 +141,8 @@ class RowsUpdateArgs(_Sized):
         ('size', c_int64), ('query', c_void_p), ('query_index', c_void_p), ('n_query_rows', c_int64), ('dim', c_int32),
         ('has_pos', c_int32), ('pos_ids', c_void_p), ('neg_ids', c_void_p), ('n_queries', c_int64), ('num_neg', c_int32),
         ('_pad', c_int32), ('dpos', c_void_p), ('dneg', c_void_p), ('upstream', c_void_p), ('n_items', c_int64),
-        ('pad_row', c_int64), ('target', c_void_p), ('exp_avg', c_void_p), ('exp_avg_sq', c_void_p), ('lr', c_float),
-        ('beta1', c_float), ('beta2', c_float), ('eps', c_float), ('step', c_int64), ('solo', c_void_p), ('workspace', c_void_p),
+        ('pad_row', c_int64), ('target', c_void_p), ('exp_avg', c_void_p), ('exp_avg_sq', c_void_p), ('lr', c_double),
+        ('beta1', c_double), ('beta2', c_double), ('eps', c_double), ('step', c_int64), ('solo', c_void_p), ('workspace', c_void_p),
         ('workspace_bytes', c_int64),
     ]
 
@@ -276,7 +276,7 @@ def build(verbose=False):
     return LIB_PATH
 
 
-ABI_VERSION = 11     # RSA_ABI_VERSION of include/recstudio_amd.h this binding was written against
+ABI_VERSION = 12     # RSA_ABI_VERSION of include/recstudio_amd.h this binding was written against
 
 
 def lib():

@@ -538,15 +538,19 @@ static int scatter_sorted_impl(const float* query, const int64_t* query_index, i
                            n_items, pad_row, target, adam, workspace, workspace_bytes, stream);
 }
 
+// The caller's hyper-parameters arrive as doubles (ABI 12): 1 - beta and the bias corrections are taken from THOSE values, as
+// torch.optim.SparseAdam takes them from its Python floats, and each kernel constant is rounded to fp32 once.  (As floats,
+// 1.f - float(0.999) = 0.0009999871: exp_avg_sq of every touched row 1.29e-5 short, the step size ~6e-6 off in one direction.)
 static AdamArgs adam_of(const rsa_rows_update_args& a) {
   if (a.exp_avg == nullptr) return AdamArgs{nullptr, nullptr, 0.f, 0.f, 0.f, 0.f};
-  const double bc1 = 1.0 - pow((double)a.beta1, (double)a.step), bc2 = 1.0 - pow((double)a.beta2, (double)a.step);
-  return AdamArgs{a.exp_avg, a.exp_avg_sq, 1.f - a.beta1, 1.f - a.beta2, a.eps, (float)((double)a.lr * sqrt(bc2) / bc1)};
+  const double bc1 = 1.0 - pow(a.beta1, (double)a.step), bc2 = 1.0 - pow(a.beta2, (double)a.step);
+  return AdamArgs{a.exp_avg, a.exp_avg_sq, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), (float)a.eps,
+                  (float)(a.lr * sqrt(bc2) / bc1)};
 }
 
 static int check_adam(const rsa_rows_update_args& a, const char* who) {
   if (a.exp_avg == nullptr && a.exp_avg_sq == nullptr) return RSA_OK;
-  RSA_CHECK_ARG(a.exp_avg && a.exp_avg_sq && a.step >= 1 && a.beta1 >= 0.f && a.beta1 < 1.f && a.beta2 >= 0.f && a.beta2 < 1.f,
+  RSA_CHECK_ARG(a.exp_avg && a.exp_avg_sq && a.step >= 1 && a.beta1 >= 0.0 && a.beta1 < 1.0 && a.beta2 >= 0.0 && a.beta2 < 1.0,
                 "%s: bad optimizer state / hyper-parameters", who);
   return RSA_OK;
 }

@@ -644,8 +644,10 @@ def _rows_update_args(target, query, query_index, n_queries, num_neg, dpos, dneg
     return a
 
 
-def _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step):
-    a.exp_avg, a.exp_avg_sq = ptr(_need(exp_avg, torch.float32, 'exp_avg')), ptr(_need(exp_avg_sq, torch.float32, 'exp_avg_sq'))
+def _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, who):
+    a.exp_avg = ptr(_need(exp_avg, torch.float32, who + ': exp_avg'))
+    a.exp_avg_sq = ptr(_need(exp_avg_sq, torch.float32, who + ': exp_avg_sq'))
+    # (doubles, as the caller holds them: the library derives 1 - beta and the bias corrections from these, ABI 12)
     a.lr, a.beta1, a.beta2, a.eps, a.step = float(lr), float(betas[0]), float(betas[1]), float(eps), int(step)
 
 
@@ -695,7 +697,7 @@ def adam_rows_presorted(weight, exp_avg, exp_avg_sq, query, workspace, n_queries
     n_items, dim = weight.shape
     a = _rows_update_args(weight, query, query_index, n_queries, num_neg, dpos, dneg, upstream, pad_row)
     a.has_pos, a.workspace, a.workspace_bytes = int(dpos is not None), ptr(workspace), workspace.numel()
-    _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step)
+    _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, 'adam_rows_presorted')
     nat.check(nat.lib().rsa_rows_update_presorted(ctypes.byref(a), _stream()), 'rsa_rows_update_presorted(adam)')
     return weight
 
@@ -990,8 +992,8 @@ def adam_rows_sorted(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, b
     """rsa_rows_update_sorted with the lazy-Adam state: lazy Adam (torch.optim.SparseAdam's rule) on the rows touched by the step, from the
     factored gradient (ids, coefficients, query rows) -- no gradient tensor."""
     weight = _need(weight, torch.float32, 'weight')
-    exp_avg = _need(exp_avg, torch.float32, 'exp_avg')
-    exp_avg_sq = _need(exp_avg_sq, torch.float32, 'exp_avg_sq')
+    exp_avg = _need(exp_avg, torch.float32, 'adam_rows_sorted: exp_avg')
+    exp_avg_sq = _need(exp_avg_sq, torch.float32, 'adam_rows_sorted: exp_avg_sq')
     query = _need(query, torch.float32, 'query')
     neg_ids = _need(neg_ids, torch.int64, 'neg_ids')
     dneg = _need(dneg, torch.float32, 'dneg')
@@ -1008,6 +1010,6 @@ def adam_rows_sorted(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, b
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=weight.device)
     a = _rows_update_args(weight, query, query_index, M, n, dpos, dneg, upstream, pad_row)
     a.pos_ids, a.neg_ids, a.workspace, a.workspace_bytes = ptr(pos_ids), ptr(neg_ids), ptr(ws), ws_bytes
-    _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step)
+    _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, 'adam_rows_sorted')
     nat.check(nat.lib().rsa_rows_update_sorted(ctypes.byref(a), _stream()), 'rsa_rows_update_sorted(adam)')
     return weight
