@@ -16,7 +16,7 @@
 //    instruction covers whole 128-B lines instead of every 4th dword of four lines.
 //  * general (any n): rows of a tile belong to different queries; q.grad is
 //    accumulated with atomics into a zero-filled [M, d] buffer.
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 
 
 namespace rsa {
@@ -319,17 +319,9 @@ static int launch_bwd(const BwdParams& p, hipStream_t s) {
     const int threads = n >= 256 ? 256 : (int)n;
     hipLaunchKernelGGL((bwd_qu_kernel<LPR, GENERIC>), dim3((unsigned)p.n_queries), dim3(threads), 0, s, p);
   } else {
-    if (p.query_grad) {
-      hipError_t e = hipMemsetAsync(p.query_grad, 0, (size_t)p.n_queries * p.dim * sizeof(float), s);
-      if (e != hipSuccess) {
-        rsa::set_error("rsa_fused_backward: memset failed: %s", hipGetErrorString(e));
-        return RSA_ERR_HIP;
-      }
-    }
+    if (p.query_grad) RSA_CHECK_HIP(hipMemsetAsync(p.query_grad, 0, (size_t)p.n_queries * p.dim * sizeof(float), s), "rsa_fused_backward");
     const int64_t n_tiles = (p.n_queries * n + 63) >> 6;
-    int64_t blocks = (n_tiles + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL((bwd_general_kernel<LPR, GENERIC>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((bwd_general_kernel<LPR, GENERIC>), dim3(grid_1d(n_tiles, 4, 2048)), dim3(256), 0, s, p);
   }
   RSA_CHECK_LAUNCH("rsa_fused_backward");
   return RSA_OK;
@@ -375,27 +367,17 @@ extern "C" int rsa_fused_backward(const rsa_backward_args* a, rsa_stream_t strea
   hipStream_t s = (hipStream_t)stream;
   p.score_mode = a->score_mode;
   if (a->score_mode == RSA_SCORE_COS || a->score_mode == RSA_SCORE_EUC) {
-    if (p.query_grad) {
-      if (hipMemsetAsync(p.query_grad, 0, (size_t)p.n_queries * p.dim * sizeof(float), s) != hipSuccess) {
-        rsa::set_error("rsa_fused_backward: memset failed");
-        return RSA_ERR_HIP;
-      }
-    }
+    if (p.query_grad) RSA_CHECK_HIP(hipMemsetAsync(p.query_grad, 0, (size_t)p.n_queries * p.dim * sizeof(float), s), "rsa_fused_backward");
     const int64_t numel = p.n_queries * (p.num_neg + (p.pos_ids ? 1 : 0));
-    int64_t blocks = (numel + 3) / 4;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(bwd_cos_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(bwd_cos_kernel, dim3(grid_1d(numel, 4, 8192)), dim3(256), 0, s, p);
     RSA_CHECK_LAUNCH("rsa_fused_backward(cosine)");
     return RSA_OK;
   }
   RSA_CHECK_ARG(a->score_mode == RSA_SCORE_IP, "rsa_fused_backward: unknown score_mode %d", a->score_mode);
-  switch (a->dim) {
-    case 32: return launch_bwd<8, false>(p, s);
-    case 64: return launch_bwd<16, false>(p, s);
-    case 128: return launch_bwd<32, false>(p, s);
-    case 256: return launch_bwd<64, false>(p, s);
-    default: return launch_bwd<64, true>(p, s);
-  }
+  int rc = RSA_OK;
+  if (!dispatch_dim<32, 64, 128, 256>(a->dim, [&](auto D) { rc = launch_bwd<D() / 4, false>(p, s); }))
+    rc = launch_bwd<64, true>(p, s);      // any other multiple of 4: the generic-width kernels
+  return rc;
 }
 
 extern "C" int rsa_scatter_add_rows(const float* src, const int64_t* ids, int64_t numel, int32_t dim, float* dst,
@@ -403,9 +385,7 @@ extern "C" int rsa_scatter_add_rows(const float* src, const int64_t* ids, int64_
   RSA_CHECK_ARG(numel >= 0 && dim >= 1 && n_rows >= 1, "rsa_scatter_add_rows: bad sizes");
   if (numel == 0) return RSA_OK;
   RSA_CHECK_ARG(src && ids && dst, "rsa_scatter_add_rows: null pointer");
-  int64_t blocks = (numel + 3) / 4;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(scatter_add_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, ids,
+  hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(grid_1d(numel, 4, 2048)), dim3(256), 0, (hipStream_t)stream, src, ids,
                      numel, (int)dim, dst, n_rows);
   RSA_CHECK_LAUNCH("rsa_scatter_add_rows");
   return RSA_OK;

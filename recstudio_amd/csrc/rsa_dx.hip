@@ -16,7 +16,7 @@
 //     kernel exists to stream -- goes straight to registers, a whole step group (16 dwords per lane) ahead of its use.
 //
 // flops 2 B N D; bytes 4 B N (probs once) + 4 N D (result once).  Bound: fp32 matrix peak (157.3 TFLOP/s) above B ~ 64.
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 
 namespace rsa {
 
@@ -198,22 +198,18 @@ extern "C" int rsa_probs_t_query(const float* probs, int64_t n_query, int64_t n_
   RSA_CHECK_ARG(out != nullptr, "rsa_probs_t_query: out is null");
   hipStream_t s = (hipStream_t)stream;
   if (n_query == 0) {
-    if (hipMemsetAsync(out, 0, (size_t)n_cols * dim * sizeof(float), s) != hipSuccess) {
-      rsa::set_error("rsa_probs_t_query: memset failed");
-      return RSA_ERR_HIP;
-    }
+    RSA_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)n_cols * dim * sizeof(float), s), "rsa_probs_t_query");
     return RSA_OK;
   }
   RSA_CHECK_ARG(probs && query, "rsa_probs_t_query: null pointer");
   RSA_CHECK_ARG(((uintptr_t)query & 15) == 0 && ((uintptr_t)out & 15) == 0, "rsa_probs_t_query: query / out must be 16-byte aligned");
   const dim3 grid((unsigned)((n_cols + 128 * RSA_DX_RT - 1) / (128 * RSA_DX_RT))), block(256);
-  switch (dim) {
-    case 32: hipLaunchKernelGGL(probs_t_query_kernel<32>, grid, block, 0, s, probs, n_cols, ld, query, n_query, out); break;
-    case 64: hipLaunchKernelGGL(probs_t_query_kernel<64>, grid, block, 0, s, probs, n_cols, ld, query, n_query, out); break;
-    case 128: hipLaunchKernelGGL(probs_t_query_kernel<128>, grid, block, 0, s, probs, n_cols, ld, query, n_query, out); break;
-    default:
-      rsa::set_error("rsa_probs_t_query: dim=%d: built for dim in {32, 64, 128}", dim);
-      return RSA_ERR_UNSUPPORTED;
+  const bool built = dispatch_dim<32, 64, 128>(dim, [&](auto D) {
+    hipLaunchKernelGGL(probs_t_query_kernel<D()>, grid, block, 0, s, probs, n_cols, ld, query, n_query, out);
+  });
+  if (!built) {
+    rsa::set_error("rsa_probs_t_query: dim=%d: built for dim in {32, 64, 128}", dim);
+    return RSA_ERR_UNSUPPORTED;
   }
   RSA_CHECK_LAUNCH("rsa_probs_t_query");
   return RSA_OK;
@@ -409,10 +405,7 @@ extern "C" int rsa_fullscore_softmax_dw(const float* item_table, int64_t n_items
   hipStream_t s = (hipStream_t)stream;
   const int64_t n_cols = n_items - 1;
   // row 0 (the padding row) takes no part in the softmax: its gradient is zero; so is everything for an empty batch
-  if (hipMemsetAsync(item_grad, 0, (size_t)(n_query == 0 ? n_items : 1) * dim * sizeof(float), s) != hipSuccess) {
-    rsa::set_error("rsa_fullscore_softmax_dw: memset failed");
-    return RSA_ERR_HIP;
-  }
+  RSA_CHECK_HIP(hipMemsetAsync(item_grad, 0, (size_t)(n_query == 0 ? n_items : 1) * dim * sizeof(float), s), "rsa_fullscore_softmax_dw");
   if (n_query == 0) return RSA_OK;
   RSA_CHECK_ARG(query && lse, "rsa_fullscore_softmax_dw: null pointer");
   RSA_CHECK_ARG(((uintptr_t)query & 15) == 0 && ((uintptr_t)item_table & 15) == 0 && ((uintptr_t)item_grad & 15) == 0,
@@ -420,13 +413,12 @@ extern "C" int rsa_fullscore_softmax_dw(const float* item_table, int64_t n_items
   const dim3 grid((unsigned)((n_cols + 127) / 128)), block(256);
   const float* items = item_table + dim;      // rows 1 .. n_items - 1
   float* out = item_grad + dim;
-  switch (dim) {
-    case 32: hipLaunchKernelGGL(softmax_dw_kernel<32>, grid, block, 0, s, items, n_cols, query, n_query, lse, row_scale, out); break;
-    case 64: hipLaunchKernelGGL(softmax_dw_kernel<64>, grid, block, 0, s, items, n_cols, query, n_query, lse, row_scale, out); break;
-    case 128: hipLaunchKernelGGL(softmax_dw_kernel<128>, grid, block, 0, s, items, n_cols, query, n_query, lse, row_scale, out); break;
-    default:
-      rsa::set_error("rsa_fullscore_softmax_dw: dim=%d: built for dim in {32, 64, 128}", dim);
-      return RSA_ERR_UNSUPPORTED;
+  const bool built = dispatch_dim<32, 64, 128>(dim, [&](auto D) {
+    hipLaunchKernelGGL(softmax_dw_kernel<D()>, grid, block, 0, s, items, n_cols, query, n_query, lse, row_scale, out);
+  });
+  if (!built) {
+    rsa::set_error("rsa_fullscore_softmax_dw: dim=%d: built for dim in {32, 64, 128}", dim);
+    return RSA_ERR_UNSUPPORTED;
   }
   RSA_CHECK_LAUNCH("rsa_fullscore_softmax_dw");
   return RSA_OK;

@@ -25,7 +25,7 @@
 // scores are far from exchangeable across the sampled tiles) is flagged and recomputed exactly by
 // D. a per-row radix select that evaluates the dot products on the fly.  The result is always the exact
 // top-k (ties -> smaller id).  With `scores` given, the radix select runs on the materialised rows.
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 #include <type_traits>
 
 #ifndef RSA_FS_MIN_BLOCKS
@@ -958,26 +958,50 @@ static TopkPlan plan_topk(int64_t n_items, int32_t k, bool scores_given) {
   return pl;
 }
 
-static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+// The workspace of rsa_fullscore for a top-k of k (0: no top-k, or the caller's `scores` hold the rows): the plan its regions
+// follow from, and the regions.
+struct FullscoreLayout {
+  TopkPlan pl;
+  int64_t splits;
+  float2* part;           // lse partials
+  float2* gmax;           // filter: group maxima of the sample pass
+  float* thr;             //   thresholds
+  int32_t* flags;
+  int32_t* seg_cnt;       //   per-segment counts
+  float2* cand;           //   candidates {score, id}
+  int32_t* ovf_cnt;       //   overflow lists
+  float* ovf_val;
+  int32_t* ovf_idx;
+  float* score_rows;      // no filter: dense score rows
+};
+
+static FullscoreLayout carve_fullscore(Carver& ws, int64_t n_query, int64_t n_items, int32_t k) {
+  FullscoreLayout L{};
+  L.pl = plan_topk(n_items, k, k <= 0);
+  L.splits = fullscore_splits(n_query, n_items - 1, L.pl.filter ? L.pl.min_splits : 1);
+  L.part = ws.take<float2>(n_query * L.splits);
+  if (k <= 0) return L;
+  if (!L.pl.filter) {
+    L.score_rows = ws.take<float>(n_query * (n_items - 1));
+    return L;
+  }
+  const int64_t n_seg = L.splits * 2;
+  L.gmax = ws.take<float2>(n_query * L.pl.groups);
+  L.thr = ws.take<float>(n_query);
+  L.flags = ws.take<int32_t>(n_query);
+  L.seg_cnt = ws.take<int32_t>(n_query * n_seg);
+  L.cand = ws.take<float2>(n_query * n_seg * (int64_t)SEG);
+  L.ovf_cnt = ws.take<int32_t>(n_query);
+  L.ovf_val = ws.take<float>(n_query * (int64_t)OVF);
+  L.ovf_idx = ws.take<int32_t>(n_query * (int64_t)OVF);
+  return L;
+}
 
 extern "C" int64_t rsa_fullscore_workspace_bytes(int64_t n_query, int64_t n_items, int32_t k) {
   if (n_query <= 0 || n_items <= 1) return 0;
-  const TopkPlan pl = plan_topk(n_items, k, k <= 0);
-  int64_t bytes = align256(n_query * fullscore_splits(n_query, n_items - 1, pl.filter ? pl.min_splits : 1) *
-                           (int64_t)sizeof(float2));   // lse partials
-  if (k > 0) {
-    if (pl.filter) {
-      bytes += align256(n_query * pl.groups * (int64_t)sizeof(float2));   // group maxima of the sample pass
-      const int64_t n_seg = fullscore_splits(n_query, n_items - 1, pl.min_splits) * 2;
-      bytes += 2 * align256(n_query * 4);                       // thresholds, flags
-      bytes += align256(n_query * n_seg * 4);                   // per-segment counts
-      bytes += align256(n_query * n_seg * (int64_t)SEG * 8);    // candidates {score, id}
-      bytes += align256(n_query * 4) + 2 * align256(n_query * (int64_t)OVF * 4);   // overflow lists
-    } else {
-      bytes += align256(n_query * (n_items - 1) * (int64_t)sizeof(float));   // dense score rows
-    }
-  }
-  return bytes + 256;
+  Carver sizing(nullptr);
+  carve_fullscore(sizing, n_query, n_items, k);
+  return align256(sizing.bytes()) + 256;
 }
 
 template <int D, int MODE>
@@ -985,136 +1009,103 @@ static void launch_gemm(dim3 grid, hipStream_t s, const float* item_table, int64
                         int64_t n_query, float* scores, int64_t score_ld, float2* lse_part, int splits, int64_t per,
                         int64_t tile_stride, int64_t n_positions, FilterArgs flt) {
   const bool L = lse_part != nullptr, S = scores != nullptr, F = flt.thr != nullptr;
-#define RSA_GEMM(LL, SS, FF)                                                                                             \
-  hipLaunchKernelGGL((fullscore_kernel<D, LL, SS, FF, MODE>), grid, dim3(256), 0, s, item_table, n_items, query, n_query, \
-                     scores, score_ld, lse_part, splits, per, tile_stride, n_positions, flt)
-  if (L && !S && !F) RSA_GEMM(true, false, false);        // training: logsumexp only
-  else if (L && !S && F) RSA_GEMM(true, false, true);     // eval: logsumexp + candidate filter
-  else if (!L && !S && F) RSA_GEMM(false, false, true);   // eval: candidate filter
-  else if (!L && S && !F) RSA_GEMM(false, true, false);   // materialised scores / threshold sample
-  else if (L && S && !F) RSA_GEMM(true, true, false);     // materialised scores + logsumexp
-  else RSA_GEMM(true, true, true);
-#undef RSA_GEMM
+  auto gemm = [&](auto LL, auto SS, auto FF) {
+    hipLaunchKernelGGL((fullscore_kernel<D, LL(), SS(), FF(), MODE>), grid, dim3(256), 0, s, item_table, n_items, query, n_query,
+                       scores, score_ld, lse_part, splits, per, tile_stride, n_positions, flt);
+  };
+  constexpr std::true_type Y{};
+  constexpr std::false_type N{};
+  if (L && !S && !F) gemm(Y, N, N);        // training: logsumexp only
+  else if (L && !S && F) gemm(Y, N, Y);    // eval: logsumexp + candidate filter
+  else if (!L && !S && F) gemm(N, N, Y);   // eval: candidate filter
+  else if (!L && S && !F) gemm(N, Y, N);   // materialised scores / threshold sample
+  else if (L && S && !F) gemm(Y, Y, N);    // materialised scores + logsumexp
+  else gemm(Y, Y, Y);
 }
 
-static void gemm_dispatch(int dim, int mode, dim3 grid, hipStream_t s, const float* item_table, int64_t n_items,
-                          const float* query, int64_t n_query, float* scores, int64_t score_ld, float2* lse_part,
-                          int splits, int64_t per, int64_t tile_stride, int64_t n_positions, FilterArgs flt) {
-#define RSA_DIM(DD, MM) launch_gemm<DD, MM>(grid, s, item_table, n_items, query, n_query, scores, score_ld, lse_part, splits, per, tile_stride, n_positions, flt)
-#define RSA_MODE(DD)                       \
-  if (mode == RSA_SCORE_COS) RSA_DIM(DD, 1); \
-  else if (mode == RSA_SCORE_EUC) RSA_DIM(DD, 2); \
-  else RSA_DIM(DD, 0)
-  switch (dim) {
-    case 32: RSA_MODE(32); break;
-    case 64: RSA_MODE(64); break;
-    default: RSA_MODE(128); break;
-  }
-#undef RSA_MODE
-#undef RSA_DIM
+// launch_gemm<dim, mode>(args...); the callers have checked dim (each with its own message) and the score mode
+template <class... Args>
+static void gemm_dispatch(int dim, int mode, Args... args) {
+  dispatch_dim<32, 64, 128>(dim, [&](auto D) {
+    dispatch_int<RSA_SCORE_IP, RSA_SCORE_COS, RSA_SCORE_EUC>(mode, [&](auto MODE) { launch_gemm<D(), MODE()>(args...); });
+  });
 }
-
-static int fullscore_impl(const float* item_table, int64_t n_items, int32_t dim, const float* query,
-                          int64_t n_query, float* scores, float* lse, float* topk_val, int64_t* topk_idx, int32_t k,
-                          int32_t score_mode, const float* item_aux, const float* query_aux,
-                          void* workspace, int64_t workspace_bytes, rsa_stream_t stream);
 
 extern "C" int rsa_fullscore(const rsa_fullscore_args* args, rsa_stream_t stream) {
   rsa_fullscore_args a;
   if (int rc = load_args(a, args, "rsa_fullscore")) return rc;
-  return fullscore_impl(a.item_table, a.n_items, a.dim, a.query, a.n_query, a.scores, a.lse, a.topk_val, a.topk_idx, a.k,
-                        a.score_mode, a.item_aux, a.query_aux, a.workspace, a.workspace_bytes, stream);
-}
-
-static int fullscore_impl(const float* item_table, int64_t n_items, int32_t dim, const float* query,
-                          int64_t n_query, float* scores, float* lse, float* topk_val, int64_t* topk_idx, int32_t k,
-                          int32_t score_mode, const float* item_aux, const float* query_aux,
-                          void* workspace, int64_t workspace_bytes, rsa_stream_t stream) {
-  RSA_CHECK_ARG(n_query >= 0 && n_items >= 2, "rsa_fullscore: need n_items >= 2");
-  if (n_query == 0) return RSA_OK;
-  RSA_CHECK_ARG(item_table && query, "rsa_fullscore: item_table/query is null");
-  RSA_CHECK_ARG(scores || lse || k > 0, "rsa_fullscore: no output requested");
-  RSA_CHECK_ARG(k >= 0 && k <= 1024 && (int64_t)k <= n_items - 1, "rsa_fullscore: k must be in [0, min(1024, n_items-1)]");
-  RSA_CHECK_ARG(k == 0 || (topk_val && topk_idx), "rsa_fullscore: topk outputs are null");
-  RSA_CHECK_ARG(score_mode >= RSA_SCORE_IP && score_mode <= RSA_SCORE_EUC, "rsa_fullscore: unknown score_mode %d", score_mode);
-  RSA_CHECK_ARG(score_mode == RSA_SCORE_IP || (item_aux && query_aux && ((uintptr_t)item_aux & 15) == 0),
+  RSA_CHECK_ARG(a.n_query >= 0 && a.n_items >= 2, "rsa_fullscore: need n_items >= 2");
+  if (a.n_query == 0) return RSA_OK;
+  RSA_CHECK_ARG(a.item_table && a.query, "rsa_fullscore: item_table/query is null");
+  RSA_CHECK_ARG(a.scores || a.lse || a.k > 0, "rsa_fullscore: no output requested");
+  RSA_CHECK_ARG(a.k >= 0 && a.k <= 1024 && (int64_t)a.k <= a.n_items - 1, "rsa_fullscore: k must be in [0, min(1024, n_items-1)]");
+  RSA_CHECK_ARG(a.k == 0 || (a.topk_val && a.topk_idx), "rsa_fullscore: topk outputs are null");
+  RSA_CHECK_ARG(a.score_mode >= RSA_SCORE_IP && a.score_mode <= RSA_SCORE_EUC, "rsa_fullscore: unknown score_mode %d", a.score_mode);
+  RSA_CHECK_ARG(a.score_mode == RSA_SCORE_IP || (a.item_aux && a.query_aux && ((uintptr_t)a.item_aux & 15) == 0),
                 "rsa_fullscore: cosine / Euclidean scores need item_aux (16-byte aligned) and query_aux");
-  if (dim != 32 && dim != 64 && dim != 128) {
-    rsa::set_error("rsa_fullscore: dim=%d: the MFMA full-score kernel is built for dim in {32, 64, 128}", dim);
+  if (a.dim != 32 && a.dim != 64 && a.dim != 128) {
+    rsa::set_error("rsa_fullscore: dim=%d: the MFMA full-score kernel is built for dim in {32, 64, 128}", a.dim);
     return RSA_ERR_UNSUPPORTED;
   }
-  const int64_t need = rsa_fullscore_workspace_bytes(n_query, n_items, scores ? 0 : k);
-  RSA_CHECK_ARG(workspace != nullptr && workspace_bytes >= need, "rsa_fullscore: workspace too small (%lld < %lld)",
-                (long long)workspace_bytes, (long long)need);
+  const int32_t ws_k = a.scores ? 0 : a.k;
+  const int64_t need = rsa_fullscore_workspace_bytes(a.n_query, a.n_items, ws_k);
+  RSA_CHECK_ARG(a.workspace != nullptr && a.workspace_bytes >= need, "rsa_fullscore: workspace too small (%lld < %lld)",
+                (long long)a.workspace_bytes, (long long)need);
   hipStream_t s = (hipStream_t)stream;
-  const int64_t n_cols = n_items - 1;
+  const int64_t n_query = a.n_query, n_cols = a.n_items - 1;
   const unsigned groups = (unsigned)((n_query + QB - 1) / QB);
-  const TopkPlan pl = plan_topk(n_items, k, scores != nullptr);
-  const int64_t splits = fullscore_splits(n_query, n_cols, pl.filter ? pl.min_splits : 1);
-  const int64_t per = ((n_cols + splits - 1) / splits + TI - 1) / TI * TI;
+  Carver ws(a.workspace);
+  const FullscoreLayout W = carve_fullscore(ws, n_query, a.n_items, ws_k);
+  const TopkPlan& pl = W.pl;
+  const int64_t per = ((n_cols + W.splits - 1) / W.splits + TI - 1) / TI * TI;
   const int64_t splits_used = (n_cols + per - 1) / per;
-  char* ws = reinterpret_cast<char*>(workspace);
-  float2* part = reinterpret_cast<float2*>(ws);
-  ws += align256(n_query * splits * (int64_t)sizeof(float2));
-  float2* lp = lse ? part : nullptr;
-  const FilterArgs no_filter{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, item_aux, query_aux, nullptr};
+  float2* lp = a.lse ? W.part : nullptr;
+  const FilterArgs no_filter{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a.item_aux, a.query_aux, nullptr};
 
   if (pl.filter) {
-    float2* gmax = reinterpret_cast<float2*>(ws);      ws += align256(n_query * pl.groups * (int64_t)sizeof(float2));
     const int64_t n_seg = splits_used * 2;
-    float* thr = reinterpret_cast<float*>(ws);         ws += align256(n_query * 4);
-    int32_t* flags = reinterpret_cast<int32_t*>(ws);   ws += align256(n_query * 4);
-    int32_t* seg_cnt = reinterpret_cast<int32_t*>(ws); ws += align256(n_query * splits * 2 * 4);
-    float2* cand = reinterpret_cast<float2*>(ws);      ws += align256(n_query * splits * 2 * (int64_t)SEG * 8);
-    int32_t* ovf_cnt = reinterpret_cast<int32_t*>(ws);  ws += align256(n_query * 4);
-    float* ovf_val = reinterpret_cast<float*>(ws);      ws += align256(n_query * (int64_t)OVF * 4);
-    int32_t* ovf_idx = reinterpret_cast<int32_t*>(ws);
     // A. sample GEMM (the logsumexp instantiation: its per-range running maximum is the group maximum) + per-query threshold
     const int64_t sper = GROUP_TILES * TI;
-    gemm_dispatch(dim, score_mode, dim3((unsigned)pl.groups, groups), s, item_table, n_items, query, n_query, nullptr,
-                  pl.sample_items, gmax, (int)pl.groups, sper, pl.tile_stride, pl.sample_items, no_filter);
+    gemm_dispatch(a.dim, a.score_mode, dim3((unsigned)pl.groups, groups), s, a.item_table, a.n_items, a.query, n_query, nullptr,
+                  pl.sample_items, W.gmax, (int)pl.groups, sper, pl.tile_stride, pl.sample_items, no_filter);
     RSA_CHECK_LAUNCH("rsa_fullscore(sample gemm)");
-    hipLaunchKernelGGL(group_threshold_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, s, gmax, n_query, (int)pl.groups,
-                       (int)pl.groups, (int)pl.j, thr);
+    hipLaunchKernelGGL(group_threshold_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, s, W.gmax, n_query, (int)pl.groups,
+                       (int)pl.groups, (int)pl.j, W.thr);
     RSA_CHECK_LAUNCH("rsa_fullscore(threshold)");
     // B. full GEMM with the filter epilogue (+ fused logsumexp)
-    if (hipMemsetAsync(ovf_cnt, 0, (size_t)n_query * 4, s) != hipSuccess) {
-      rsa::set_error("rsa_fullscore: memset failed");
-      return RSA_ERR_HIP;
-    }
-    const FilterArgs flt{thr, seg_cnt, cand, nullptr, nullptr, ovf_cnt, ovf_val, ovf_idx, item_aux, query_aux, nullptr};
-    gemm_dispatch(dim, score_mode, dim3((unsigned)splits_used, groups), s, item_table, n_items, query, n_query, nullptr, n_cols, lp,
-                  (int)splits_used, per, 1, n_cols, flt);
+    RSA_CHECK_HIP(hipMemsetAsync(W.ovf_cnt, 0, (size_t)n_query * 4, s), "rsa_fullscore");
+    const FilterArgs flt{W.thr, W.seg_cnt, W.cand, nullptr, nullptr, W.ovf_cnt, W.ovf_val, W.ovf_idx, a.item_aux, a.query_aux, nullptr};
+    gemm_dispatch(a.dim, a.score_mode, dim3((unsigned)splits_used, groups), s, a.item_table, a.n_items, a.query, n_query, nullptr,
+                  n_cols, lp, (int)splits_used, per, 1, n_cols, flt);
     RSA_CHECK_LAUNCH("rsa_fullscore(gemm+filter)");
     // C. exact select over the candidates;  D. exact recompute of flagged rows
     SelectArgs ca{};
-    ca.cand = cand; ca.seg_cnt = seg_cnt; ca.n_seg = (int32_t)n_seg; ca.flags = flags;
-    ca.ovf_cnt = ovf_cnt; ca.ovf_val = ovf_val; ca.ovf_idx = ovf_idx;
-    hipLaunchKernelGGL(topk_row_kernel<SEL_CAND>, dim3((unsigned)n_query), dim3(1024), 0, s, ca, (int)k, topk_val,
-                       topk_idx);
+    ca.cand = W.cand; ca.seg_cnt = W.seg_cnt; ca.n_seg = (int32_t)n_seg; ca.flags = W.flags;
+    ca.ovf_cnt = W.ovf_cnt; ca.ovf_val = W.ovf_val; ca.ovf_idx = W.ovf_idx;
+    hipLaunchKernelGGL(topk_row_kernel<SEL_CAND>, dim3((unsigned)n_query), dim3(1024), 0, s, ca, (int)a.k, a.topk_val,
+                       a.topk_idx);
     SelectArgs ra{};
-    ra.flags = flags; ra.n_cols = n_cols; ra.item_table = item_table; ra.query = query; ra.dim = dim; ra.values = query;
-    ra.score_mode = score_mode; ra.item_aux = item_aux; ra.query_aux = query_aux;
-    hipLaunchKernelGGL(topk_row_kernel<SEL_RECOMPUTE>, dim3((unsigned)n_query), dim3(1024), 0, s, ra, (int)k, topk_val,
-                       topk_idx);
+    ra.flags = W.flags; ra.n_cols = n_cols; ra.item_table = a.item_table; ra.query = a.query; ra.dim = a.dim; ra.values = a.query;
+    ra.score_mode = a.score_mode; ra.item_aux = a.item_aux; ra.query_aux = a.query_aux;
+    hipLaunchKernelGGL(topk_row_kernel<SEL_RECOMPUTE>, dim3((unsigned)n_query), dim3(1024), 0, s, ra, (int)a.k, a.topk_val,
+                       a.topk_idx);
     RSA_CHECK_LAUNCH("rsa_fullscore(select)");
   } else {
-    float* score_rows = scores;
-    if (k > 0 && scores == nullptr) score_rows = reinterpret_cast<float*>(ws);
-    gemm_dispatch(dim, score_mode, dim3((unsigned)splits_used, groups), s, item_table, n_items, query, n_query, score_rows,
+    float* score_rows = a.scores ? a.scores : W.score_rows;      // (null: logsumexp only)
+    gemm_dispatch(a.dim, a.score_mode, dim3((unsigned)splits_used, groups), s, a.item_table, a.n_items, a.query, n_query, score_rows,
                   n_cols, lp, (int)splits_used, per, 1, n_cols, no_filter);
     RSA_CHECK_LAUNCH("rsa_fullscore(gemm)");
-    if (k > 0) {
+    if (a.k > 0) {
       SelectArgs da{};
       da.values = score_rows; da.ld = n_cols; da.n_cols = n_cols; da.idx_base = 1;
-      hipLaunchKernelGGL(topk_row_kernel<SEL_DENSE>, dim3((unsigned)n_query), dim3(1024), 0, s, da, (int)k, topk_val,
-                         topk_idx);
+      hipLaunchKernelGGL(topk_row_kernel<SEL_DENSE>, dim3((unsigned)n_query), dim3(1024), 0, s, da, (int)a.k, a.topk_val,
+                         a.topk_idx);
       RSA_CHECK_LAUNCH("rsa_fullscore(topk)");
     }
   }
-  if (lse) {
-    hipLaunchKernelGGL(lse_merge_kernel, dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0, s, part, n_query,
-                       (int)splits_used, lse);
+  if (a.lse) {
+    hipLaunchKernelGGL(lse_merge_kernel, dim3((unsigned)((n_query + 255) / 256)), dim3(256), 0, s, W.part, n_query,
+                       (int)splits_used, a.lse);
     RSA_CHECK_LAUNCH("rsa_fullscore(lse)");
   }
   return RSA_OK;
@@ -1162,11 +1153,18 @@ static void softmax_plan(int64_t n_query, int64_t n_items, int64_t& per, int64_t
   splits_used = (n_cols + per - 1) / per;
 }
 
-extern "C" int64_t rsa_fullscore_softmax_dq_workspace_bytes(int64_t n_query, int64_t n_items, int32_t dim) {
-  if (n_query <= 0 || n_items <= 1 || dim <= 0) return 0;
+// per item range: a [n_query, dim] partial of the query gradient
+static float* carve_dq(Carver& ws, int64_t n_query, int64_t n_items, int32_t dim) {
   int64_t per, splits_used;
   softmax_plan(n_query, n_items, per, splits_used);
-  return splits_used * n_query * (int64_t)dim * (int64_t)sizeof(float) + 256;
+  return ws.take<float>(splits_used * n_query * (int64_t)dim);
+}
+
+extern "C" int64_t rsa_fullscore_softmax_dq_workspace_bytes(int64_t n_query, int64_t n_items, int32_t dim) {
+  if (n_query <= 0 || n_items <= 1 || dim <= 0) return 0;
+  Carver sizing(nullptr);
+  carve_dq(sizing, n_query, n_items, dim);
+  return sizing.bytes() + 256;
 }
 
 extern "C" int rsa_fullscore_softmax_dq(const float* item_table, int64_t n_items, int32_t dim, const float* query,
@@ -1186,24 +1184,18 @@ extern "C" int rsa_fullscore_softmax_dq(const float* item_table, int64_t n_items
   const unsigned groups = (unsigned)((n_query + QB - 1) / QB);
   int64_t per, splits_used;
   softmax_plan(n_query, n_items, per, splits_used);
-  float* part = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+  Carver ws(workspace);
+  float* part = carve_dq(ws, n_query, n_items, dim);
   const FilterArgs ep{nullptr, nullptr, nullptr, lse, row_scale, nullptr, nullptr, nullptr, nullptr, nullptr, part};
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)splits_used, groups);
   // probs == NULL: the softmax tile only feeds the second product (nothing of [B, N] is written)
-#define RSA_DQ(DD)                                                                                                                  \
-  if (probs != nullptr)                                                                                                             \
-    hipLaunchKernelGGL((fullscore_kernel<DD, false, true, false, 0, true>), grid, dim3(256), 0, s, item_table, n_items, query,       \
-                       n_query, probs, n_cols, (float2*)nullptr, (int)splits_used, per, (int64_t)1, n_cols, ep);                     \
-  else                                                                                                                              \
-    hipLaunchKernelGGL((fullscore_kernel<DD, false, true, false, 0, true, false>), grid, dim3(256), 0, s, item_table, n_items, query, \
-                       n_query, probs, n_cols, (float2*)nullptr, (int)splits_used, per, (int64_t)1, n_cols, ep)
-  switch (dim) {
-    case 32: RSA_DQ(32); break;
-    case 64: RSA_DQ(64); break;
-    default: RSA_DQ(128); break;
-  }
-#undef RSA_DQ
+  dispatch_dim<32, 64, 128>(dim, [&](auto D) {
+    dispatch_bool(probs != nullptr, [&](auto PROBS) {
+      hipLaunchKernelGGL((fullscore_kernel<D(), false, true, false, 0, true, PROBS()>), grid, dim3(256), 0, s, item_table, n_items,
+                         query, n_query, probs, n_cols, (float2*)nullptr, (int)splits_used, per, (int64_t)1, n_cols, ep);
+    });
+  });
   const int64_t n4 = n_query * dim / 4;
   hipLaunchKernelGGL(dq_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(part), (int)splits_used, n4, reinterpret_cast<float4*>(query_grad));
@@ -1236,11 +1228,26 @@ __global__ __launch_bounds__(256) void flash_merge_kernel(const float2* __restri
   if (i - q * d4 == 0) lse[q] = m + logf(den);
 }
 
-extern "C" int64_t rsa_fullscore_lse_grad_workspace_bytes(int64_t n_query, int64_t n_items, int32_t dim) {
-  if (n_query <= 0 || n_items <= 1 || dim <= 0) return 0;
+// per (query, item range): the flash forward's {reference, sum} record and its [dim] partial of softmax @ items
+struct LseGradLayout {
+  float2* part;
+  float* dq_part;
+};
+
+static LseGradLayout carve_lse_grad(Carver& ws, int64_t n_query, int64_t n_items, int32_t dim) {
   int64_t per, splits_used;
   softmax_plan(n_query, n_items, per, splits_used);
-  return splits_used * n_query * (int64_t)dim * (int64_t)sizeof(float) + align256(splits_used * n_query * (int64_t)sizeof(float2)) + 512;
+  LseGradLayout L;
+  L.part = ws.take<float2>(splits_used * n_query);
+  L.dq_part = ws.take<float>(splits_used * n_query * (int64_t)dim);
+  return L;
+}
+
+extern "C" int64_t rsa_fullscore_lse_grad_workspace_bytes(int64_t n_query, int64_t n_items, int32_t dim) {
+  if (n_query <= 0 || n_items <= 1 || dim <= 0) return 0;
+  Carver sizing(nullptr);
+  carve_lse_grad(sizing, n_query, n_items, dim);
+  return sizing.bytes() + 512;
 }
 
 extern "C" int rsa_fullscore_lse_grad(const float* item_table, int64_t n_items, int32_t dim, const float* query, int64_t n_query,
@@ -1258,21 +1265,17 @@ extern "C" int rsa_fullscore_lse_grad(const float* item_table, int64_t n_items, 
   const unsigned groups = (unsigned)((n_query + QB - 1) / QB);
   int64_t per, splits_used;
   softmax_plan(n_query, n_items, per, splits_used);
-  char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-  float2* part = reinterpret_cast<float2*>(ws);
-  float* dq_part = reinterpret_cast<float*>(ws + align256(splits_used * n_query * (int64_t)sizeof(float2)));
+  Carver ws(workspace);
+  const LseGradLayout W = carve_lse_grad(ws, n_query, n_items, dim);
+  float2* part = W.part;
+  float* dq_part = W.dq_part;
   const FilterArgs ep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dq_part};
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)splits_used, groups);
-#define RSA_FL(DD)                                                                                                                       \
-  hipLaunchKernelGGL((fullscore_kernel<DD, false, true, false, 0, true, false, true>), grid, dim3(256), 0, s, item_table, n_items, query, \
-                     n_query, (float*)nullptr, n_cols, part, (int)splits_used, per, (int64_t)1, n_cols, ep)
-  switch (dim) {
-    case 32: RSA_FL(32); break;
-    case 64: RSA_FL(64); break;
-    default: RSA_FL(128); break;
-  }
-#undef RSA_FL
+  dispatch_dim<32, 64, 128>(dim, [&](auto D) {
+    hipLaunchKernelGGL((fullscore_kernel<D(), false, true, false, 0, true, false, true>), grid, dim3(256), 0, s, item_table, n_items,
+                       query, n_query, (float*)nullptr, n_cols, part, (int)splits_used, per, (int64_t)1, n_cols, ep);
+  });
   const int64_t n4 = n_query * dim / 4;
   hipLaunchKernelGGL(flash_merge_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, part, dq_part, (int)splits_used, n_query,
                      (int)dim, lse, query_grad);

@@ -18,7 +18,7 @@
 //
 // The kernel is HBM-bound: 4*D bytes of random row traffic per element against
 // ~2*D flops; see DESIGN.md for the byte model.
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 #include "rsa_tile.hpp"
 
 #ifndef RSA_QG_BATCH
@@ -877,82 +877,74 @@ __global__ __launch_bounds__(256, QG ? RSA_WALK_MIN_WAVES : RSA_WALK_FWD_MIN_WAV
 
 template <int LPR>
 static int launch_bpr_walk(const FwdParams& p, hipStream_t stream) {
-  const bool nt = (size_t)p.n_items * p.dim * sizeof(float) > (512ull << 20);
   const int T = p.num_neg >> 6;
   const int wpq_log2 = T >= 4 ? 2 : (T >= 2 ? 1 : 0);
-  const int qpb = 4 >> wpq_log2;
-  int64_t blocks = (p.n_queries + qpb - 1) / qpb;
-  if (blocks > RSA_FWD_GRID_CAP) blocks = RSA_FWD_GRID_CAP;
-  dim3 grid((unsigned)blocks), block(256);
-  if (p.qgrad != nullptr) {
-    if (nt) hipLaunchKernelGGL((fused_bpr_walk_kernel<LPR, true, true>), grid, block, 0, stream, p, wpq_log2);
-    else hipLaunchKernelGGL((fused_bpr_walk_kernel<LPR, false, true>), grid, block, 0, stream, p, wpq_log2);
-  } else {
-    if (nt) hipLaunchKernelGGL((fused_bpr_walk_kernel<LPR, true, false>), grid, block, 0, stream, p, wpq_log2);
-    else hipLaunchKernelGGL((fused_bpr_walk_kernel<LPR, false, false>), grid, block, 0, stream, p, wpq_log2);
-  }
+  const dim3 grid(grid_1d(p.n_queries, 4 >> wpq_log2, RSA_FWD_GRID_CAP)), block(256);
+  dispatch_bool(streams_past_cache(p.n_items, p.dim), [&](auto NT) {
+    dispatch_bool(p.qgrad != nullptr, [&](auto QG) {
+      hipLaunchKernelGGL((fused_bpr_walk_kernel<LPR, NT(), QG()>), grid, block, 0, stream, p, wpq_log2);
+    });
+  });
   RSA_CHECK_LAUNCH("rsa_fused_sample_gather_score(bpr walk)");
   return RSA_OK;
 }
 
 template <int LPR>
 static int launch_ssm(const FwdParams& p, hipStream_t stream) {
-  const bool nt = (size_t)p.n_items * p.dim * sizeof(float) > (512ull << 20);
-  int64_t blocks = (p.n_queries + 3) / 4;      // one wave per query
-  if (blocks > RSA_FWD_GRID_CAP) blocks = RSA_FWD_GRID_CAP;
-  dim3 grid((unsigned)blocks), block(256);
-  if (p.qgrad != nullptr) {
-    if (nt) hipLaunchKernelGGL((fused_ssm_kernel<LPR, true, true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((fused_ssm_kernel<LPR, false, true>), grid, block, 0, stream, p);
-  } else {
-    if (nt) hipLaunchKernelGGL((fused_ssm_kernel<LPR, true, false>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((fused_ssm_kernel<LPR, false, false>), grid, block, 0, stream, p);
-  }
+  const dim3 grid(grid_1d(p.n_queries, 4, RSA_FWD_GRID_CAP)), block(256);      // one wave per query
+  dispatch_bool(streams_past_cache(p.n_items, p.dim), [&](auto NT) {
+    dispatch_bool(p.qgrad != nullptr, [&](auto QG) {
+      hipLaunchKernelGGL((fused_ssm_kernel<LPR, NT(), QG()>), grid, block, 0, stream, p);
+    });
+  });
   RSA_CHECK_LAUNCH("rsa_fused_sample_gather_score(ssm)");
   return RSA_OK;
 }
 
 template <int LPR, bool GENERIC, bool COS, bool QU>
 static void launch_fwd2(const FwdParams& p, dim3 grid, dim3 block, hipStream_t stream) {
-  // streaming (nontemporal) row loads once the table cannot live in the 256 MB Infinity Cache
-  const bool nt = !GENERIC && (size_t)p.n_items * p.dim * sizeof(float) > (512ull << 20);
-  if constexpr (QU && !COS && !GENERIC) {
-    if (p.qgrad != nullptr && p.solo_flags != nullptr) {     // ... + SGD in place for the rows one element owns
-      if (nt) hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, true, true, true>), grid, block, 0, stream, p);
-      else hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, false, true, true>), grid, block, 0, stream, p);
-      return;
+  dispatch_bool(!GENERIC && streams_past_cache(p.n_items, p.dim), [&](auto NT) {
+    if constexpr (QU && !COS && !GENERIC) {
+      if (p.qgrad != nullptr && p.solo_flags != nullptr) {     // ... + SGD in place for the rows one element owns
+        hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, NT(), true, true>), grid, block, 0, stream, p);
+        return;
+      }
+      if (p.qgrad != nullptr) {     // training forward: query gradient accumulated from the rows in flight
+        hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, NT(), true>), grid, block, 0, stream, p);
+        return;
+      }
+      if (((p.numel + 63) >> 6) <= RSA_PIPE_MAX_TILES) {      // small / medium launch: the butterfly tile
+        hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, NT(), false, false, RSA_PIPE_BATCH>), grid, block, 0, stream, p);
+        return;
+      }
     }
-    if (p.qgrad != nullptr) {     // training forward: query gradient accumulated from the rows in flight
-      if (nt) hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, true, true>), grid, block, 0, stream, p);
-      else hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, false, true>), grid, block, 0, stream, p);
-      return;
-    }
-    if (((p.numel + 63) >> 6) <= RSA_PIPE_MAX_TILES) {      // small / medium launch: the butterfly tile
-      if (nt) hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, true, false, false, RSA_PIPE_BATCH>), grid, block, 0, stream, p);
-      else hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, false, false, false, RSA_PIPE_BATCH>), grid, block, 0, stream, p);
-      return;
-    }
-  }
-  if (nt) hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, !GENERIC>), grid, block, 0, stream, p);
-  else hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, false>), grid, block, 0, stream, p);
+    hipLaunchKernelGGL((fused_fwd_kernel<LPR, GENERIC, COS, QU, NT() && !GENERIC>), grid, block, 0, stream, p);
+  });
 }
 
 template <int LPR, bool GENERIC>
 static int launch_fwd(const FwdParams& p, bool cos, bool qu, hipStream_t stream) {
-  const int64_t n_tiles = (p.numel + 63) >> 6;
-  int64_t blocks = (n_tiles + 3) / 4;
-  if (blocks > RSA_FWD_GRID_CAP) blocks = RSA_FWD_GRID_CAP;
-  if (blocks < 1) blocks = 1;
-  dim3 grid((unsigned)blocks), block(256);
-  if (cos) {
-    if (qu) launch_fwd2<LPR, GENERIC, true, true>(p, grid, block, stream);
-    else launch_fwd2<LPR, GENERIC, true, false>(p, grid, block, stream);
-  } else {
-    if (qu) launch_fwd2<LPR, GENERIC, false, true>(p, grid, block, stream);
-    else launch_fwd2<LPR, GENERIC, false, false>(p, grid, block, stream);
-  }
+  const int64_t n_tiles = (p.numel + 63) >> 6;      // (>= 1: the callers return before this on an empty launch)
+  const dim3 grid(grid_1d(n_tiles, 4, RSA_FWD_GRID_CAP)), block(256);
+  dispatch_bool(cos, [&](auto COS) {
+    dispatch_bool(qu, [&](auto QU) { launch_fwd2<LPR, GENERIC, COS(), QU()>(p, grid, block, stream); });
+  });
   RSA_CHECK_LAUNCH("rsa_fused_sample_gather_score");
   return RSA_OK;
+}
+
+// The widths the forward has kernels of their own for (f receives D); any other multiple of 4 takes the generic-width kernels
+// where those exist.
+template <class F>
+static bool dispatch_fixed_width(int dim, F&& f) {
+  return dispatch_dim<32, 64, 128, 256>(dim, static_cast<F&&>(f));
+}
+
+static int launch_fwd_dim(const FwdParams& p, bool cos, bool qu, hipStream_t stream) {
+  int rc = RSA_OK;
+  if (!dispatch_fixed_width(p.dim, [&](auto D) { rc = launch_fwd<D() / 4, false>(p, cos, qu, stream); }))
+    rc = launch_fwd<64, true>(p, cos, qu, stream);
+  return rc;
 }
 
 __global__ void rng_advance_kernel(uint64_t* offset_dev, uint64_t increment) { *offset_dev += increment; }
@@ -1060,6 +1052,7 @@ extern "C" int rsa_fused_sample_gather_score(const rsa_fused_args* a, rsa_stream
   p.score_mode = a->score_mode;
 
   const bool cos = a->score_mode != RSA_SCORE_IP;   // cosine and Euclidean both need the squared norms
+  const bool fixed_width = dispatch_fixed_width(a->dim, [](auto) {});
   hipStream_t s = (hipStream_t)stream;
   int rc = RSA_OK;
   if (numel == 0) {
@@ -1106,7 +1099,7 @@ extern "C" int rsa_fused_sample_gather_score(const rsa_fused_args* a, rsa_stream
       p.loss_partials = reinterpret_cast<float*>(sc + SCRATCH_FUSED_PARTIALS);
     }
     if (a->query_grad != nullptr) {
-      RSA_CHECK_ARG(!cos && (a->dim == 32 || a->dim == 64 || a->dim == 128 || a->dim == 256),
+      RSA_CHECK_ARG(!cos && fixed_width,
                     "rsa_fused_sample_gather_score: query_grad needs the inner-product scorer and dim in "
                     "{32, 64, 128, 256}");
       p.qgrad = a->query_grad;
@@ -1122,37 +1115,20 @@ extern "C" int rsa_fused_sample_gather_score(const rsa_fused_args* a, rsa_stream
     }
   }
   if (ssm) {
-    RSA_CHECK_ARG(!cos && (a->dim == 32 || a->dim == 64 || a->dim == 128 || a->dim == 256) && a->packed_keys == nullptr,
+    RSA_CHECK_ARG(!cos && fixed_width && a->packed_keys == nullptr,
                   "rsa_fused_sample_gather_score: the SampledSoftmax epilogue needs the inner-product scorer and dim in "
                   "{32, 64, 128, 256}");
-    switch (a->dim) {
-      case 32: return launch_ssm<8>(p, s);
-      case 64: return launch_ssm<16>(p, s);
-      case 128: return launch_ssm<32>(p, s);
-      default: return launch_ssm<64>(p, s);
-    }
+    dispatch_fixed_width(a->dim, [&](auto D) { rc = launch_ssm<D() / 4>(p, s); });
+    return rc;
   }
+  // queries longer than one tile: the workgroup-per-query walk (deterministic, no atomics, nothing to zero)
   if (bpr && a->num_neg != 64 && !cos && a->packed_keys == nullptr &&
-      (a->dim == 32 || a->dim == 64 || a->dim == 128 || a->dim == 256)) {
-    // queries longer than one tile: the workgroup-per-query walk (deterministic, no atomics, nothing to zero)
-    switch (a->dim) {
-      case 32: return launch_bpr_walk<8>(p, s);
-      case 64: return launch_bpr_walk<16>(p, s);
-      case 128: return launch_bpr_walk<32>(p, s);
-      default: return launch_bpr_walk<64>(p, s);
-    }
-  }
+      dispatch_fixed_width(a->dim, [&](auto D) { rc = launch_bpr_walk<D() / 4>(p, s); }))
+    return rc;
   RSA_CHECK_ARG(!bpr || a->num_neg == 64,
                 "rsa_fused_sample_gather_score: the BPR epilogue with num_neg > 64 needs the inner-product scorer and dim in "
                 "{32, 64, 128, 256}");
-  switch (a->dim) {
-    case 32: rc = launch_fwd<8, false>(p, cos, qu, s); break;
-    case 64: rc = launch_fwd<16, false>(p, cos, qu, s); break;
-    case 128: rc = launch_fwd<32, false>(p, cos, qu, s); break;
-    case 256: rc = launch_fwd<64, false>(p, cos, qu, s); break;
-    default: rc = launch_fwd<64, true>(p, cos, qu, s); break;
-  }
-  return rc;
+  return launch_fwd_dim(p, cos, qu, s);
 }
 
 
@@ -1186,12 +1162,5 @@ extern "C" int rsa_shard_score_segments(const float* item_table, int64_t n_rows,
   p.num_neg = 1;
   p.sampler = RSA_SAMPLER_GIVEN;
   p.score_mode = RSA_SCORE_IP;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dim) {
-    case 32: return launch_fwd<8, false>(p, false, false, s);
-    case 64: return launch_fwd<16, false>(p, false, false, s);
-    case 128: return launch_fwd<32, false>(p, false, false, s);
-    case 256: return launch_fwd<64, false>(p, false, false, s);
-    default: return launch_fwd<64, true>(p, false, false, s);
-  }
+  return launch_fwd_dim(p, false, false, (hipStream_t)stream);
 }

@@ -1,6 +1,6 @@
 // Declarations shared between the translation units of librecstudio_amd.so (not part of the C ABI).
 #pragma once
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 
 namespace rsa {
 
@@ -41,10 +41,7 @@ int apply_step_all(bool users, const float* query, const int64_t* query_index, i
                    const float* dpos, const float* dneg, const float* upstream, int64_t n_items, int64_t n_users, float* target,
                    void* workspace, hipStream_t s);
 
-// PopularSamplerModel.forward on explicit arguments (rsa_sample.hip; the body behind rsa_sample_popular)
-int sample_popular_impl(const float* table, const float* pop_prob, const int32_t* guide, int64_t n_items,
-                        int32_t guide_log2, int64_t* neg_ids, float* neg_logp, float* u_out, int64_t numel,
-                        uint64_t seed, uint64_t offset, uint32_t grid_threads, uint64_t elem_base,
-                        const float* cdf_lut, const float* cdf_lines, int32_t lines_log2, rsa_stream_t stream);
+// PopularSamplerModel.forward (rsa_sample.hip; the body behind rsa_sample_popular) on a loaded argument block
+int sample_popular(const rsa_popular_args& a, rsa_stream_t stream);
 
 }  // namespace rsa

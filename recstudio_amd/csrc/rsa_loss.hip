@@ -7,7 +7,7 @@
 // striding over the row's negatives; group shuffles finish the row reductions.
 // Rows are reduced to the mean by a second, single-block, fixed-order kernel so the
 // scalar is deterministic.
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 
 namespace rsa {
 
@@ -371,21 +371,11 @@ extern "C" int rsa_row_lse(const float* x, int64_t n_rows, int64_t n_cols, float
 
 // Deterministic mean of n_rows floats.  The <= 256 stage-1 partials live in the caller-owned scratch block
 // (rsa_scratch_bytes(), include/recstudio_amd.h): calls sharing a block must be stream-ordered.
-static int mean_rows_impl(const float* row_loss, int64_t n_rows, const int32_t* denom, float* out, void* scratch,
-                          rsa_stream_t stream);
-
-extern "C" int rsa_mean_rows(const float* row_loss, int64_t n_rows, float* out, void* scratch, rsa_stream_t stream) {
-  return mean_rows_impl(row_loss, n_rows, nullptr, out, scratch, stream);
-}
-
-static int mean_rows_impl(const float* row_loss, int64_t n_rows, const int32_t* denom, float* out, void* scratch,
-                          rsa_stream_t stream) {
+static int mean_rows(const float* row_loss, int64_t n_rows, const int32_t* denom, float* out, void* scratch, hipStream_t s) {
   RSA_CHECK_ARG(row_loss && out && n_rows >= 1, "rsa_mean_rows: bad arguments");
   RSA_CHECK_ARG(scratch != nullptr, "rsa_mean_rows: scratch is null (rsa_scratch_bytes() bytes, zeroed once by the caller)");
-  hipStream_t s = (hipStream_t)stream;
   float* g_partials = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + SCRATCH_MEAN_PARTIALS);
-  int blocks = (int)((n_rows + 1023) / 1024);
-  if (blocks > 256) blocks = 256;
+  const int blocks = (int)grid_1d(n_rows, 1024, 256);
   const int64_t chunk = (n_rows + blocks - 1) / blocks;
   hipLaunchKernelGGL(mean_rows_stage1, dim3(blocks), dim3(256), 0, s, row_loss, n_rows, chunk, g_partials);
   hipLaunchKernelGGL(mean_rows_stage2, dim3(1), dim3(256), 0, s, g_partials, blocks, n_rows, denom, out);
@@ -393,128 +383,64 @@ static int mean_rows_impl(const float* row_loss, int64_t n_rows, const int32_t* 
   return RSA_OK;
 }
 
-static int pairwise_loss_ex_impl(int32_t loss_kind, const float* pos_score, const float* neg_score,
-                                 const float* pos_logp, const float* neg_logp, int64_t n_rows, int32_t num_neg,
-                                 float param0, float param1, float* row_loss, float* loss_out, float* dpos,
-                                 float* dneg, void* scratch, rsa_stream_t stream);
-static int pairwise_loss_impl(int32_t loss_kind, const float* pos_score, const float* neg_score,
-                              const float* pos_logp, const float* neg_logp, int64_t n_rows, int32_t num_neg,
-                              float* row_loss, float* loss_out, float* dpos, float* dneg, void* scratch,
-                              rsa_stream_t stream);
+extern "C" int rsa_mean_rows(const float* row_loss, int64_t n_rows, float* out, void* scratch, rsa_stream_t stream) {
+  return mean_rows(row_loss, n_rows, nullptr, out, scratch, (hipStream_t)stream);
+}
+
+// The pairwise losses give a row 1, 4, 16 or 64 lanes by its number of negatives: f receives RL.
+template <class F>
+static void dispatch_row_lanes(int64_t n_rows, int32_t num_neg, F&& f) {
+  const int rl = num_neg <= 2 ? 1 : num_neg <= 8 ? 4 : num_neg <= 32 ? 16 : 64;
+  const dim3 grid(grid_1d(n_rows * rl, 256, 4096));
+  dispatch_int<1, 4, 16, 64>(rl, [&](auto RL) { f(RL, grid); });
+}
+
+// the number of valid rows (the BCE losses' denominator) into the scratch block's counter
+static int count_valid_rows(const rsa_loss_args& a, int32_t* g_count, hipStream_t s) {
+  RSA_CHECK_HIP(hipMemsetAsync(g_count, 0, sizeof(int32_t), s), "rsa_pairwise_loss");
+  hipLaunchKernelGGL(count_valid_kernel, dim3(grid_1d(a.n_rows, 256, 1024)), dim3(256), 0, s, a.pos_score, a.n_rows, g_count);
+  return RSA_OK;
+}
 
 extern "C" int rsa_pairwise_loss(const rsa_loss_args* args, rsa_stream_t stream) {
   rsa_loss_args a;
   if (int rc = load_args(a, args, "rsa_pairwise_loss")) return rc;
-  if (a.loss_kind >= RSA_LOSS_WBPR)
-    return pairwise_loss_ex_impl(a.loss_kind, a.pos_score, a.neg_score, a.pos_logp, a.neg_logp, a.n_rows, a.num_neg, a.param0,
-                                 a.param1, a.row_loss, a.loss_out, a.dpos, a.dneg, a.scratch, stream);
-  return pairwise_loss_impl(a.loss_kind, a.pos_score, a.neg_score, a.pos_logp, a.neg_logp, a.n_rows, a.num_neg, a.row_loss,
-                            a.loss_out, a.dpos, a.dneg, a.scratch, stream);
-}
-
-static int pairwise_loss_impl(int32_t loss_kind, const float* pos_score, const float* neg_score,
-                              const float* pos_logp, const float* neg_logp, int64_t n_rows, int32_t num_neg,
-                              float* row_loss, float* loss_out, float* dpos, float* dneg, void* scratch,
-                              rsa_stream_t stream) {
-  RSA_CHECK_ARG(scratch != nullptr, "rsa_pairwise_loss: scratch is null");
-  int32_t* g_count = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(scratch) + SCRATCH_BCE_COUNT);
-  RSA_CHECK_ARG(loss_kind == RSA_LOSS_BPR || loss_kind == RSA_LOSS_SSM || loss_kind == RSA_LOSS_BCE,
-                "rsa_pairwise_loss: unknown loss %d", loss_kind);
-  RSA_CHECK_ARG(n_rows >= 1 && num_neg >= 1, "rsa_pairwise_loss: need n_rows >= 1 and num_neg >= 1");
-  RSA_CHECK_ARG(pos_score && neg_score && row_loss && loss_out, "rsa_pairwise_loss: null pointer");
+  const bool ex = a.loss_kind >= RSA_LOSS_WBPR;        // the parametrised losses: pairwise_loss_ex_kernel
+  RSA_CHECK_ARG(a.scratch != nullptr, "rsa_pairwise_loss: scratch is null");
+  int32_t* g_count = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(a.scratch) + SCRATCH_BCE_COUNT);
+  RSA_CHECK_ARG(ex ? a.loss_kind <= RSA_LOSS_CCL : (a.loss_kind == RSA_LOSS_BPR || a.loss_kind == RSA_LOSS_SSM || a.loss_kind == RSA_LOSS_BCE),
+                "rsa_pairwise_loss: unknown loss %d", a.loss_kind);
+  RSA_CHECK_ARG(a.n_rows >= 1 && a.num_neg >= 1, "rsa_pairwise_loss: need n_rows >= 1 and num_neg >= 1");
+  RSA_CHECK_ARG(a.pos_score && a.neg_score && a.row_loss && a.loss_out, "rsa_pairwise_loss: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const int rl = num_neg <= 2 ? 1 : num_neg <= 8 ? 4 : num_neg <= 32 ? 16 : 64;
-  int64_t blocks = (n_rows * rl + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  dim3 grid((unsigned)blocks), block(256);
-  if (loss_kind == RSA_LOSS_BCE) {
-    if (hipMemsetAsync(g_count, 0, sizeof(int32_t), s) != hipSuccess) {
-      rsa::set_error("rsa_pairwise_loss: memset failed");
-      return RSA_ERR_HIP;
-    }
-    int64_t cb = (n_rows + 255) / 256;
-    if (cb > 1024) cb = 1024;
-    hipLaunchKernelGGL(count_valid_kernel, dim3((unsigned)cb), dim3(256), 0, s, pos_score, n_rows, g_count);
-#define RSA_LAUNCH_BCE(RL) \
-  hipLaunchKernelGGL(bce_loss_kernel<RL>, grid, block, 0, s, pos_score, neg_score, n_rows, (int)num_neg, g_count, row_loss, dpos, dneg)
-    switch (rl) {
-      case 1: RSA_LAUNCH_BCE(1); break;
-      case 4: RSA_LAUNCH_BCE(4); break;
-      case 16: RSA_LAUNCH_BCE(16); break;
-      default: RSA_LAUNCH_BCE(64); break;
-    }
-#undef RSA_LAUNCH_BCE
-    RSA_CHECK_LAUNCH("rsa_pairwise_loss(bce)");
-    return mean_rows_impl(row_loss, n_rows, g_count, loss_out, scratch, stream);
-  }
-#define RSA_LAUNCH_LOSS(RL)                                                                                      \
-  hipLaunchKernelGGL(pairwise_loss_kernel<RL>, grid, block, 0, s, (int)loss_kind, pos_score, neg_score, pos_logp, \
-                     neg_logp, n_rows, (int)num_neg, row_loss, dpos, dneg)
-  switch (rl) {
-    case 1: RSA_LAUNCH_LOSS(1); break;
-    case 4: RSA_LAUNCH_LOSS(4); break;
-    case 16: RSA_LAUNCH_LOSS(16); break;
-    default: RSA_LAUNCH_LOSS(64); break;
-  }
-#undef RSA_LAUNCH_LOSS
-  RSA_CHECK_LAUNCH("rsa_pairwise_loss");
-  return rsa_mean_rows(row_loss, n_rows, loss_out, scratch, stream);
-}
-
-static int pairwise_loss_ex_impl(int32_t loss_kind, const float* pos_score, const float* neg_score,
-                                 const float* pos_logp, const float* neg_logp, int64_t n_rows, int32_t num_neg,
-                                 float param0, float param1, float* row_loss, float* loss_out, float* dpos,
-                                 float* dneg, void* scratch, rsa_stream_t stream) {
-  RSA_CHECK_ARG(scratch != nullptr, "rsa_pairwise_loss: scratch is null");
-  int32_t* g_count = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(scratch) + SCRATCH_BCE_COUNT);
-  RSA_CHECK_ARG(loss_kind >= RSA_LOSS_WBPR && loss_kind <= RSA_LOSS_CCL, "rsa_pairwise_loss: unknown loss %d",
-                loss_kind);
-  RSA_CHECK_ARG(n_rows >= 1 && num_neg >= 1, "rsa_pairwise_loss: need n_rows >= 1 and num_neg >= 1");
-  RSA_CHECK_ARG(pos_score && neg_score && row_loss && loss_out, "rsa_pairwise_loss: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const int rl = num_neg <= 2 ? 1 : num_neg <= 8 ? 4 : num_neg <= 32 ? 16 : 64;
-  int64_t blocks = (n_rows * rl + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  dim3 grid((unsigned)blocks), block(256);
   const int32_t* count = nullptr;
-  if (loss_kind == RSA_LOSS_WBCE) {
-    if (hipMemsetAsync(g_count, 0, sizeof(int32_t), s) != hipSuccess) {
-      rsa::set_error("rsa_pairwise_loss: memset failed");
-      return RSA_ERR_HIP;
-    }
-    int64_t cb = (n_rows + 255) / 256;
-    if (cb > 1024) cb = 1024;
-    hipLaunchKernelGGL(count_valid_kernel, dim3((unsigned)cb), dim3(256), 0, s, pos_score, n_rows, g_count);
+  if (a.loss_kind == RSA_LOSS_BCE || a.loss_kind == RSA_LOSS_WBCE) {
+    if (int rc = count_valid_rows(a, g_count, s)) return rc;
     count = g_count;
   }
-#define RSA_LAUNCH_EX(RL)                                                                                         \
-  hipLaunchKernelGGL(pairwise_loss_ex_kernel<RL>, grid, block, 0, s, (int)loss_kind, pos_score, neg_score, pos_logp, \
-                     neg_logp, n_rows, (int)num_neg, param0, param1, count, row_loss, dpos, dneg)
-  switch (rl) {
-    case 1: RSA_LAUNCH_EX(1); break;
-    case 4: RSA_LAUNCH_EX(4); break;
-    case 16: RSA_LAUNCH_EX(16); break;
-    default: RSA_LAUNCH_EX(64); break;
-  }
-#undef RSA_LAUNCH_EX
-  RSA_CHECK_LAUNCH("rsa_pairwise_loss");
-  return mean_rows_impl(row_loss, n_rows, count, loss_out, scratch, stream);
+  dispatch_row_lanes(a.n_rows, a.num_neg, [&](auto RL, dim3 grid) {
+    if (ex)
+      hipLaunchKernelGGL(pairwise_loss_ex_kernel<RL()>, grid, dim3(256), 0, s, (int)a.loss_kind, a.pos_score, a.neg_score, a.pos_logp,
+                         a.neg_logp, a.n_rows, (int)a.num_neg, a.param0, a.param1, count, a.row_loss, a.dpos, a.dneg);
+    else if (a.loss_kind == RSA_LOSS_BCE)
+      hipLaunchKernelGGL(bce_loss_kernel<RL()>, grid, dim3(256), 0, s, a.pos_score, a.neg_score, a.n_rows, (int)a.num_neg, g_count,
+                         a.row_loss, a.dpos, a.dneg);
+    else
+      hipLaunchKernelGGL(pairwise_loss_kernel<RL()>, grid, dim3(256), 0, s, (int)a.loss_kind, a.pos_score, a.neg_score, a.pos_logp,
+                         a.neg_logp, a.n_rows, (int)a.num_neg, a.row_loss, a.dpos, a.dneg);
+  });
+  RSA_CHECK_LAUNCH(a.loss_kind == RSA_LOSS_BCE ? "rsa_pairwise_loss(bce)" : "rsa_pairwise_loss");
+  return mean_rows(a.row_loss, a.n_rows, count, a.loss_out, a.scratch, s);
 }
 
 extern "C" int rsa_ssm_shared_loss(const rsa_loss_args* args, rsa_stream_t stream) {
   rsa_loss_args a;
   if (int rc = load_args(a, args, "rsa_ssm_shared_loss")) return rc;
-  const float *pos_score = a.pos_score, *pos_logp = a.pos_logp, *neg_score = a.neg_score, *neg_logp = a.neg_logp;
-  const int64_t n_rows = a.n_rows;
-  const int32_t n_pos = a.n_pos, num_neg = a.num_neg;
-  float *row_loss = a.row_loss, *loss_out = a.loss_out, *dpos = a.dpos, *dneg = a.dneg;
-  void* scratch = a.scratch;
-  RSA_CHECK_ARG(n_rows >= 1 && n_pos >= 1 && num_neg >= 1, "rsa_ssm_shared_loss: bad sizes");
-  RSA_CHECK_ARG(pos_score && neg_score && row_loss && loss_out, "rsa_ssm_shared_loss: null pointer");
-  int64_t blocks = (n_rows + 3) / 4;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(ssm_shared_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, pos_score, pos_logp,
-                     neg_score, neg_logp, n_rows, (int)n_pos, (int)num_neg, row_loss, dpos, dneg);
+  RSA_CHECK_ARG(a.n_rows >= 1 && a.n_pos >= 1 && a.num_neg >= 1, "rsa_ssm_shared_loss: bad sizes");
+  RSA_CHECK_ARG(a.pos_score && a.neg_score && a.row_loss && a.loss_out, "rsa_ssm_shared_loss: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ssm_shared_kernel, dim3(grid_1d(a.n_rows, 4, 4096)), dim3(256), 0, s, a.pos_score, a.pos_logp, a.neg_score,
+                     a.neg_logp, a.n_rows, (int)a.n_pos, (int)a.num_neg, a.row_loss, a.dpos, a.dneg);
   RSA_CHECK_LAUNCH("rsa_ssm_shared_loss");
-  return rsa_mean_rows(row_loss, n_rows, loss_out, scratch, stream);
+  return mean_rows(a.row_loss, a.n_rows, nullptr, a.loss_out, a.scratch, s);
 }

@@ -2,7 +2,7 @@
 #include <cstdarg>
 #include <cstdio>
 
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 
 namespace rsa {
 
@@ -147,9 +147,7 @@ extern "C" int rsa_embedding_gather(const float* table, int64_t n_rows, int32_t 
   if (numel == 0) return RSA_OK;
   RSA_CHECK_ARG(table && ids && out, "rsa_embedding_gather: null pointer");
   const int64_t total = numel * (dim / 4);
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(embedding_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table,
+  hipLaunchKernelGGL(embedding_gather_kernel, dim3(grid_1d(total, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream, table,
                      n_rows, (int)dim, ids, numel, out);
   RSA_CHECK_LAUNCH("rsa_embedding_gather");
   return RSA_OK;
@@ -158,19 +156,13 @@ extern "C" int rsa_embedding_gather(const float* table, int64_t n_rows, int32_t 
 extern "C" int rsa_seg_gather(const rsa_seg_gather_args* args, rsa_stream_t stream) {
   rsa_seg_gather_args a;
   if (int rc = load_args(a, args, "rsa_seg_gather")) return rc;
-  const float* item_table = a.item_table;
-  const int64_t n_items = a.n_items, n_flat = a.n_flat, n_seg = a.n_seg;
-  const int32_t dim = a.dim, max_len = a.max_len;
-  const int64_t *flat_item_ids = a.flat_item_ids, *seg_start = a.seg_start, *seg_end = a.seg_end;
-  int64_t *out_ids = a.out_ids, *out_len = a.out_len;
-  float* out_rows = a.out_rows;
-  RSA_CHECK_ARG(n_seg >= 0 && max_len >= 1 && n_flat >= 0, "rsa_seg_gather: bad sizes");
-  if (n_seg == 0) return RSA_OK;
-  RSA_CHECK_ARG(flat_item_ids && seg_start && seg_end, "rsa_seg_gather: null input pointer");
-  RSA_CHECK_ARG(out_rows == nullptr || (item_table && dim >= 4 && dim % 4 == 0 && n_items >= 1),
+  RSA_CHECK_ARG(a.n_seg >= 0 && a.max_len >= 1 && a.n_flat >= 0, "rsa_seg_gather: bad sizes");
+  if (a.n_seg == 0) return RSA_OK;
+  RSA_CHECK_ARG(a.flat_item_ids && a.seg_start && a.seg_end, "rsa_seg_gather: null input pointer");
+  RSA_CHECK_ARG(a.out_rows == nullptr || (a.item_table && a.dim >= 4 && a.dim % 4 == 0 && a.n_items >= 1),
                 "rsa_seg_gather: out_rows needs item_table and dim % 4 == 0");
-  hipLaunchKernelGGL(seg_gather_kernel, dim3((unsigned)n_seg), dim3(256), 0, (hipStream_t)stream, item_table, n_items,
-                     (int)dim, flat_item_ids, n_flat, seg_start, seg_end, (int)max_len, out_ids, out_rows, out_len);
+  hipLaunchKernelGGL(seg_gather_kernel, dim3((unsigned)a.n_seg), dim3(256), 0, (hipStream_t)stream, a.item_table, a.n_items,
+                     (int)a.dim, a.flat_item_ids, a.n_flat, a.seg_start, a.seg_end, (int)a.max_len, a.out_ids, a.out_rows, a.out_len);
   RSA_CHECK_LAUNCH("rsa_seg_gather");
   return RSA_OK;
 }
@@ -181,9 +173,7 @@ extern "C" int rsa_row_sqnorm(const float* table, int64_t n_rows, int32_t dim, i
   RSA_CHECK_ARG(score_mode == RSA_SCORE_COS || score_mode == RSA_SCORE_EUC, "rsa_row_sqnorm: score_mode must be COS or EUC");
   if (n_rows == 0) return RSA_OK;
   RSA_CHECK_ARG(table && out, "rsa_row_sqnorm: null pointer");
-  int64_t blocks = (n_rows + 3) / 4;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(rsa::row_sqnorm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, n_rows,
+  hipLaunchKernelGGL(rsa::row_sqnorm_kernel, dim3(grid_1d(n_rows, 4, 8192)), dim3(256), 0, (hipStream_t)stream, table, n_rows,
                      (int)dim, (int)score_mode, out);
   RSA_CHECK_LAUNCH("rsa_row_sqnorm");
   return RSA_OK;

@@ -624,54 +624,44 @@ __global__ __launch_bounds__(256) void shard_pos_score_kernel(const float* __res
 
 template <int LPR, bool SCORE>
 static void launch_walk(const OwnArgs& a, bool upd, int64_t slots, hipStream_t s) {
-  const bool nt = (size_t)a.n_rows * LPR * 16 > (512ull << 20);
-  const int64_t tiles_per_query = slots / (a.n_queries > 0 ? a.n_queries : 1) / 64;
-  const int wpq_log2 = tiles_per_query >= 8 ? 2 : (tiles_per_query >= 3 ? 1 : 0);
-  const int qpb = 4 >> wpq_log2;
-  int64_t blocks = ((int64_t)a.n_queries + qpb - 1) / qpb;
-  if (blocks > 4096) blocks = 4096;
-  dim3 grid((unsigned)blocks), block(256);
-  if (upd) {
-    if (nt) hipLaunchKernelGGL((owner_backward_walk_kernel<LPR, true, true, SCORE>), grid, block, 0, s, a, wpq_log2);
-    else hipLaunchKernelGGL((owner_backward_walk_kernel<LPR, false, true, SCORE>), grid, block, 0, s, a, wpq_log2);
-  } else {
-    if (nt) hipLaunchKernelGGL((owner_backward_walk_kernel<LPR, true, false, SCORE>), grid, block, 0, s, a, wpq_log2);
-    else hipLaunchKernelGGL((owner_backward_walk_kernel<LPR, false, false, SCORE>), grid, block, 0, s, a, wpq_log2);
-  }
+  const WalkGeometry g = owner_walk_geometry(slots, a.n_queries);
+  dispatch_bool(streams_past_cache(a.n_rows, LPR * 4), [&](auto NT) {
+    dispatch_bool(upd, [&](auto UPD) {
+      hipLaunchKernelGGL((owner_backward_walk_kernel<LPR, NT(), UPD(), SCORE>), dim3(g.blocks), dim3(256), 0, s, a, g.wpq_log2);
+    });
+  });
 }
-
-static inline int64_t align256o(int64_t b) { return (b + 255) / 256 * 256; }
 
 struct OwnLayout {
   void* sorted_ws;              // the row sort + sorted apply workspace (sorted_workspace_bytes(slots + positives))
   uint64_t *qa, *qb;            // the query sort's ping-pong buffers
   void* qtemp;
-  int32_t *run_start, *run_end;
+  int32_t *run_start, *run_end; // adjacent: one memset clears both
   uint8_t* solo;                // [slots + positives]
 };
 
-static OwnLayout own_layout(void* workspace, int64_t slots, int64_t n_queries) {
-  char* ws = reinterpret_cast<char*>(workspace);
+static OwnLayout carve_own(Carver& ws, int64_t slots, int64_t n_queries) {
   OwnLayout L;
-  L.sorted_ws = ws;
-  ws += align256o(sorted_workspace_bytes(slots + n_queries));
-  L.qa = reinterpret_cast<uint64_t*>(ws);
-  ws += align256o(slots * 8);
-  L.qb = reinterpret_cast<uint64_t*>(ws);
-  ws += align256o(slots * 8);
-  L.qtemp = ws;
-  ws += align256o(radix_temp_bytes(slots));
-  L.run_start = reinterpret_cast<int32_t*>(ws);
-  ws += align256o(n_queries * 4);
-  L.run_end = reinterpret_cast<int32_t*>(ws);
-  ws += align256o(n_queries * 4);
-  L.solo = reinterpret_cast<uint8_t*>(ws);
+  L.sorted_ws = ws.take<char>(sorted_workspace_bytes(slots + n_queries));
+  L.qa = ws.take<uint64_t>(slots);
+  L.qb = ws.take<uint64_t>(slots);
+  L.qtemp = ws.take<char>(radix_temp_bytes(slots));
+  L.run_start = ws.take<int32_t>(n_queries);
+  L.run_end = ws.take<int32_t>(n_queries);
+  L.solo = ws.take<uint8_t>(slots + n_queries);
   return L;
 }
 
 static int64_t own_workspace_bytes(int64_t slots, int64_t n_queries) {
-  return align256o(sorted_workspace_bytes(slots + n_queries)) + 2 * align256o(slots * 8) + align256o(radix_temp_bytes(slots)) +
-         2 * align256o(n_queries * 4) + align256o(slots + n_queries) + 256;
+  Carver sizing(nullptr);
+  carve_own(sizing, slots, n_queries);
+  return align256(sizing.bytes()) + 256;
+}
+
+// run_start and run_end, both cleared
+static int clear_runs(const OwnLayout& W, int64_t n_queries, hipStream_t s, const char* who) {
+  RSA_CHECK_HIP(hipMemsetAsync(W.run_start, 0, (size_t)(2 * align256(n_queries * 4)), s), who);
+  return RSA_OK;
 }
 
 // What both forms of the owner pass share: the update scales, the row sort (+ classification), the query sort, the runs
@@ -710,6 +700,12 @@ struct OwnPrepared {
 // step ahead, on another stream), or the update scales only (the step's own half of such a split)
 enum OwnPrep { OWN_PREP_ALL = 0, OWN_PREP_LAYOUT = 1, OWN_PREP_SORTS = 2, OWN_PREP_SCALE = 3 };
 
+// The widths the owner kernels are built for.  owner_prepare, which every owner entry point goes through, rejects the others.
+template <class F>
+static bool dispatch_own_dim(int dim, F&& f) {
+  return dispatch_dim<64, 128, 256>(dim, static_cast<F&&>(f));
+}
+
 static int owner_prepare(const OwnCommon& c, OwnPrepared& P, OwnPrep mode, hipStream_t s, const char* who) {
   RSA_CHECK_ARG(c.n_segments >= 0 && c.stride > RSA_SHARD_HDR, "%s: bad sizes", who);
   P.slots = c.n_segments * c.stride;
@@ -718,14 +714,15 @@ static int owner_prepare(const OwnCommon& c, OwnPrepared& P, OwnPrep mode, hipSt
   RSA_CHECK_ARG(c.item_local && (c.q_all || mode == OWN_PREP_SORTS) && (c.keys || P.slots == 0) && c.item_target, "%s: null pointer", who);
   RSA_CHECK_ARG(c.n_rows >= 1 && c.n_rows < (1ll << 31) && c.n_query_rows >= 1 && c.n_query_rows < (1ll << 31),
                 "%s: table sizes out of range", who);
-  if (c.dim != 64 && c.dim != 128 && c.dim != 256) {
+  if (!dispatch_own_dim(c.dim, [](auto) {})) {
     rsa::set_error("%s: dim=%d: built for dim in {64, 128, 256}", who, c.dim);
     return RSA_ERR_UNSUPPORTED;
   }
   const int64_t need = own_workspace_bytes(P.slots, c.n_query_rows);
   RSA_CHECK_ARG(c.workspace && c.workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who,
                 (long long)c.workspace_bytes, (long long)need);
-  P.W = own_layout(c.workspace, P.slots, c.n_query_rows);
+  Carver ws(c.workspace);
+  P.W = carve_own(ws, P.slots, c.n_query_rows);
   P.row_total = P.slots + (c.pos_rows ? c.n_query_rows : 0);
   P.L = sorted_layout(P.W.sorted_ws, P.slots + c.n_query_rows);
   P.inplace = c.item_target == c.item_local;
@@ -754,13 +751,8 @@ static int owner_prepare(const OwnCommon& c, OwnPrepared& P, OwnPrep mode, hipSt
   }
   if (P.slots == 0) return RSA_OK;
   if (c.keys_grouped) {       // 2'. the router already grouped the segments by query: read the runs off the slots
-    if (hipMemsetAsync(P.W.run_start, 0, (size_t)(2 * align256o(c.n_query_rows * 4)), s) != hipSuccess) {
-      rsa::set_error("%s: memset failed", who);
-      return RSA_ERR_HIP;
-    }
-    int64_t gblocks = (P.slots + 255) / 256;
-    if (gblocks > 8192) gblocks = 8192;
-    hipLaunchKernelGGL(query_runs_segments_kernel, dim3((unsigned)gblocks), dim3(256), 0, s, c.keys, P.slots, by_stride,
+    if (int rc = clear_runs(P.W, c.n_query_rows, s, who)) return rc;
+    hipLaunchKernelGGL(query_runs_segments_kernel, dim3(grid_1d(P.slots, 256, 8192)), dim3(256), 0, s, c.keys, P.slots, by_stride,
                        (int32_t)c.n_query_rows, P.W.run_start, P.W.run_end);
     RSA_CHECK_LAUNCH(who);
     P.q_sorted = nullptr;
@@ -772,13 +764,8 @@ static int owner_prepare(const OwnCommon& c, OwnPrepared& P, OwnPrep mode, hipSt
     rsa::set_error("%s: query sort failed: %s", who, hipGetErrorString(hipGetLastError()));
     return RSA_ERR_HIP;
   }
-  if (hipMemsetAsync(P.W.run_start, 0, (size_t)(2 * align256o(c.n_query_rows * 4)), s) != hipSuccess) {
-    rsa::set_error("%s: memset failed", who);
-    return RSA_ERR_HIP;
-  }
-  int64_t blocks = (P.slots + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(query_runs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, P.q_sorted, P.slots, (int32_t)c.n_query_rows,
+  if (int rc = clear_runs(P.W, c.n_query_rows, s, who)) return rc;
+  hipLaunchKernelGGL(query_runs_kernel, dim3(grid_1d(P.slots, 256, 8192)), dim3(256), 0, s, P.q_sorted, P.slots, (int32_t)c.n_query_rows,
                      P.W.run_start, P.W.run_end);
   RSA_CHECK_LAUNCH(who);
   return RSA_OK;
@@ -823,11 +810,7 @@ extern "C" int rsa_shard_backward_segments(const rsa_shard_backward_args* a, rsa
   // 3. the walk: query gradients, solo rows in place
   OwnArgs o = walk_args(c, P, a->qgrad_all);
   o.d = a->d_owner;
-  switch (a->dim) {
-    case 64: launch_walk<16, false>(o, P.inplace, P.slots, s); break;
-    case 128: launch_walk<32, false>(o, P.inplace, P.slots, s); break;
-    default: launch_walk<64, false>(o, P.inplace, P.slots, s); break;
-  }
+  dispatch_own_dim(a->dim, [&](auto D) { launch_walk<D() / 4, false>(o, P.inplace, P.slots, s); });
   RSA_CHECK_LAUNCH("rsa_shard_backward_segments(walk)");
   // 4. the rows that several elements touch (or, for a gradient block, every row): sorted apply
   return apply_sorted_segments(P.row_sorted, P.slots, P.slots, a->q_all, a->dim, a->keys, a->d_owner, a->scale_out, a->n_rows,
@@ -843,21 +826,15 @@ extern "C" int rsa_shard_pos_score(const float* item_local, int64_t n_rows, int3
   if (n_query_rows == 0) return RSA_OK;
   RSA_CHECK_ARG(item_local && q_all && pos_rows && out, "rsa_shard_pos_score: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  int64_t blocks;
-#define RSA_POS_LAUNCH(LPR)                                                                                       \
-  blocks = (n_query_rows + 256 / LPR - 1) / (256 / LPR);                                                          \
-  if (blocks > 4096) blocks = 4096;                                                                               \
-  hipLaunchKernelGGL(shard_pos_score_kernel<LPR>, dim3((unsigned)blocks), dim3(256), 0, s, item_local, q_all, pos_rows, \
-                     n_rows, (int32_t)n_query_rows, out, pos_ids, rows_per_shard, n_shards, rank)
-  switch (dim) {
-    case 64: RSA_POS_LAUNCH(16); break;
-    case 128: RSA_POS_LAUNCH(32); break;
-    case 256: RSA_POS_LAUNCH(64); break;
-    default:
-      rsa::set_error("rsa_shard_pos_score: dim=%d: built for dim in {64, 128, 256}", dim);
-      return RSA_ERR_UNSUPPORTED;
+  const bool built = dispatch_dim<64, 128, 256>(dim, [&](auto D) {
+    constexpr int LPR = D() / 4;
+    hipLaunchKernelGGL(shard_pos_score_kernel<LPR>, dim3(grid_1d(n_query_rows, 256 / LPR, 4096)), dim3(256), 0, s, item_local, q_all,
+                       pos_rows, n_rows, (int32_t)n_query_rows, out, pos_ids, rows_per_shard, n_shards, rank);
+  });
+  if (!built) {
+    rsa::set_error("rsa_shard_pos_score: dim=%d: built for dim in {64, 128, 256}", dim);
+    return RSA_ERR_UNSUPPORTED;
   }
-#undef RSA_POS_LAUNCH
   RSA_CHECK_LAUNCH("rsa_shard_pos_score");
   return RSA_OK;
 }
@@ -880,11 +857,8 @@ extern "C" int rsa_shard_owner_bpr_forward(const rsa_shard_owner_bpr_args* a, rs
   int rc = owner_prepare(c, P, a->forward_parts == 1 ? OWN_PREP_SORTS : a->forward_parts == 2 ? OWN_PREP_SCALE : OWN_PREP_ALL, s,
                          "rsa_shard_owner_bpr_forward");
   if (rc != RSA_OK || a->forward_parts == 1) return rc;
-  if (hipMemsetAsync(a->dsum_part, 0, (size_t)a->n_query_rows * 4, s) != hipSuccess ||
-      (a->loss_part && hipMemsetAsync(a->loss_part, 0, 4, s) != hipSuccess)) {
-    rsa::set_error("rsa_shard_owner_bpr_forward: memset failed");
-    return RSA_ERR_HIP;
-  }
+  RSA_CHECK_HIP(hipMemsetAsync(a->dsum_part, 0, (size_t)a->n_query_rows * 4, s), "rsa_shard_owner_bpr_forward");
+  if (a->loss_part) RSA_CHECK_HIP(hipMemsetAsync(a->loss_part, 0, 4, s), "rsa_shard_owner_bpr_forward");
   if (P.slots == 0) return RSA_OK;
   OwnArgs o = walk_args(c, P, a->qgrad_all);
   o.d_out = a->d_slots;
@@ -900,11 +874,7 @@ extern "C" int rsa_shard_owner_bpr_forward(const rsa_shard_owner_bpr_args* a, rs
     o.done_counter = reinterpret_cast<unsigned int*>(sc + SCRATCH_COUNTER);
     o.loss_partials = reinterpret_cast<float*>(sc + SCRATCH_FUSED_PARTIALS);
   }
-  switch (a->dim) {
-    case 64: launch_walk<16, true>(o, P.inplace, P.slots, s); break;
-    case 128: launch_walk<32, true>(o, P.inplace, P.slots, s); break;
-    default: launch_walk<64, true>(o, P.inplace, P.slots, s); break;
-  }
+  dispatch_own_dim(a->dim, [&](auto D) { launch_walk<D() / 4, true>(o, P.inplace, P.slots, s); });
   RSA_CHECK_LAUNCH("rsa_shard_owner_bpr_forward(walk)");
   return RSA_OK;
 }
@@ -921,19 +891,12 @@ extern "C" int rsa_shard_owner_bpr_finish(const rsa_shard_owner_bpr_args* a, con
     return apply_sorted_segments(P.row_sorted, P.row_total, P.slots, a->q_all, a->dim, a->keys, a->d_slots, a->scale_out, a->n_rows,
                                  a->item_pad_row, a->item_target, P.L, s);
   const int64_t Q = a->n_query_rows;
-  int64_t blocks;
-#define RSA_FIN_LAUNCH(LPR)                                                                                          \
-  blocks = (Q + 256 / LPR - 1) / (256 / LPR);                                                                        \
-  if (blocks > 4096) blocks = 4096;                                                                                  \
-  hipLaunchKernelGGL(owner_pos_finish_kernel<LPR>, dim3((unsigned)blocks), dim3(256), 0, s, a->item_local,           \
-                     P.inplace ? a->item_target : nullptr, a->q_all, a->qgrad_all, a->pos_rows, dsum_all,             \
-                     a->d_slots + P.slots, P.W.solo + P.slots, a->scale_out, a->n_rows, (int32_t)Q)
-  switch (a->dim) {
-    case 64: RSA_FIN_LAUNCH(16); break;
-    case 128: RSA_FIN_LAUNCH(32); break;
-    default: RSA_FIN_LAUNCH(64); break;
-  }
-#undef RSA_FIN_LAUNCH
+  dispatch_own_dim(a->dim, [&](auto D) {
+    constexpr int LPR = D() / 4;
+    hipLaunchKernelGGL(owner_pos_finish_kernel<LPR>, dim3(grid_1d(Q, 256 / LPR, 4096)), dim3(256), 0, s, a->item_local,
+                       P.inplace ? a->item_target : nullptr, a->q_all, a->qgrad_all, a->pos_rows, dsum_all,
+                       a->d_slots + P.slots, P.W.solo + P.slots, a->scale_out, a->n_rows, (int32_t)Q);
+  });
   RSA_CHECK_LAUNCH("rsa_shard_owner_bpr_finish(positives)");
   if (a->finish_parts == 1) return RSA_OK;
   return apply_sorted_segments(P.row_sorted, P.row_total, P.slots, a->q_all, a->dim, a->keys, a->d_slots, a->scale_out, a->n_rows,
@@ -962,27 +925,13 @@ extern "C" int rsa_shard_owner_ssm_forward(const rsa_shard_owner_bpr_args* a, rs
   o.run_acc = a->run_acc;
   // (the walk writes the three per-query outputs of EVERY query, with or without slots -- also when there is no slot at all:
   // its runs are then all empty)
-  if (P.slots == 0) {
-    if (hipMemsetAsync(P.W.run_start, 0, (size_t)(2 * align256o(Q * 4)), s) != hipSuccess) {
-      rsa::set_error("rsa_shard_owner_ssm_forward: memset failed");
-      return RSA_ERR_HIP;
-    }
-  }
-  const bool nt = (size_t)a->n_rows * a->dim * 4 > (512ull << 20);
-  const int64_t tiles_per_query = P.slots / (Q > 0 ? Q : 1) / 64;
-  const int wpq_log2 = tiles_per_query >= 8 ? 2 : (tiles_per_query >= 3 ? 1 : 0);
-  const int qpb = 4 >> wpq_log2;
-  int64_t blocks = (Q + qpb - 1) / qpb;
-  if (blocks > 4096) blocks = 4096;
-#define RSA_SSM_WALK(LPR)                                                                                                \
-  if (nt) hipLaunchKernelGGL((owner_ssm_walk_kernel<LPR, true>), dim3((unsigned)blocks), dim3(256), 0, s, o, wpq_log2);   \
-  else hipLaunchKernelGGL((owner_ssm_walk_kernel<LPR, false>), dim3((unsigned)blocks), dim3(256), 0, s, o, wpq_log2)
-  switch (a->dim) {
-    case 64: RSA_SSM_WALK(16); break;
-    case 128: RSA_SSM_WALK(32); break;
-    default: RSA_SSM_WALK(64); break;
-  }
-#undef RSA_SSM_WALK
+  if (P.slots == 0 && (rc = clear_runs(P.W, Q, s, "rsa_shard_owner_ssm_forward")) != RSA_OK) return rc;
+  const WalkGeometry g = owner_walk_geometry(P.slots, Q);
+  dispatch_own_dim(a->dim, [&](auto D) {
+    dispatch_bool(streams_past_cache(a->n_rows, a->dim), [&](auto NT) {
+      hipLaunchKernelGGL((owner_ssm_walk_kernel<D() / 4, NT()>), dim3(g.blocks), dim3(256), 0, s, o, g.wpq_log2);
+    });
+  });
   RSA_CHECK_LAUNCH("rsa_shard_owner_ssm_forward(walk)");
   return RSA_OK;
 }
@@ -1002,54 +951,34 @@ extern "C" int rsa_shard_owner_ssm_finish(const rsa_shard_owner_bpr_args* a, con
   // In place (SGD applied by the kernels) the forward's row sort has flagged the rows one element touches: the positives'
   // owners update such a row themselves, the second walk below the negatives'.  A gradient BLOCK takes every element through
   // the apply pass (nothing was classified: the flags behind the slots' are cleared for the positives' kernel).
-  if (!P.inplace && hipMemsetAsync(P.W.solo + P.slots, 0, (size_t)Q, s) != hipSuccess) {
-    rsa::set_error("rsa_shard_owner_ssm_finish: memset failed");
-    return RSA_ERR_HIP;
-  }
-  int64_t blocks;
+  if (!P.inplace) RSA_CHECK_HIP(hipMemsetAsync(P.W.solo + P.slots, 0, (size_t)Q, s), "rsa_shard_owner_ssm_finish");
   // per query: the query-gradient partials from the phase-1 accumulators, then the positives' terms (d loss/d pos behind the
   // slots' coefficients for the apply pass; a positive alone on its row is updated here).  Both read rows as they were
   // BEFORE this step's updates: a solo row belongs to one element, and the shared rows change in the apply pass only.
-#define RSA_SSM_FIN(LPR)                                                                                                  \
-  blocks = (Q + 256 / LPR - 1) / (256 / LPR);                                                                             \
-  if (blocks > 4096) blocks = 4096;                                                                                       \
-  hipLaunchKernelGGL(owner_ssm_query_kernel<LPR>, dim3((unsigned)blocks), dim3(256), 0, s, a->run_max, a->run_acc, lse_all, \
-                     a->pos_score, binv, a->scale_out, a->qgrad_all, a->dsum_part, (int32_t)Q);                           \
-  hipLaunchKernelGGL(owner_pos_finish_kernel<LPR>, dim3((unsigned)blocks), dim3(256), 0, s, a->item_local,                \
-                     P.inplace ? a->item_target : (float*)nullptr, a->q_all, a->qgrad_all, a->pos_rows, a->dsum_part,      \
-                     a->d_slots + P.slots, P.W.solo + P.slots, a->scale_out, a->n_rows, (int32_t)Q)
-  switch (a->dim) {
-    case 64: RSA_SSM_FIN(16); break;
-    case 128: RSA_SSM_FIN(32); break;
-    default: RSA_SSM_FIN(64); break;
-  }
-#undef RSA_SSM_FIN
+  dispatch_own_dim(a->dim, [&](auto D) {
+    constexpr int LPR = D() / 4;
+    const dim3 grid(grid_1d(Q, 256 / LPR, 4096));
+    hipLaunchKernelGGL(owner_ssm_query_kernel<LPR>, grid, dim3(256), 0, s, a->run_max, a->run_acc, lse_all, a->pos_score, binv,
+                       a->scale_out, a->qgrad_all, a->dsum_part, (int32_t)Q);
+    hipLaunchKernelGGL(owner_pos_finish_kernel<LPR>, grid, dim3(256), 0, s, a->item_local,
+                       P.inplace ? a->item_target : (float*)nullptr, a->q_all, a->qgrad_all, a->pos_rows, a->dsum_part,
+                       a->d_slots + P.slots, P.W.solo + P.slots, a->scale_out, a->n_rows, (int32_t)Q);
+  });
   RSA_CHECK_LAUNCH("rsa_shard_owner_ssm_finish");
   if (P.slots > 0 && !P.inplace) {          // z -> d for every slot
-    int64_t dblocks = (P.slots + 255) / 256;
-    if (dblocks > 8192) dblocks = 8192;
-    hipLaunchKernelGGL(owner_ssm_d_kernel, dim3((unsigned)dblocks), dim3(256), 0, s, a->keys, P.slots, rdx_make_div32((uint64_t)a->stride),
+    hipLaunchKernelGGL(owner_ssm_d_kernel, dim3(grid_1d(P.slots, 256, 8192)), dim3(256), 0, s, a->keys, P.slots, rdx_make_div32((uint64_t)a->stride),
                        (int32_t)Q, lse_all, binv, a->d_slots);
     RSA_CHECK_LAUNCH("rsa_shard_owner_ssm_finish(d)");
   } else if (P.slots > 0) {                 // the second walk by query: z -> d, solo rows rewritten with the query row in registers
     OwnArgs o = walk_args(c, P, a->qgrad_all);
     o.d_out = a->d_slots;
     o.binv = binv;
-    const bool nt = (size_t)a->n_rows * a->dim * 4 > (512ull << 20);
-    const int64_t tiles_per_query = P.slots / (Q > 0 ? Q : 1) / 64;
-    const int wpq_log2 = tiles_per_query >= 8 ? 2 : (tiles_per_query >= 3 ? 1 : 0);
-    const int qpb = 4 >> wpq_log2;
-    int64_t wblocks = (Q + qpb - 1) / qpb;
-    if (wblocks > 4096) wblocks = 4096;
-#define RSA_SSM_UPD(LPR)                                                                                                          \
-  if (nt) hipLaunchKernelGGL((owner_ssm_update_walk_kernel<LPR, true>), dim3((unsigned)wblocks), dim3(256), 0, s, o, lse_all, wpq_log2); \
-  else hipLaunchKernelGGL((owner_ssm_update_walk_kernel<LPR, false>), dim3((unsigned)wblocks), dim3(256), 0, s, o, lse_all, wpq_log2)
-    switch (a->dim) {
-      case 64: RSA_SSM_UPD(16); break;
-      case 128: RSA_SSM_UPD(32); break;
-      default: RSA_SSM_UPD(64); break;
-    }
-#undef RSA_SSM_UPD
+    const WalkGeometry g = owner_walk_geometry(P.slots, Q);
+    dispatch_own_dim(a->dim, [&](auto D) {
+      dispatch_bool(streams_past_cache(a->n_rows, a->dim), [&](auto NT) {
+        hipLaunchKernelGGL((owner_ssm_update_walk_kernel<D() / 4, NT()>), dim3(g.blocks), dim3(256), 0, s, o, lse_all, g.wpq_log2);
+      });
+    });
     RSA_CHECK_LAUNCH("rsa_shard_owner_ssm_finish(update walk)");
   }
   // the rows several elements touch (or, for a gradient block, every row): sorted apply

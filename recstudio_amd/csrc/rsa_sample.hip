@@ -205,12 +205,9 @@ __global__ __launch_bounds__(256) void sample_masked_kernel(const int64_t* __res
 }
 
 constexpr int LUT_BATCH = 4;
-static inline int grid_for(int64_t numel) {
-  // one element per thread up to 64 K workgroups: the samplers are a chain of dependent loads per
-  // element, so more threads in flight beat a grid-stride loop (0.23 -> 0.1x ms for 4 M ids)
-  int64_t b = (numel + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
+// one element per thread up to 64 K workgroups: the samplers are a chain of dependent loads per
+// element, so more threads in flight beat a grid-stride loop (0.23 -> 0.1x ms for 4 M ids)
+static inline unsigned grid_for(int64_t numel) { return grid_1d(numel, 256, 65536); }
 
 }  // namespace rsa
 
@@ -230,80 +227,60 @@ extern "C" int rsa_sample_uniform(int64_t* neg_ids, int64_t numel, int64_t low, 
   return RSA_OK;
 }
 
-static int check_popular(const char* fn, const float* table, const float* pop_prob, const int32_t* guide,
-                         int64_t n_items, int32_t guide_log2, const float* lines, int32_t lines_log2) {
-  RSA_CHECK_ARG(table && pop_prob, "%s: table/pop_prob is null", fn);
-  RSA_CHECK_ARG(n_items >= 1 && n_items < (1ll << 31), "%s: n_items out of range", fn);
-  if (lines != nullptr) {
-    RSA_CHECK_ARG(lines_log2 >= 0 && lines_log2 <= 28 && ((uintptr_t)lines & 127) == 0,
+static int check_popular(const char* fn, const rsa_popular_args& a) {
+  RSA_CHECK_ARG(a.table && a.pop_prob, "%s: table/pop_prob is null", fn);
+  RSA_CHECK_ARG(a.n_items >= 1 && a.n_items < (1ll << 31), "%s: n_items out of range", fn);
+  if (a.cdf_lines != nullptr) {
+    RSA_CHECK_ARG(a.lines_log2 >= 0 && a.lines_log2 <= 28 && ((uintptr_t)a.cdf_lines & 127) == 0,
                   "%s: cdf_lines must be 128-byte aligned with lines_log2 in [0, 28]", fn);
   } else {
-    RSA_CHECK_ARG(guide != nullptr, "%s: guide is null", fn);
-    RSA_CHECK_ARG(guide_log2 >= 0 && guide_log2 <= 28, "%s: guide_log2 must be in [0, 28]", fn);
+    RSA_CHECK_ARG(a.guide != nullptr, "%s: guide is null", fn);
+    RSA_CHECK_ARG(a.guide_log2 >= 0 && a.guide_log2 <= 28, "%s: guide_log2 must be in [0, 28]", fn);
   }
+  return RSA_OK;
+}
+
+// Both entry points: U_GIVEN looks the caller's uniforms (a.u_in) up, !U_GIVEN draws them.  With a direct-lookup table and no
+// bucket lines, the batched LUT kernel; otherwise the kernel that picks the structure per call.
+template <bool U_GIVEN>
+static void launch_popular(const rsa_popular_args& a, const PhiloxCall& pc, hipStream_t s) {
+  const float* u = U_GIVEN ? a.u_in : nullptr;
+  float* u_out = U_GIVEN ? nullptr : a.u_out;
+  if (a.cdf_lut != nullptr && a.cdf_lines == nullptr) {
+    hipLaunchKernelGGL((sample_popular_lut_kernel<U_GIVEN, LUT_BATCH>), dim3((unsigned)((a.numel + 256 * LUT_BATCH - 1) / (256 * LUT_BATCH))),
+                       dim3(256), 0, s, a.table, a.pop_prob, reinterpret_cast<const float4*>(a.cdf_lut), a.n_items, a.guide_log2, u,
+                       a.ids, a.logp, u_out, a.numel, pc);
+    return;
+  }
+  hipLaunchKernelGGL(sample_popular_kernel<U_GIVEN>, dim3(grid_for(a.numel)), dim3(256), 0, s, a.table, a.pop_prob, a.guide, a.cdf_lut,
+                     a.cdf_lines, (int)a.lines_log2, a.n_items, a.guide_log2, u, a.ids, a.logp, u_out, a.numel, pc);
+}
+
+int rsa::sample_popular(const rsa_popular_args& a, rsa_stream_t stream) {
+  RSA_CHECK_ARG(a.numel >= 0, "rsa_sample_popular: numel < 0");
+  if (a.numel == 0) return RSA_OK;
+  if (int rc = check_popular("rsa_sample_popular", a)) return rc;
+  RSA_CHECK_ARG(a.ids != nullptr, "rsa_sample_popular: neg_ids is null");
+  RSA_CHECK_ARG(a.grid_threads > 0 && (a.offset & 3) == 0, "rsa_sample_popular: bad philox state");
+  launch_popular<false>(a, PhiloxCall{a.seed, a.offset >> 2, a.grid_threads, a.elem_base}, (hipStream_t)stream);
+  RSA_CHECK_LAUNCH("rsa_sample_popular");
   return RSA_OK;
 }
 
 extern "C" int rsa_sample_popular(const rsa_popular_args* args, rsa_stream_t stream) {
   rsa_popular_args a;
   if (int rc = load_args(a, args, "rsa_sample_popular")) return rc;
-  return sample_popular_impl(a.table, a.pop_prob, a.guide, a.n_items, a.guide_log2, a.ids, a.logp, a.u_out, a.numel, a.seed,
-                             a.offset, a.grid_threads, a.elem_base, a.cdf_lut, a.cdf_lines, a.lines_log2, stream);
+  return sample_popular(a, stream);
 }
-
-int rsa::sample_popular_impl(const float* table, const float* pop_prob, const int32_t* guide, int64_t n_items,
-                             int32_t guide_log2, int64_t* neg_ids, float* neg_logp, float* u_out, int64_t numel,
-                             uint64_t seed, uint64_t offset, uint32_t grid_threads, uint64_t elem_base,
-                             const float* cdf_lut, const float* cdf_lines, int32_t lines_log2, rsa_stream_t stream) {
-  RSA_CHECK_ARG(numel >= 0, "rsa_sample_popular: numel < 0");
-  if (numel == 0) return RSA_OK;
-  if (int rc = check_popular("rsa_sample_popular", table, pop_prob, guide, n_items, guide_log2, cdf_lines, lines_log2)) return rc;
-  RSA_CHECK_ARG(neg_ids != nullptr, "rsa_sample_popular: neg_ids is null");
-  RSA_CHECK_ARG(grid_threads > 0 && (offset & 3) == 0, "rsa_sample_popular: bad philox state");
-  PhiloxCall pc{seed, offset >> 2, grid_threads, elem_base};
-  if (cdf_lut != nullptr && cdf_lines == nullptr) {
-    hipLaunchKernelGGL((sample_popular_lut_kernel<false, LUT_BATCH>), dim3((unsigned)((numel + 256 * LUT_BATCH - 1) / (256 * LUT_BATCH))),
-                       dim3(256), 0, (hipStream_t)stream, table, pop_prob, reinterpret_cast<const float4*>(cdf_lut),
-                       n_items, guide_log2, (const float*)nullptr, neg_ids, neg_logp, u_out, numel, pc);
-    RSA_CHECK_LAUNCH("rsa_sample_popular");
-    return RSA_OK;
-  }
-  hipLaunchKernelGGL(sample_popular_kernel<false>, dim3(grid_for(numel)), dim3(256), 0, (hipStream_t)stream, table,
-                     pop_prob, guide, cdf_lut, cdf_lines, (int)lines_log2, n_items, guide_log2, (const float*)nullptr,
-                     neg_ids, neg_logp, u_out, numel, pc);
-  RSA_CHECK_LAUNCH("rsa_sample_popular");
-  return RSA_OK;
-}
-
-static int popular_lookup_impl(const float* table, const float* pop_prob, const int32_t* guide, int64_t n_items,
-                               int32_t guide_log2, const float* u, int64_t* ids, float* logp, int64_t numel,
-                               const float* cdf_lut, const float* cdf_lines, int32_t lines_log2, rsa_stream_t stream);
 
 extern "C" int rsa_popular_lookup(const rsa_popular_args* args, rsa_stream_t stream) {
   rsa_popular_args a;
   if (int rc = load_args(a, args, "rsa_popular_lookup")) return rc;
-  return popular_lookup_impl(a.table, a.pop_prob, a.guide, a.n_items, a.guide_log2, a.u_in, a.ids, a.logp, a.numel, a.cdf_lut,
-                             a.cdf_lines, a.lines_log2, stream);
-}
-
-static int popular_lookup_impl(const float* table, const float* pop_prob, const int32_t* guide, int64_t n_items,
-                               int32_t guide_log2, const float* u, int64_t* ids, float* logp, int64_t numel,
-                               const float* cdf_lut, const float* cdf_lines, int32_t lines_log2, rsa_stream_t stream) {
-  RSA_CHECK_ARG(numel >= 0, "rsa_popular_lookup: numel < 0");
-  if (numel == 0) return RSA_OK;
-  if (int rc = check_popular("rsa_popular_lookup", table, pop_prob, guide, n_items, guide_log2, cdf_lines, lines_log2)) return rc;
-  RSA_CHECK_ARG(u && ids, "rsa_popular_lookup: u/ids is null");
-  PhiloxCall pc{0, 0, 1, 0};
-  if (cdf_lut != nullptr && cdf_lines == nullptr) {
-    hipLaunchKernelGGL((sample_popular_lut_kernel<true, LUT_BATCH>), dim3((unsigned)((numel + 256 * LUT_BATCH - 1) / (256 * LUT_BATCH))),
-                       dim3(256), 0, (hipStream_t)stream, table, pop_prob, reinterpret_cast<const float4*>(cdf_lut),
-                       n_items, guide_log2, u, ids, logp, (float*)nullptr, numel, pc);
-    RSA_CHECK_LAUNCH("rsa_popular_lookup");
-    return RSA_OK;
-  }
-  hipLaunchKernelGGL(sample_popular_kernel<true>, dim3(grid_for(numel)), dim3(256), 0, (hipStream_t)stream, table,
-                     pop_prob, guide, cdf_lut, cdf_lines, (int)lines_log2, n_items, guide_log2, u, ids, logp,
-                     (float*)nullptr, numel, pc);
+  RSA_CHECK_ARG(a.numel >= 0, "rsa_popular_lookup: numel < 0");
+  if (a.numel == 0) return RSA_OK;
+  if (int rc = check_popular("rsa_popular_lookup", a)) return rc;
+  RSA_CHECK_ARG(a.u_in && a.ids, "rsa_popular_lookup: u/ids is null");
+  launch_popular<true>(a, PhiloxCall{0, 0, 1, 0}, (hipStream_t)stream);
   RSA_CHECK_LAUNCH("rsa_popular_lookup");
   return RSA_OK;
 }

@@ -12,7 +12,7 @@
 //   rsa_scatter_f32   : home side, dst[pos[i]] = src[i]  (returned scores -> [pos_score | neg_score] buffer)
 // Fixed-capacity exchange, version 2 (the default; second half of this file):
 //   rsa_shard_sample_route / rsa_shard_score_segments (rsa_fused.hip) / rsa_shard_home / rsa_shard_unpack_segments
-#include "rsa_common.hpp"
+#include "rsa_launch.hpp"
 
 namespace rsa {
 
@@ -890,20 +890,15 @@ template <int LOSS>
 static void launch_home(const HomeArgs& h, hipStream_t s) {
   const int n = h.n;
   const int qpw = n <= 64 ? 8 : (n <= 128 ? 4 : (n <= 256 ? 2 : 1));
-  int64_t blocks = (h.n_queries + 4 * qpw - 1) / (4 * qpw);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  const dim3 grid((unsigned)blocks), block(256);
-  if (qpw == 8) hipLaunchKernelGGL((shard_home_small_kernel<LOSS, 8>), grid, block, 0, s, h);
-  else if (qpw == 4) hipLaunchKernelGGL((shard_home_small_kernel<LOSS, 4>), grid, block, 0, s, h);
-  else if (qpw == 2) hipLaunchKernelGGL((shard_home_small_kernel<LOSS, 2>), grid, block, 0, s, h);
-  else hipLaunchKernelGGL(shard_home_kernel<LOSS>, grid, block, 0, s, h);
+  const dim3 grid(grid_1d(h.n_queries, 4 * qpw, 2048)), block(256);
+  const bool small = dispatch_int<8, 4, 2>(qpw, [&](auto QPW) {
+    hipLaunchKernelGGL((shard_home_small_kernel<LOSS, QPW()>), grid, block, 0, s, h);
+  });
+  if (!small) hipLaunchKernelGGL(shard_home_kernel<LOSS>, grid, block, 0, s, h);
 }
 
-static inline int grid1d(int64_t numel) {
-  int64_t b = (numel + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
+// the element-wise kernels of this file: one element per thread, grid-strided past 2048 workgroups
+static inline unsigned grid_elems(int64_t numel) { return grid_1d(numel, 256, 2048); }
 
 }  // namespace rsa
 
@@ -914,19 +909,13 @@ extern "C" int rsa_shard_count(const int64_t* pos_ids, const int64_t* neg_ids, i
   RSA_CHECK_ARG(n_queries >= 0 && num_neg >= 0 && rows_per_shard >= 0, "rsa_shard_count: bad sizes");
   RSA_CHECK_ARG(n_shards >= 1 && n_shards <= 64, "rsa_shard_count: n_shards must be in [1, 64]");
   RSA_CHECK_ARG(counts != nullptr, "rsa_shard_count: counts is null");
-  hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * n_shards, (hipStream_t)stream);
-  if (e != hipSuccess) {
-    rsa::set_error("rsa_shard_count: memset failed: %s", hipGetErrorString(e));
-    return RSA_ERR_HIP;
-  }
+  RSA_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * n_shards, (hipStream_t)stream), "rsa_shard_count");
   if (n_queries == 0) return RSA_OK;
   RSA_CHECK_ARG(pos_ids && (neg_ids || num_neg == 0), "rsa_shard_count: null ids");
   RSA_CHECK_ARG(n_queries * (num_neg + 1) < (1ll << 32), "rsa_shard_count: more than 2^32 elements");
   const RouteShape sh{pos_ids, neg_ids, n_queries, (int)num_neg, (int)n_shards, rows_per_shard,
                       make_fastdiv((uint64_t)num_neg + 1), make_fastdiv((uint64_t)(rows_per_shard ? rows_per_shard : n_shards))};
-  int64_t count_blocks = (n_queries * (num_neg + 1) + ROUTE_CHUNK - 1) / ROUTE_CHUNK;
-  if (count_blocks > 4096) count_blocks = 4096;
-  hipLaunchKernelGGL(shard_count_kernel, dim3((unsigned)count_blocks), dim3(256), 0, (hipStream_t)stream, sh, counts);
+  hipLaunchKernelGGL(shard_count_kernel, dim3(grid_1d(n_queries * (num_neg + 1), ROUTE_CHUNK, 4096)), dim3(256), 0, (hipStream_t)stream, sh, counts);
   RSA_CHECK_LAUNCH("rsa_shard_count");
   return RSA_OK;
 }
@@ -956,7 +945,7 @@ extern "C" int rsa_shard_unpack(const int64_t* keys, int64_t numel, int64_t* loc
   RSA_CHECK_ARG(numel >= 0, "rsa_shard_unpack: numel < 0");
   if (numel == 0) return RSA_OK;
   RSA_CHECK_ARG(keys && local_rows && query_index, "rsa_shard_unpack: null pointer");
-  hipLaunchKernelGGL(shard_unpack_kernel, dim3(grid1d(numel)), dim3(256), 0, (hipStream_t)stream, keys, numel,
+  hipLaunchKernelGGL(shard_unpack_kernel, dim3(grid_elems(numel)), dim3(256), 0, (hipStream_t)stream, keys, numel,
                      local_rows, query_index);
   RSA_CHECK_LAUNCH("rsa_shard_unpack");
   return RSA_OK;
@@ -967,7 +956,7 @@ extern "C" int rsa_scatter_f32(const float* src, const int64_t* positions, int64
   RSA_CHECK_ARG(numel >= 0, "rsa_scatter_f32: numel < 0");
   if (numel == 0) return RSA_OK;
   RSA_CHECK_ARG(src && positions && dst, "rsa_scatter_f32: null pointer");
-  hipLaunchKernelGGL(scatter_f32_kernel, dim3(grid1d(numel)), dim3(256), 0, (hipStream_t)stream, src, positions, numel,
+  hipLaunchKernelGGL(scatter_f32_kernel, dim3(grid_elems(numel)), dim3(256), 0, (hipStream_t)stream, src, positions, numel,
                      dst);
   RSA_CHECK_LAUNCH("rsa_scatter_f32");
   return RSA_OK;
@@ -978,7 +967,7 @@ extern "C" int rsa_gather_f32(const float* src, const int64_t* positions, int64_
   RSA_CHECK_ARG(numel >= 0, "rsa_gather_f32: numel < 0");
   if (numel == 0) return RSA_OK;
   RSA_CHECK_ARG(src && positions && dst, "rsa_gather_f32: null pointer");
-  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid1d(numel)), dim3(256), 0, (hipStream_t)stream, src, positions, numel,
+  hipLaunchKernelGGL(gather_f32_kernel, dim3(grid_elems(numel)), dim3(256), 0, (hipStream_t)stream, src, positions, numel,
                      dst);
   RSA_CHECK_LAUNCH("rsa_gather_f32");
   return RSA_OK;
@@ -997,6 +986,42 @@ extern "C" int32_t rsa_shard_route_query_groups(int32_t num_neg, uint32_t grid_t
   return (int64_t)ql * n_shards <= ROUTE_CNT ? ql : 0;
 }
 
+// How a routing call enumerates its negatives -- Philox blocks of the torch call (see the kernel), or the same shape made up
+// for given ids (four interleaved quarters) -- and the workgroups that takes.  One definition: rsa_shard_route_workgroups
+// sizes the deterministic mode's scratch by what rsa_shard_sample_route launches.  An in-kernel sampler needs grid_threads > 0.
+struct RoutePlan {
+  PhiloxCall pc;
+  int unroll;
+  uint64_t k_lo;
+  int64_t n_groups;        // work items that are Philox blocks
+  int64_t blocks;
+};
+
+static RoutePlan plan_route(const rsa_shard_route_args& a) {
+  RoutePlan p;
+  const int64_t n_neg = a.n_queries * a.num_neg;
+  if (a.sampler == RSA_SAMPLER_GIVEN || n_neg == 0) {
+    int64_t quarter = ((n_neg + 3) / 4 + 255) / 256 * 256;
+    if (quarter < 256) quarter = 256;
+    p.pc = PhiloxCall{0, 0, (uint32_t)quarter, 0};
+    p.unroll = 4;
+  } else {
+    p.pc = PhiloxCall{a.seed, a.offset >> 2, a.grid_threads, a.elem_base};
+    p.unroll = (a.sampler == RSA_SAMPLER_UNIFORM && (uint64_t)(a.n_items - 1) >= (1ull << 28)) ? 2 : 4;   // ATen: 64-bit draws
+  }
+  const uint64_t T = p.pc.grid_threads;
+  uint64_t k_hi = 0;
+  p.k_lo = 0;
+  if (n_neg > 0) {
+    p.k_lo = (p.pc.elem_base / T) / p.unroll;
+    k_hi = ((p.pc.elem_base + (uint64_t)n_neg - 1) / T) / p.unroll;
+  }
+  p.n_groups = n_neg > 0 ? (int64_t)((k_hi - p.k_lo + 1) * T) : 0;
+  p.blocks = (p.n_groups + a.n_queries + ROUTE_ITEMS_PER_BLOCK - 1) / ROUTE_ITEMS_PER_BLOCK;
+  if (p.blocks < (int64_t)a.n_slices * a.n_banks) p.blocks = (int64_t)a.n_slices * a.n_banks;     // every bank owns at least one workgroup
+  return p;
+}
+
 extern "C" int rsa_shard_sample_route(const rsa_shard_route_args* a, rsa_stream_t stream) {
   RSA_CHECK_ARG(a != nullptr, "rsa_shard_sample_route: args is null");
   RSA_CHECK_ARG(a->n_queries >= 0 && a->num_neg >= 0 && a->rows_per_shard >= 0 && a->rows_per_shard < (1ll << 32),
@@ -1011,19 +1036,14 @@ extern "C" int rsa_shard_sample_route(const rsa_shard_route_args* a, rsa_stream_
   const bool count_only = a->send_keys == nullptr;
   RSA_CHECK_ARG(!count_only || a->counts_out != nullptr, "rsa_shard_sample_route: nothing to do (send_keys and counts_out null)");
   if (a->n_queries == 0) {
-    if (a->counts_out) {
-      if (hipMemsetAsync(a->counts_out, 0, sizeof(int32_t) * a->n_slices * a->n_shards * a->n_banks, (hipStream_t)stream) != hipSuccess) {
-        rsa::set_error("rsa_shard_sample_route: memset failed");
-        return RSA_ERR_HIP;
-      }
-    }
+    if (a->counts_out)
+      RSA_CHECK_HIP(hipMemsetAsync(a->counts_out, 0, sizeof(int32_t) * a->n_slices * a->n_shards * a->n_banks, (hipStream_t)stream),
+                    "rsa_shard_sample_route");
     if (!count_only) {     // empty segments still carry their headers
       const int64_t stride = a->capacity + RSA_SHARD_HDR;
-      if (hipMemset2DAsync(a->send_keys, sizeof(int64_t) * stride, 0, sizeof(int64_t) * RSA_SHARD_HDR,
-                           (size_t)a->n_slices * a->n_shards * a->n_banks, (hipStream_t)stream) != hipSuccess) {
-        rsa::set_error("rsa_shard_sample_route: memset failed");
-        return RSA_ERR_HIP;
-      }
+      RSA_CHECK_HIP(hipMemset2DAsync(a->send_keys, sizeof(int64_t) * stride, 0, sizeof(int64_t) * RSA_SHARD_HDR,
+                                     (size_t)a->n_slices * a->n_shards * a->n_banks, (hipStream_t)stream),
+                    "rsa_shard_sample_route");
     }
     return RSA_OK;
   }
@@ -1072,24 +1092,10 @@ extern "C" int rsa_shard_sample_route(const rsa_shard_route_args* a, rsa_stream_
   r.n_slices = a->n_slices;
   r.n_banks = a->n_banks;
   r.skip_pos = a->skip_pos;
-  // the enumeration of the negatives: Philox blocks of the torch call (see the kernel), or the same shape made up for
-  // given ids (four interleaved quarters)
-  if (a->sampler == RSA_SAMPLER_GIVEN || n_neg == 0) {
-    int64_t quarter = ((n_neg + 3) / 4 + 255) / 256 * 256;
-    if (quarter < 256) quarter = 256;
-    r.pc = PhiloxCall{0, 0, (uint32_t)quarter, 0};
-    r.unroll = 4;
-  } else {
-    r.pc = PhiloxCall{a->seed, a->offset >> 2, a->grid_threads, a->elem_base};
-    r.unroll = (a->sampler == RSA_SAMPLER_UNIFORM && (uint64_t)(a->n_items - 1) >= (1ull << 28)) ? 2 : 4;   // ATen: 64-bit draws
-  }
-  const uint64_t T = r.pc.grid_threads;
-  uint64_t k_lo = 0, k_hi = 0;
-  if (n_neg > 0) {
-    k_lo = (r.pc.elem_base / T) / r.unroll;
-    k_hi = ((r.pc.elem_base + (uint64_t)n_neg - 1) / T) / r.unroll;
-  }
-  r.k_lo = k_lo;
+  const RoutePlan plan = plan_route(*a);
+  r.pc = plan.pc;
+  r.unroll = plan.unroll;
+  r.k_lo = plan.k_lo;
   r.group_ql = 0;
   if (a->group_by_query) {
     RSA_CHECK_ARG(a->skip_pos && a->sampler != RSA_SAMPLER_GIVEN && n_neg > 0,
@@ -1102,15 +1108,14 @@ extern "C" int rsa_shard_sample_route(const rsa_shard_route_args* a, rsa_stream_
   r.det_phase = 0;
   r.wg_cnt = nullptr;
   r.wg_base = nullptr;
-  r.n_groups = n_neg > 0 ? (int64_t)((k_hi - k_lo + 1) * T) : 0;
+  r.n_groups = plan.n_groups;
   RSA_CHECK_ARG(r.n_groups + a->n_queries < (1ll << 32), "rsa_shard_sample_route: too many work items");
   r.by_width = make_div32((uint64_t)a->num_neg + 1);
   r.by_rows = make_div32((uint64_t)(a->rows_per_shard ? a->rows_per_shard : a->n_shards));    // 0: interleaved rows
   r.by_n = make_div32((uint64_t)(a->num_neg > 0 ? a->num_neg : 1));
-  r.by_gt = make_div32(T);
+  r.by_gt = make_div32(r.pc.grid_threads);
   r.by_range = make_div32((uint64_t)(a->n_items - 1));        // 32-bit draws only (ranges below 2^28)
-  int64_t blocks = (r.n_groups + a->n_queries + ROUTE_ITEMS_PER_BLOCK - 1) / ROUTE_ITEMS_PER_BLOCK;
-  if (blocks < (int64_t)a->n_slices * a->n_banks) blocks = (int64_t)a->n_slices * a->n_banks;     // every bank owns at least one workgroup
+  const int64_t blocks = plan.blocks;
   RSA_CHECK_ARG(blocks < (1ll << 31), "rsa_shard_sample_route: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
   if (a->deterministic && !count_only) {
@@ -1135,8 +1140,9 @@ extern "C" int rsa_shard_sample_route(const rsa_shard_route_args* a, rsa_stream_
     RSA_CHECK_LAUNCH("rsa_shard_sample_route(deterministic)");
     return RSA_OK;
   }
-  if (count_only) hipLaunchKernelGGL(shard_sample_route_kernel<true>, grid, block, 0, (hipStream_t)stream, r);
-  else hipLaunchKernelGGL(shard_sample_route_kernel<false>, grid, block, 0, (hipStream_t)stream, r);
+  dispatch_bool(count_only, [&](auto COUNT_ONLY) {
+    hipLaunchKernelGGL(shard_sample_route_kernel<COUNT_ONLY()>, grid, block, 0, (hipStream_t)stream, r);
+  });
   RSA_CHECK_LAUNCH("rsa_shard_sample_route");
   return RSA_OK;
 }
@@ -1144,28 +1150,8 @@ extern "C" int rsa_shard_sample_route(const rsa_shard_route_args* a, rsa_stream_
 // workgroups rsa_shard_sample_route launches for these arguments (sizes the deterministic mode's wg_scratch: 2 x this x n_shards ints)
 extern "C" int64_t rsa_shard_route_workgroups(const rsa_shard_route_args* a) {
   if (a == nullptr || a->n_queries <= 0) return 0;
-  const int64_t n_neg = a->n_queries * a->num_neg;
-  uint64_t T;
-  int unroll = 4;
-  uint64_t elem_base = 0;
-  if (a->sampler == RSA_SAMPLER_GIVEN || n_neg == 0) {
-    int64_t quarter = ((n_neg + 3) / 4 + 255) / 256 * 256;
-    if (quarter < 256) quarter = 256;
-    T = (uint64_t)quarter;
-  } else {
-    if (a->grid_threads == 0) return 0;
-    T = a->grid_threads;
-    elem_base = a->elem_base;
-    unroll = (a->sampler == RSA_SAMPLER_UNIFORM && (uint64_t)(a->n_items - 1) >= (1ull << 28)) ? 2 : 4;
-  }
-  int64_t n_groups = 0;
-  if (n_neg > 0) {
-    const uint64_t k_lo = (elem_base / T) / unroll, k_hi = ((elem_base + (uint64_t)n_neg - 1) / T) / unroll;
-    n_groups = (int64_t)((k_hi - k_lo + 1) * T);
-  }
-  int64_t blocks = (n_groups + a->n_queries + ROUTE_ITEMS_PER_BLOCK - 1) / ROUTE_ITEMS_PER_BLOCK;
-  if (blocks < (int64_t)a->n_slices * a->n_banks) blocks = (int64_t)a->n_slices * a->n_banks;
-  return blocks;
+  if (a->sampler != RSA_SAMPLER_GIVEN && a->num_neg != 0 && a->grid_threads == 0) return 0;
+  return plan_route(*a).blocks;
 }
 
 extern "C" int rsa_shard_home(const rsa_shard_home_args* a, rsa_stream_t stream) {
@@ -1201,9 +1187,7 @@ extern "C" int rsa_shard_home(const rsa_shard_home_args* a, rsa_stream_t stream)
     h.loss_partials = reinterpret_cast<float*>(sc + SCRATCH_FUSED_PARTIALS);
   }
   hipStream_t s = (hipStream_t)stream;
-  if (a->loss == 0) launch_home<0>(h, s);
-  else if (a->loss == 1) launch_home<1>(h, s);
-  else launch_home<2>(h, s);
+  dispatch_int<0, 1, 2>(a->loss, [&](auto LOSS) { launch_home<LOSS()>(h, s); });
   RSA_CHECK_LAUNCH("rsa_shard_home");
   return RSA_OK;
 }
@@ -1214,7 +1198,7 @@ extern "C" int rsa_shard_scatter_slots(const float* dpos, const float* dneg, con
   if (n_queries == 0) return RSA_OK;
   RSA_CHECK_ARG(dpos && (dneg || num_neg == 0) && slot_of && d_send, "rsa_shard_scatter_slots: null pointer");
   RSA_CHECK_ARG(n_queries * (num_neg + 1) < (1ll << 31), "rsa_shard_scatter_slots: more than 2^31 elements");
-  hipLaunchKernelGGL(shard_scatter_slots_kernel, dim3(grid1d(n_queries * (num_neg + 1))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(shard_scatter_slots_kernel, dim3(grid_elems(n_queries * (num_neg + 1))), dim3(256), 0, (hipStream_t)stream,
                      dpos, dneg, slot_of, n_queries, (int)num_neg, make_fastdiv((uint64_t)num_neg + 1), d_send);
   RSA_CHECK_LAUNCH("rsa_shard_scatter_slots");
   return RSA_OK;
@@ -1227,7 +1211,7 @@ extern "C" int rsa_shard_unpack_segments(const int64_t* keys, int64_t n_segments
   const int64_t numel = n_segments * stride;
   if (numel == 0) return RSA_OK;
   RSA_CHECK_ARG(keys && local_rows && query_index, "rsa_shard_unpack_segments: null pointer");
-  hipLaunchKernelGGL(shard_unpack_segments_kernel, dim3(grid1d(numel)), dim3(256), 0, (hipStream_t)stream, keys, numel, stride,
+  hipLaunchKernelGGL(shard_unpack_segments_kernel, dim3(grid_elems(numel)), dim3(256), 0, (hipStream_t)stream, keys, numel, stride,
                      local_rows, query_index, scale_in, step_dropped, scale_out);
   RSA_CHECK_LAUNCH("rsa_shard_unpack_segments");
   return RSA_OK;

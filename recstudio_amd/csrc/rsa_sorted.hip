@@ -314,8 +314,6 @@ __global__ __launch_bounds__(256) void classify_solo_kernel(uint64_t* __restrict
   }
 }
 
-static inline int64_t align256s(int64_t b) { return (b + 255) / 256 * 256; }
-
 // ---- the workspace of a sorted scatter over `max_total` elements: two packed-pair buffers, the radix sort's counters,
 // per 64-element chunk two partial rows (sized for dim = 256) and the segment record
 // Chunks of the apply pass: 64 sorted elements per wave, 16 for a pass over at most SMALL_TOTAL elements (a function of the
@@ -330,25 +328,27 @@ static int64_t sorted_max_chunks(int64_t max_total) {
   return by64 > by16 ? by64 : by16;
 }
 
-int64_t sorted_workspace_bytes(int64_t max_total) {
+static SortedLayout carve_sorted(Carver& ws, int64_t max_total) {
   const int64_t chunks = sorted_max_chunks(max_total);
-  return 2 * align256s(max_total * 8) + align256s(radix_temp_bytes(max_total)) + 2 * align256s(chunks * 256 * 4) +
-         align256s(chunks * META_STRIDE * 4) + 256;
+  SortedLayout L;
+  L.pairs_a = ws.take<uint64_t>(max_total);
+  L.pairs_b = ws.take<uint64_t>(max_total);
+  L.temp = ws.take<char>(radix_temp_bytes(max_total));
+  L.lead_part = ws.take<float>(chunks * 256);
+  L.trail_part = ws.take<float>(chunks * 256);
+  L.meta = ws.take<int32_t>(chunks * META_STRIDE);
+  return L;
+}
+
+int64_t sorted_workspace_bytes(int64_t max_total) {
+  Carver sizing(nullptr);
+  carve_sorted(sizing, max_total);
+  return align256(sizing.bytes()) + 256;
 }
 
 SortedLayout sorted_layout(void* workspace, int64_t max_total) {
-  char* ws = reinterpret_cast<char*>(workspace);
-  const int64_t seg = align256s(max_total * 8);
-  const int64_t max_chunks = sorted_max_chunks(max_total);
-  SortedLayout L;
-  L.pairs_a = reinterpret_cast<uint64_t*>(ws);
-  L.pairs_b = reinterpret_cast<uint64_t*>(ws + seg);
-  L.temp = ws + 2 * seg;
-  char* tail = ws + 2 * seg + align256s(radix_temp_bytes(max_total));
-  L.lead_part = reinterpret_cast<float*>(tail);
-  L.trail_part = reinterpret_cast<float*>(tail + align256s(max_chunks * 256 * 4));
-  L.meta = reinterpret_cast<int32_t*>(tail + 2 * align256s(max_chunks * 256 * 4));
-  return L;
+  Carver ws(workspace);
+  return carve_sorted(ws, max_total);
 }
 
 int classify_solo(uint64_t* pairs, int64_t total, int64_t pad_row, int64_t drop_key, uint8_t* solo, hipStream_t s, const char* who) {
@@ -357,16 +357,11 @@ int classify_solo(uint64_t* pairs, int64_t total, int64_t pad_row, int64_t drop_
   // exp(-total / rows), i.e. most elements are solo below total / rows = ln 2.  A skewed draw has fewer solo elements than that;
   // the guess only decides which of the two polarities stores fewer bytes.
   const bool mostly_solo = (double)total < 0.69 * (double)drop_key;
-  if (hipMemsetAsync(solo, mostly_solo ? 1 : 0, (size_t)total, s) != hipSuccess) {
-    rsa::set_error("%s: memset failed", who);
-    return RSA_ERR_HIP;
-  }
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (mostly_solo)
-    hipLaunchKernelGGL(classify_solo_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, pairs, total, pad, (int32_t)drop_key, solo);
-  else
-    hipLaunchKernelGGL(classify_solo_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, pairs, total, pad, (int32_t)drop_key, solo);
+  RSA_CHECK_HIP(hipMemsetAsync(solo, mostly_solo ? 1 : 0, (size_t)total, s), who);
+  dispatch_bool(mostly_solo, [&](auto MOSTLY_SOLO) {
+    hipLaunchKernelGGL(classify_solo_kernel<MOSTLY_SOLO()>, dim3(grid_1d(total, 256, 8192)), dim3(256), 0, s, pairs, total, pad,
+                       (int32_t)drop_key, solo);
+  });
   RSA_CHECK_LAUNCH(who);
   return RSA_OK;
 }
@@ -376,29 +371,25 @@ template <class DEC>
 static int apply_sorted_pairs(const uint64_t* pairs, int64_t total, const float* query, int32_t dim, const DEC& dec,
                               const float* upstream, int64_t drop_key, int64_t pad_row, float* target, AdamArgs adam,
                               const SortedLayout& L, hipStream_t s, int64_t key_base = 0, int64_t elem_base = 0) {
-  if (dim != 64 && dim != 128 && dim != 256) {
-    rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", dim);
-    return RSA_ERR_UNSUPPORTED;
-  }
   const int ce = sorted_chunk_elems(total);
   const unsigned chunks = (unsigned)((total + ce - 1) / ce);
   dim3 grid((chunks + 3) / 4), block(256);
   const int32_t pad = (int32_t)(pad_row < 0 || pad_row >= (1ll << 31) ? -2 : pad_row);
-  const bool nt = RSA_SORTED_NT == 1 || (RSA_SORTED_NT == 2 && (size_t)drop_key * dim * sizeof(float) > (512ull << 20));      // (drop_key = the table's row count)
-#define RSA_SORTED_LAUNCH(NDW)                                                                                                 \
-  if (nt) hipLaunchKernelGGL((sorted_apply_kernel<NDW, DEC, true>), grid, block, 0, s, pairs, total, query, dec, upstream, pad, \
-                             (int32_t)drop_key, target, adam, L.lead_part, L.trail_part, L.meta, (int32_t)key_base,            \
-                             (int32_t)elem_base, (int32_t)ce);                                                                   \
-  else hipLaunchKernelGGL((sorted_apply_kernel<NDW, DEC, false>), grid, block, 0, s, pairs, total, query, dec, upstream, pad,   \
-                          (int32_t)drop_key, target, adam, L.lead_part, L.trail_part, L.meta, (int32_t)key_base, (int32_t)elem_base, (int32_t)ce); \
-  hipLaunchKernelGGL(sorted_finish_kernel<NDW>, grid, block, 0, s, (int64_t)chunks, upstream, pad, target, adam, L.lead_part,   \
-                     L.trail_part, L.meta)
-  switch (dim) {
-    case 64: RSA_SORTED_LAUNCH(1); break;
-    case 128: RSA_SORTED_LAUNCH(2); break;
-    default: RSA_SORTED_LAUNCH(4); break;
+  const bool nt = RSA_SORTED_NT == 1 || (RSA_SORTED_NT == 2 && streams_past_cache(drop_key, dim));      // (drop_key = the table's row count)
+  const bool built = dispatch_dim<64, 128, 256>(dim, [&](auto D) {
+    constexpr int NDW = D() / 64;
+    dispatch_bool(nt, [&](auto NT) {
+      hipLaunchKernelGGL((sorted_apply_kernel<NDW, DEC, NT()>), grid, block, 0, s, pairs, total, query, dec, upstream, pad,
+                         (int32_t)drop_key, target, adam, L.lead_part, L.trail_part, L.meta, (int32_t)key_base, (int32_t)elem_base,
+                         (int32_t)ce);
+    });
+    hipLaunchKernelGGL(sorted_finish_kernel<NDW>, grid, block, 0, s, (int64_t)chunks, upstream, pad, target, adam, L.lead_part,
+                       L.trail_part, L.meta);
+  });
+  if (!built) {
+    rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", dim);
+    return RSA_ERR_UNSUPPORTED;
   }
-#undef RSA_SORTED_LAUNCH
   RSA_CHECK_LAUNCH("rsa_rows_update_sorted(apply)");
   return RSA_OK;
 }
@@ -477,65 +468,25 @@ static uint64_t* step_sorted(const SortedLayout& L, int64_t n_items) {
 }
 
 // (item id, element) pairs of a step, radix-sorted by id into the workspace; with `solo` also the classification pass
-static int sort_elements_impl(const int64_t* pos_ids, const int64_t* neg_ids, int64_t n_queries, int32_t num_neg, int64_t n_items,
-                              int64_t pad_row, uint8_t* solo, void* workspace, int64_t workspace_bytes, rsa_stream_t stream,
-                              const char* who) {
-  RSA_CHECK_ARG(n_queries >= 0 && num_neg >= 1 && n_items >= 1 && n_items < (1ll << 31), "%s: bad sizes", who);
-  if (n_queries == 0) return RSA_OK;
-  RSA_CHECK_ARG(neg_ids != nullptr, "%s: neg_ids is null", who);
-  const int has_pos = pos_ids != nullptr ? 1 : 0;
-  const int64_t total = n_queries * (int64_t)(num_neg + has_pos);
+static int sort_step_elements(const rsa_rows_update_args& a, uint8_t* solo, hipStream_t s, const char* who) {
+  RSA_CHECK_ARG(a.n_queries >= 0 && a.num_neg >= 1 && a.n_items >= 1 && a.n_items < (1ll << 31), "%s: bad sizes", who);
+  if (a.n_queries == 0) return RSA_OK;
+  RSA_CHECK_ARG(a.neg_ids != nullptr, "%s: neg_ids is null", who);
+  const int has_pos = a.pos_ids != nullptr ? 1 : 0;
+  const int64_t total = a.n_queries * (int64_t)(a.num_neg + has_pos);
   RSA_CHECK_ARG(total < (1ll << 31), "%s: more than 2^31 elements", who);
-  const int64_t need = rsa_scatter_rows_sorted_workspace_bytes(n_queries, num_neg, n_items);
-  RSA_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)workspace_bytes,
+  const int64_t need = rsa_scatter_rows_sorted_workspace_bytes(a.n_queries, a.num_neg, a.n_items);
+  RSA_CHECK_ARG(a.workspace && a.workspace_bytes >= need, "%s: workspace too small (%lld < %lld)", who, (long long)a.workspace_bytes,
                 (long long)need);
-  hipStream_t s = (hipStream_t)stream;
-  const SortedLayout L = sorted_layout(workspace, n_queries * (int64_t)(num_neg + 1));
+  const SortedLayout L = sorted_layout(a.workspace, a.n_queries * (int64_t)(a.num_neg + 1));
   // pass 0 of the sort reads the id tensors themselves (no key-extraction launch, no id round trip)
-  const SrcStepIds src{pos_ids, neg_ids, n_items, num_neg, num_neg + has_pos, has_pos};
-  if (radix_sort_pairs(src, L.pairs_a, L.pairs_b, total, radix_key_bits(n_items + 1), L.temp, s) != hipSuccess) {
+  const SrcStepIds src{a.pos_ids, a.neg_ids, a.n_items, a.num_neg, a.num_neg + has_pos, has_pos};
+  if (radix_sort_pairs(src, L.pairs_a, L.pairs_b, total, radix_key_bits(a.n_items + 1), L.temp, s) != hipSuccess) {
     rsa::set_error("%s: radix sort failed: %s", who, hipGetErrorString(hipGetLastError()));
     return RSA_ERR_HIP;
   }
-  if (solo != nullptr) return classify_solo(step_sorted(L, n_items), total, pad_row, n_items, solo, s, who);
+  if (solo != nullptr) return classify_solo(step_sorted(L, a.n_items), total, a.pad_row, a.n_items, solo, s, who);
   return RSA_OK;
-}
-
-// the apply + finish passes over the sorted pairs in the workspace
-static int apply_sorted_impl(const float* query, const int64_t* query_index, int64_t n_query_rows, int32_t dim, int has_pos,
-                             int64_t n_queries, int32_t num_neg, const float* dpos, const float* dneg, const float* upstream,
-                             int64_t n_items, int64_t pad_row, float* target, AdamArgs adam, void* workspace,
-                             int64_t workspace_bytes, rsa_stream_t stream) {
-  RSA_CHECK_ARG(n_queries >= 0 && num_neg >= 1 && n_items >= 1 && n_items < (1ll << 31), "rsa_rows_update_sorted: bad sizes");
-  if (n_queries == 0) return RSA_OK;
-  RSA_CHECK_ARG(query && dneg && target, "rsa_rows_update_sorted: null pointer");
-  RSA_CHECK_ARG(!has_pos || dpos != nullptr, "rsa_rows_update_sorted: pos_ids without dpos");
-  RSA_CHECK_ARG(query_index != nullptr || n_query_rows >= n_queries, "rsa_rows_update_sorted: query has fewer rows than n_queries");
-  const int64_t total = n_queries * (int64_t)(num_neg + has_pos);
-  const int64_t need = rsa_scatter_rows_sorted_workspace_bytes(n_queries, num_neg, n_items);
-  RSA_CHECK_ARG(workspace && workspace_bytes >= need, "rsa_rows_update_sorted: workspace too small (%lld < %lld)",
-                (long long)workspace_bytes, (long long)need);
-  const SortedLayout L = sorted_layout(workspace, n_queries * (int64_t)(num_neg + 1));
-  const DecStep dec{query_index, dpos, dneg, (int)num_neg, has_pos};
-  return apply_sorted_pairs(step_sorted(L, n_items), total, query, dim, dec, upstream, n_items, pad_row, target, adam, L,
-                            (hipStream_t)stream);
-}
-
-static int scatter_sorted_impl(const float* query, const int64_t* query_index, int64_t n_query_rows, int32_t dim,
-                               const int64_t* pos_ids, const int64_t* neg_ids, int64_t n_queries, int32_t num_neg,
-                               const float* dpos, const float* dneg, const float* upstream, int64_t n_items,
-                               int64_t pad_row, float* target, AdamArgs adam, void* workspace, int64_t workspace_bytes,
-                               rsa_stream_t stream) {
-  RSA_CHECK_ARG(pos_ids == nullptr || dpos != nullptr, "rsa_rows_update_sorted: pos_ids without dpos");
-  if (dim != 64 && dim != 128 && dim != 256) {
-    rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", dim);
-    return RSA_ERR_UNSUPPORTED;
-  }
-  int rc = sort_elements_impl(pos_ids, neg_ids, n_queries, num_neg, n_items, pad_row, nullptr, workspace, workspace_bytes, stream,
-                              "rsa_rows_update_sorted");
-  if (rc != RSA_OK) return rc;
-  return apply_sorted_impl(query, query_index, n_query_rows, dim, pos_ids != nullptr, n_queries, num_neg, dpos, dneg, upstream,
-                           n_items, pad_row, target, adam, workspace, workspace_bytes, stream);
 }
 
 // The caller's hyper-parameters arrive as doubles (ABI 12): 1 - beta and the bias corrections are taken from THOSE values, as
@@ -555,25 +506,45 @@ static int check_adam(const rsa_rows_update_args& a, const char* who) {
   return RSA_OK;
 }
 
+// the apply + finish passes over the sorted pairs in the workspace
+static int apply_step_elements(const rsa_rows_update_args& a, int has_pos, hipStream_t s) {
+  RSA_CHECK_ARG(a.n_queries >= 0 && a.num_neg >= 1 && a.n_items >= 1 && a.n_items < (1ll << 31), "rsa_rows_update_sorted: bad sizes");
+  if (a.n_queries == 0) return RSA_OK;
+  RSA_CHECK_ARG(a.query && a.dneg && a.target, "rsa_rows_update_sorted: null pointer");
+  RSA_CHECK_ARG(!has_pos || a.dpos != nullptr, "rsa_rows_update_sorted: pos_ids without dpos");
+  RSA_CHECK_ARG(a.query_index != nullptr || a.n_query_rows >= a.n_queries, "rsa_rows_update_sorted: query has fewer rows than n_queries");
+  const int64_t total = a.n_queries * (int64_t)(a.num_neg + has_pos);
+  const int64_t need = rsa_scatter_rows_sorted_workspace_bytes(a.n_queries, a.num_neg, a.n_items);
+  RSA_CHECK_ARG(a.workspace && a.workspace_bytes >= need, "rsa_rows_update_sorted: workspace too small (%lld < %lld)",
+                (long long)a.workspace_bytes, (long long)need);
+  const SortedLayout L = sorted_layout(a.workspace, a.n_queries * (int64_t)(a.num_neg + 1));
+  const DecStep dec{a.query_index, a.dpos, a.dneg, (int)a.num_neg, has_pos};
+  return apply_sorted_pairs(step_sorted(L, a.n_items), total, a.query, a.dim, dec, a.upstream, a.n_items, a.pad_row, a.target,
+                            adam_of(a), L, s);
+}
+
 extern "C" int rsa_sort_step_elements(const rsa_rows_update_args* args, rsa_stream_t stream) {
   rsa_rows_update_args a;
   if (int rc = load_args(a, args, "rsa_sort_step_elements")) return rc;
-  return sort_elements_impl(a.pos_ids, a.neg_ids, a.n_queries, a.num_neg, a.n_items, a.pad_row, a.solo, a.workspace,
-                            a.workspace_bytes, stream, "rsa_sort_step_elements");
+  return sort_step_elements(a, a.solo, (hipStream_t)stream, "rsa_sort_step_elements");
 }
 
 extern "C" int rsa_rows_update_presorted(const rsa_rows_update_args* args, rsa_stream_t stream) {
   rsa_rows_update_args a;
   if (int rc = load_args(a, args, "rsa_rows_update_presorted")) return rc;
   if (int rc = check_adam(a, "rsa_rows_update_presorted")) return rc;
-  return apply_sorted_impl(a.query, a.query_index, a.n_query_rows, a.dim, a.has_pos != 0, a.n_queries, a.num_neg, a.dpos, a.dneg,
-                           a.upstream, a.n_items, a.pad_row, a.target, adam_of(a), a.workspace, a.workspace_bytes, stream);
+  return apply_step_elements(a, a.has_pos != 0, (hipStream_t)stream);
 }
 
 extern "C" int rsa_rows_update_sorted(const rsa_rows_update_args* args, rsa_stream_t stream) {
   rsa_rows_update_args a;
   if (int rc = load_args(a, args, "rsa_rows_update_sorted")) return rc;
   if (int rc = check_adam(a, "rsa_rows_update_sorted")) return rc;
-  return scatter_sorted_impl(a.query, a.query_index, a.n_query_rows, a.dim, a.pos_ids, a.neg_ids, a.n_queries, a.num_neg, a.dpos,
-                             a.dneg, a.upstream, a.n_items, a.pad_row, a.target, adam_of(a), a.workspace, a.workspace_bytes, stream);
+  RSA_CHECK_ARG(a.pos_ids == nullptr || a.dpos != nullptr, "rsa_rows_update_sorted: pos_ids without dpos");
+  if (a.dim != 64 && a.dim != 128 && a.dim != 256) {      // before the sort is issued
+    rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", a.dim);
+    return RSA_ERR_UNSUPPORTED;
+  }
+  if (int rc = sort_step_elements(a, nullptr, (hipStream_t)stream, "rsa_rows_update_sorted")) return rc;
+  return apply_step_elements(a, a.pos_ids != nullptr, (hipStream_t)stream);
 }

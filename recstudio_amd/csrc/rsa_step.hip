@@ -73,9 +73,15 @@ extern "C" int rsa_bpr_sgd_prepare(const rsa_bpr_sgd_args* args, rsa_stream_t st
       draw.lines_log2 = p.lines_log2;
       draw.table = p.table;
       draw.pop_prob = p.pop_prob;
-    } else if (int rc = sample_popular_impl(p.table, p.pop_prob, p.guide, p.n_items, p.guide_log2, a.neg_ids, nullptr, nullptr, numel,
-                                            a.seed, a.offset, a.grid_threads, a.elem_base, p.cdf_lut, p.cdf_lines, p.lines_log2, stream)) {
-      return rc;
+    } else {      // the step's tables, the step's outputs and generator state
+      p.ids = a.neg_ids;
+      p.logp = p.u_out = nullptr;
+      p.numel = numel;
+      p.seed = a.seed;
+      p.offset = a.offset;
+      p.grid_threads = a.grid_threads;
+      p.elem_base = a.elem_base;
+      if (int rc = sample_popular(p, stream)) return rc;
     }
   } else if (a.sampler != RSA_SAMPLER_GIVEN) {
     rsa::set_error("rsa_bpr_sgd_prepare: sampler must be RSA_SAMPLER_GIVEN, RSA_SAMPLER_UNIFORM or RSA_SAMPLER_POPULAR");
