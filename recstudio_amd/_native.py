@@ -304,6 +304,14 @@ def check(rc, what):
         raise NativeError(f'{what} failed (status {rc}): {msg.decode() if msg else ""}')
 
 
+def launch(name, stream, *args):
+    """One-shot call of the stream-taking entry point ``name`` (the stream is its last argument); a non-zero status raises
+    NativeError carrying that name.  Frozen hot paths (a bound function and a byref kept across steps) do not come through here."""
+    rc = getattr(lib(), name)(*args, stream)
+    if rc != RSA_OK:
+        check(rc, name)
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else c_void_p(t.data_ptr())

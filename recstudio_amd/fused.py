@@ -15,16 +15,20 @@ import torch
 from . import _native as nat
 from . import ops, rng
 from ._native import ptr
-from .sampler import PopularSamplerModel, Sampler, UniformSampler
+from .sampler import sampler_kind
 
 
-def _sampler_kind(sampler):
-    # exact types only: a subclass may override forward, and must then go through the plugin path
-    if type(sampler) is UniformSampler:
-        return nat.SAMPLER_UNIFORM
-    if type(sampler) is PopularSamplerModel:
-        return nat.SAMPLER_POPULAR
-    return None
+def _sampler_cfg(sampler, neg_ids, M):
+    """(rsa_sampler_kind, the ``ops.fused_forward`` keywords that go with it) of a step over M queries: ``neg_ids`` as [M, n] when no
+    sampler is given, the tables of the popularity sampler, nothing for the uniform one."""
+    kind = sampler_kind(sampler) if sampler is not None else nat.SAMPLER_GIVEN
+    if kind is None:
+        raise TypeError(f'fused path does not cover sampler {type(sampler).__name__}')
+    if kind == nat.SAMPLER_GIVEN:
+        if neg_ids is None:
+            raise ValueError('neg_ids is required when no sampler is given')
+        return kind, {'neg_ids': neg_ids.reshape(M, -1)}
+    return kind, (sampler.lookup_kwargs() if kind == nat.SAMPLER_POPULAR else {})
 
 
 _POP_KEYS = ('table', 'pop_prob', 'guide', 'guide_log2', 'table_prob', 'cdf_lut', 'cdf_lines', 'lines_log2')
@@ -114,16 +118,8 @@ def retriever_scores(item_weight, query_src, num_neg, *, query_index=None, pos_i
     M = query_index.numel() if query_index is not None else query_src.shape[0]
     cfg = {'num_neg': int(num_neg), 'query_index': query_index, 'pos_ids': pos_ids, 'cosine': cosine,
            'mask_pad_pos': mask_pad_pos, 'sparse_grad': sparse_grad, 'n_queries': M}
-    kind = _sampler_kind(sampler) if sampler is not None else nat.SAMPLER_GIVEN
-    if kind is None:
-        raise TypeError(f'fused path does not cover sampler {type(sampler).__name__}')
-    cfg['sampler'] = kind
-    if kind == nat.SAMPLER_GIVEN:
-        if neg_ids is None:
-            raise ValueError('neg_ids is required when no sampler is given')
-        cfg['neg_ids'] = neg_ids.reshape(M, -1)
-    elif kind == nat.SAMPLER_POPULAR:
-        cfg.update(sampler.lookup_kwargs())
+    kind, kw = _sampler_cfg(sampler, neg_ids, M)
+    cfg.update(kw, sampler=kind)
     pos_score, neg_score = _ScoreFn.apply(item_weight, query_src, cfg)
     out = cfg['out']
     score = {'pos_score': pos_score if pos_ids is not None else None, 'neg_score': neg_score}
@@ -218,14 +214,8 @@ def fused_bpr_loss(item_weight, query_src, num_neg, *, query_index=None, pos_ids
     M = query_index.numel() if query_index is not None else query_src.shape[0]
     cfg = {'num_neg': int(num_neg), 'query_index': query_index, 'pos_ids': pos_ids, 'sparse_grad': sparse_grad,
            'n_queries': M, 'loss': loss, 'pos_logp': pos_logp, 'neg_logp': neg_logp}
-    kind = _sampler_kind(sampler) if sampler is not None else nat.SAMPLER_GIVEN
-    if kind is None:
-        raise TypeError(f'fused path does not cover sampler {type(sampler).__name__}')
-    cfg['sampler'] = kind
-    if kind == nat.SAMPLER_GIVEN:
-        cfg['neg_ids'] = neg_ids.reshape(M, -1)
-    elif kind == nat.SAMPLER_POPULAR:
-        cfg.update(sampler.lookup_kwargs())
+    kind, kw = _sampler_cfg(sampler, neg_ids, M)
+    cfg.update(kw, sampler=kind)
     loss = _FusedBPRFn.apply(item_weight, query_src, cfg)
     return loss, cfg['out']['neg_ids']
 
@@ -266,14 +256,7 @@ def bpr_sgd_step(item_weight, user_weight, num_neg, lr, *, user_ids, pos_ids, sa
     through the apply pass (``rsa_rows_update_presorted``).  Same result as the all-sorted
     form bit for bit on the solo rows, equal up to fp32 summation order on the shared ones; bit-reproducible."""
     M = user_ids.numel()
-    kind = _sampler_kind(sampler) if sampler is not None else nat.SAMPLER_GIVEN
-    if kind is None:
-        raise TypeError(f'fused path does not cover sampler {type(sampler).__name__}')
-    kw = {}
-    if kind == nat.SAMPLER_GIVEN:
-        kw['neg_ids'] = neg_ids.reshape(M, -1)
-    elif kind == nat.SAMPLER_POPULAR:
-        kw.update(sampler.lookup_kwargs())
+    kind, kw = _sampler_cfg(sampler, neg_ids, M)
     if in_forward is None:
         in_forward = num_neg == 64 and item_weight.shape[1] in (64, 128, 256) and not atomics
     if in_forward:
@@ -311,11 +294,12 @@ def _sgd_step_block(iw, uw, num_neg, M, kind, sampler, step_scale, neg=None):
     """The buffers and the frozen ``rsa_bpr_sgd_args`` block of an in-place SGD step of M queries: ONE allocation (``ops.carve``)
     for what the two calls write, the item-AND-user sort workspace (ABI 11), the block filled but for the batch pointers and the
     Philox state."""
-    lib, dev, n, d = nat.lib(), iw.device, int(num_neg), iw.shape[1]
+    dev, n, d = iw.device, int(num_neg), iw.shape[1]
     N, U = iw.shape[0], uw.shape[0]
-    ws = int(lib.rsa_scatter_rows_sorted_workspace_bytes(M, n + 1, N))       # M * (n + 2) elements: items, positives, users
+    # (M * (n + 2) elements: items, positives, users)
+    ws, ws_alloc = ops._workspace_bytes('rsa_scatter_rows_sorted_workspace_bytes', M, n + 1, N)
     f32, u8 = torch.float32, torch.uint8
-    specs = [('solo', (M, n + 1), u8), ('iws', (max(ws, 8),), u8), ('pos_score', (M,), f32), ('neg_score', (M, n), f32),
+    specs = [('solo', (M, n + 1), u8), ('iws', (ws_alloc,), u8), ('pos_score', (M,), f32), ('neg_score', (M, n), f32),
              ('row_loss', (M,), f32), ('dpos', (M,), f32), ('dneg', (M, n), f32), ('query_grad', (M, d), f32)]
     if neg is None:
         specs.insert(0, ('neg', (M, n), torch.int64))
@@ -338,9 +322,27 @@ def _sgd_step_block(iw, uw, num_neg, M, kind, sampler, step_scale, neg=None):
 
 def _reserve_draw(a, kind, sampler, M, num_neg, dev):
     """the Philox state the Sampler plugin's call would consume for this step's negatives -> the argument block"""
-    unroll = 4 if kind == nat.SAMPLER_POPULAR else rng.randint_unroll(1, int(sampler.num_items) + 1)
-    pc = rng.reserve(M * num_neg, unroll, dev, None)
+    pc = rng.reserve(M * num_neg, rng.sampler_unroll(kind, int(sampler.num_items) + 1), dev, None)
     a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
+
+
+def _popular_block(sampler):
+    """(``rsa_popular_args`` over the popularity sampler's tables -- all but the interleaved ``table_prob`` copy, which that block
+    does not carry --, the tensors it points to)"""
+    kw = sampler.lookup_kwargs()
+    kw.pop('table_prob', None)
+    return ops.popular_args(**kw), kw
+
+
+def _check_tables(who, iw, uw):
+    if not (iw.is_cuda and iw.is_contiguous() and uw.is_contiguous() and uw.device == iw.device and iw.dtype == uw.dtype == torch.float32):
+        raise RuntimeError(f'{who}: contiguous fp32 tables on one GPU (there is no CPU fallback)')
+
+
+def _ids_ok(user_ids, pos_ids, dev):
+    """int64 user / positive ids on ``dev``, one positive per query"""
+    return (user_ids.is_cuda and user_ids.dtype == pos_ids.dtype == torch.int64 and user_ids.device == dev
+            and pos_ids.numel() == user_ids.numel())
 
 
 def _bpr_sgd_step_in_forward(item_weight, user_weight, num_neg, lr, user_ids, pos_ids, sampler, kind, kw):
@@ -350,9 +352,8 @@ def _bpr_sgd_step_in_forward(item_weight, user_weight, num_neg, lr, user_ids, po
     M = user_ids.numel()
     iw, uw = item_weight.data, user_weight.data
     dev = iw.device
-    if not (iw.is_cuda and iw.is_contiguous() and uw.is_contiguous() and uw.device == dev and iw.dtype == uw.dtype == torch.float32):
-        raise RuntimeError('bpr_sgd_step: contiguous fp32 tables on one GPU (there is no CPU fallback)')
-    if not (user_ids.is_cuda and user_ids.dtype == pos_ids.dtype == torch.int64 and user_ids.device == dev and pos_ids.numel() == M):
+    _check_tables('bpr_sgd_step', iw, uw)
+    if not _ids_ok(user_ids, pos_ids, dev):
         raise TypeError('bpr_sgd_step: int64 user / positive ids on the tables\' device, one positive per query')
     user_ids, pos_ids = user_ids.contiguous(), pos_ids.contiguous()
     neg = None
@@ -366,9 +367,7 @@ def _bpr_sgd_step_in_forward(item_weight, user_weight, num_neg, lr, user_ids, po
         b = _sgd_step_block(iw, uw, num_neg, M, kind, sampler, step, neg=neg)
         a = b['args']
         if kind == nat.SAMPLER_POPULAR:
-            pk = sampler.lookup_kwargs()
-            pk.pop('table_prob', None)
-            pop = ops.popular_args(**pk)
+            pop, _ = _popular_block(sampler)
             a.pop = ctypes.pointer(pop)
         a.user_ids, a.pos_ids = user_ids.data_ptr(), pos_ids.data_ptr()
         if kind != nat.SAMPLER_GIVEN:
@@ -410,12 +409,10 @@ class PrefetchedBPRSGD:
         self.iw, self.uw = item_weight.data, user_weight.data
         if not (num_neg == 64 and self.iw.shape[1] in (64, 128, 256)):
             raise NotImplementedError('PrefetchedBPRSGD: num_neg == 64 and embed_dim in {64, 128, 256} (the in-forward update)')
-        self.kind = _sampler_kind(sampler)
+        self.kind = sampler_kind(sampler)
         if self.kind not in (nat.SAMPLER_UNIFORM, nat.SAMPLER_POPULAR):
             raise TypeError(f'PrefetchedBPRSGD does not cover sampler {type(sampler).__name__}')
-        if not (self.iw.is_cuda and self.iw.is_contiguous() and self.uw.is_contiguous() and self.uw.device == self.iw.device
-                and self.iw.dtype == self.uw.dtype == torch.float32):
-            raise RuntimeError('PrefetchedBPRSGD: contiguous fp32 tables on one GPU (there is no CPU fallback)')
+        _check_tables('PrefetchedBPRSGD', self.iw, self.uw)
         self.num_neg, self.sampler, self.dev = int(num_neg), sampler, self.iw.device
         self.side = torch.cuda.Stream(device=self.dev)
         self.step_scale = torch.full((1,), -float(lr), dtype=torch.float32, device=self.dev)
@@ -432,10 +429,7 @@ class PrefetchedBPRSGD:
     def _popular_tables(self):
         src = self.sampler._buffers.get('table')
         if self._pop is None or src is not self._pop_src:        # (re)built tables after load_state_dict / .to()
-            kw = self.sampler.lookup_kwargs()
-            kw.pop('table_prob', None)
-            self._pop = ops.popular_args(**kw)
-            self._pop_keep = kw
+            self._pop, self._pop_keep = _popular_block(self.sampler)
             self._pop_src = src
             for slots in self._slots.values():
                 for sl in slots:
@@ -457,8 +451,7 @@ class PrefetchedBPRSGD:
 
     def prepare(self, user_ids, pos_ids):
         """Issue the weight-independent part of a step (negatives, sorts, classification) on the side stream -> ticket."""
-        if not (user_ids.is_cuda and user_ids.dtype == pos_ids.dtype == torch.int64 and user_ids.is_contiguous()
-                and pos_ids.is_contiguous() and user_ids.numel() == pos_ids.numel() and user_ids.device == self.dev):
+        if not (_ids_ok(user_ids, pos_ids, self.dev) and user_ids.is_contiguous() and pos_ids.is_contiguous()):
             raise TypeError('PrefetchedBPRSGD.prepare: contiguous int64 user / positive ids on the tables\' device')
         M = user_ids.numel()
         if self.kind == nat.SAMPLER_POPULAR:
@@ -535,14 +528,7 @@ class FusedBPRAdam:
     def step(self, num_neg, *, user_ids, pos_ids, sampler=None, neg_ids=None):
         """One step; returns (loss, neg_ids).  num_neg % 64 == 0."""
         M = user_ids.numel()
-        kind = _sampler_kind(sampler) if sampler is not None else nat.SAMPLER_GIVEN
-        if kind is None:
-            raise TypeError(f'fused path does not cover sampler {type(sampler).__name__}')
-        kw = {}
-        if kind == nat.SAMPLER_GIVEN:
-            kw['neg_ids'] = neg_ids.reshape(M, -1)
-        elif kind == nat.SAMPLER_POPULAR:
-            kw.update(sampler.lookup_kwargs())
+        kind, kw = _sampler_cfg(sampler, neg_ids, M)
         self.t += 1
         st = self.state
         with torch.no_grad():
@@ -561,7 +547,7 @@ class FusedBPRAdam:
         """Draw the negatives of a batch and sort its (item id, element) pairs on a side stream -> ticket for
         ``step_prepared``.  Tickets are stepped once each, in the order they were prepared; the results are those of the
         same sequence of ``step`` calls bit for bit."""
-        if _sampler_kind(sampler) not in (nat.SAMPLER_UNIFORM, nat.SAMPLER_POPULAR):
+        if sampler_kind(sampler) not in (nat.SAMPLER_UNIFORM, nat.SAMPLER_POPULAR):
             raise TypeError(f'FusedBPRAdam.prepare does not cover sampler {type(sampler).__name__}')
         if getattr(self, 'side', None) is None:
             self.side = torch.cuda.Stream(device=self.iw.device)

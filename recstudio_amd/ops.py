@@ -23,13 +23,7 @@ _ZERO_LOGP = {}
 
 def zero_logp_like(ids):
     """An int64 all-zero tensor shaped like ``ids`` (a view of a cached constant buffer)."""
-    key = (ids.numel(), ids.device)
-    z = _ZERO_LOGP.get(key)
-    if z is None:
-        if len(_ZERO_LOGP) >= 16:              # a handful of batch shapes at most; do not grow without bound
-            _ZERO_LOGP.clear()
-        z = _ZERO_LOGP[key] = torch.zeros(ids.numel(), dtype=torch.int64, device=ids.device)
-    return z.view(ids.shape)
+    return zero_logp(ids.shape, ids.device)
 
 
 def zero_logp(shape, device):
@@ -44,7 +38,7 @@ def zero_logp(shape, device):
     key = (numel, device)
     z = _ZERO_LOGP.get(key)
     if z is None:
-        if len(_ZERO_LOGP) >= 16:
+        if len(_ZERO_LOGP) >= 16:              # a handful of batch shapes at most; do not grow without bound
             _ZERO_LOGP.clear()
         z = _ZERO_LOGP[key] = torch.zeros(numel, dtype=torch.int64, device=device)
     return z.view(shape)
@@ -73,6 +67,11 @@ def _raw_stream(dev=None):
 
 def _stream():
     return ctypes.c_void_p(_raw_stream(_LAUNCH_DEV[-1] if _LAUNCH_DEV else None))
+
+
+def _launch(name, *args):
+    """``nat.launch`` on the current stream of the launch device: every one-shot native call of ops.py and shard.py."""
+    nat.launch(name, _stream(), *args)
 
 
 def _tensor_device(args, kwargs):
@@ -148,6 +147,24 @@ def _need_opt(t, dtype, name):
     return None if t is None else _need(t, dtype, name)
 
 
+def _workspace_bytes(sizer, *dims):
+    """(what the size query ``sizer`` returns for ``dims`` -- the ``workspace_bytes`` the library is told --, the bytes to set
+    aside for it: never an empty buffer).  Callers that carve the workspace out of an arena use this directly."""
+    nbytes = int(getattr(nat.lib(), sizer)(*dims))
+    return nbytes, max(nbytes, 8)
+
+
+def _workspace(dev, sizer, *dims):
+    """(uint8 workspace tensor on ``dev``, workspace_bytes) for the size query ``sizer``."""
+    nbytes, alloc = _workspace_bytes(sizer, *dims)
+    return torch.empty(alloc, dtype=torch.uint8, device=dev), nbytes
+
+
+def _score_mode(cosine):
+    """rsa_score_mode from the wrappers' ``cosine`` argument: a bool (inner product / cosine) or the mode itself."""
+    return int(cosine) if not isinstance(cosine, bool) else (nat.SCORE_COS if cosine else nat.SCORE_IP)
+
+
 # ------------------------------------------------------------------ samplers
 @_on_device
 def sample_uniform(numel, low, high, device, generator=None):
@@ -156,8 +173,7 @@ def sample_uniform(numel, low, high, device, generator=None):
     if numel == 0:
         return out
     pc = rng.reserve(numel, rng.randint_unroll(low, high), device, generator)
-    nat.check(nat.lib().rsa_sample_uniform(ptr(out), int(numel), int(low), int(high), pc.seed, pc.offset,
-                                           pc.grid_threads, pc.elem_base, _stream()), 'rsa_sample_uniform')
+    _launch('rsa_sample_uniform', ptr(out), int(numel), int(low), int(high), pc.seed, pc.offset, pc.grid_threads, pc.elem_base)
     return out
 
 
@@ -169,9 +185,8 @@ def sample_masked_uniform(user_hist, num_items, per_row, generator=None):
     out = torch.empty(B, int(per_row), dtype=torch.int64, device=user_hist.device)
     if B * per_row:
         pc = rng.reserve(B * per_row, 4, user_hist.device, generator)
-        nat.check(nat.lib().rsa_sample_masked_uniform(ptr(user_hist), B, Lh, int(num_items), int(per_row), ptr(out),
-                                                      pc.seed, pc.offset, pc.grid_threads, pc.elem_base, _stream()),
-                  'rsa_sample_masked_uniform')
+        _launch('rsa_sample_masked_uniform', ptr(user_hist), B, Lh, int(num_items), int(per_row), ptr(out),
+                pc.seed, pc.offset, pc.grid_threads, pc.elem_base)
     return out
 
 
@@ -200,7 +215,7 @@ def sample_popular(table, pop_prob, guide, guide_log2, numel, generator=None, wa
         a = popular_args(table, pop_prob, guide, guide_log2, cdf_lut, cdf_lines, lines_log2)
         a.ids, a.logp, a.u_out, a.numel = ptr(ids), ptr(logp), ptr(u), int(numel)
         a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
-        nat.check(nat.lib().rsa_sample_popular(ctypes.byref(a), _stream()), 'rsa_sample_popular')
+        _launch('rsa_sample_popular', ctypes.byref(a))
     return (ids, logp, u) if want_u else (ids, logp)
 
 
@@ -214,7 +229,7 @@ def popular_lookup(table, pop_prob, guide, guide_log2, u, cdf_lut=None, cdf_line
     logp = torch.empty(u.numel(), dtype=torch.float32, device=u.device)
     a = popular_args(table, pop_prob, guide, guide_log2, cdf_lut, cdf_lines, lines_log2)
     a.u_in, a.ids, a.logp, a.numel = ptr(u), ptr(ids), ptr(logp), u.numel()
-    nat.check(nat.lib().rsa_popular_lookup(ctypes.byref(a), _stream()), 'rsa_popular_lookup')
+    _launch('rsa_popular_lookup', ctypes.byref(a))
     return ids.view(u.shape), logp.view(u.shape)
 
 
@@ -223,8 +238,7 @@ def item_logp(pop_prob, ids):
     pop_prob = _need(pop_prob, torch.float32, 'pop_prob')
     ids = _need(ids, torch.int64, 'ids')
     out = torch.empty(ids.shape, dtype=torch.float32, device=ids.device)
-    nat.check(nat.lib().rsa_item_logp(ptr(pop_prob), pop_prob.numel(), ptr(ids), ids.numel(), ptr(out), _stream()),
-              'rsa_item_logp')
+    _launch('rsa_item_logp', ptr(pop_prob), pop_prob.numel(), ptr(ids), ids.numel(), ptr(out))
     return out
 
 
@@ -235,8 +249,7 @@ def embedding_gather(table, ids):
     ids = _need(ids, torch.int64, 'ids')
     n_rows, dim = table.shape
     out = torch.empty(*ids.shape, dim, dtype=torch.float32, device=table.device)
-    nat.check(nat.lib().rsa_embedding_gather(ptr(table), n_rows, dim, ptr(ids), ids.numel(), ptr(out), _stream()),
-              'rsa_embedding_gather')
+    _launch('rsa_embedding_gather', ptr(table), n_rows, dim, ptr(ids), ids.numel(), ptr(out))
     return out
 
 
@@ -249,8 +262,7 @@ def scatter_add_rows(src, ids, n_rows, out=None):
     dim = src.shape[-1]
     dst = _need(out, torch.float32, 'out') if out is not None else torch.zeros(n_rows, dim, dtype=torch.float32,
                                                                                 device=src.device)
-    nat.check(nat.lib().rsa_scatter_add_rows(ptr(src), ptr(ids), ids.numel(), dim, ptr(dst), n_rows, _stream()),
-              'rsa_scatter_add_rows')
+    _launch('rsa_scatter_add_rows', ptr(src), ptr(ids), ids.numel(), dim, ptr(dst), n_rows)
     return dst
 
 
@@ -271,16 +283,8 @@ def seg_gather(item_table, flat_item_ids, seg_start, seg_end, max_len, want_rows
     a.item_table, a.n_items, a.dim, a.max_len = ptr(tab), n_items, dim, int(max_len)
     a.flat_item_ids, a.n_flat, a.seg_start, a.seg_end, a.n_seg = ptr(flat), flat.numel(), ptr(s), ptr(e), B
     a.out_ids, a.out_rows, a.out_len = ptr(ids), ptr(rows), ptr(lens)
-    nat.check(nat.lib().rsa_seg_gather(ctypes.byref(a), _stream()), 'rsa_seg_gather')
+    _launch('rsa_seg_gather', ctypes.byref(a))
     return ids, rows, lens
-
-
-def _loss_args(kind, pos_score, neg_score, pos_logp, neg_logp, n_rows, num_neg, row_loss, loss_out, dpos, dneg):
-    a = nat.LossArgs()
-    a.loss_kind, a.n_rows, a.num_neg = int(kind), int(n_rows), int(num_neg)
-    a.pos_score, a.neg_score, a.pos_logp, a.neg_logp = ptr(pos_score), ptr(neg_score), ptr(pos_logp), ptr(neg_logp)
-    a.row_loss, a.loss_out, a.dpos, a.dneg, a.scratch = ptr(row_loss), ptr(loss_out), ptr(dpos), ptr(dneg), ptr(_scratch())
-    return a
 
 
 def carve(dev, specs, align=4096):
@@ -348,13 +352,14 @@ def fused_forward(item_table, query, num_neg, *, query_index=None, pos_ids=None,
     if pos_ids is not None and pos_ids.numel() != M:
         raise ValueError('pos_ids must have one id per query')
     a = nat.FusedArgs()
+    # (None: the launch does not consume the torch generator -- nothing for ``FusedStep`` to reserve per step)
+    unroll = None if sampler == nat.SAMPLER_GIVEN or rng_state is not None else rng.sampler_unroll(sampler, n_items)
     if sampler == nat.SAMPLER_GIVEN:
         neg_ids = _need(neg_ids, torch.int64, 'neg_ids')
         if neg_ids.numel() != M * n:
             raise ValueError('neg_ids must be [M, num_neg]')
     else:
         neg_ids = out['neg_ids'] if out is not None else None          # (allocated with the other outputs below)
-        unroll = 4 if sampler == nat.SAMPLER_POPULAR else rng.randint_unroll(1, n_items)
         if rng_state is not None:
             # graph-capturable form: (seed, device int64 tensor holding the offset); the caller advances it
             # (rsa_rng_advance) and mirrors the consumption into the torch generator afterwards
@@ -378,12 +383,21 @@ def fused_forward(item_table, query, num_neg, *, query_index=None, pos_ids=None,
     reuse = out is not None        # caller-provided output buffers (same keys/shapes as returned)
     if fused_loss is None and fused_bpr:
         fused_loss = 'bpr'
-    score_mode = int(cosine) if not isinstance(cosine, bool) else (nat.SCORE_COS if cosine else nat.SCORE_IP)
+    score_mode = _score_mode(cosine)
     composed = fused_loss == 'bpr' and n != 64 and (dim not in (32, 64, 128, 256) or score_mode != nat.SCORE_IP)
     keep_scores = want_scores or fused_loss not in ('bpr', 'ssm') or composed
-    if not reuse:
+    f32 = torch.float32
+    loss_specs = []
+    if fused_loss in ('bpr', 'ssm'):
+        loss_specs = [('dneg', (M, n), f32), ('loss', (), f32), ('row_loss', (M,), f32), ('dpos', (M,), f32)]
+        if want_query_grad:
+            loss_specs.append(('query_grad', (M, dim), f32))
+    if reuse:
+        missing = [spec for spec in loss_specs if spec[0] not in out]      # a dict of an earlier call without this loss
+        if missing:
+            out.update(carve(dev, missing))
+    else:
         # every output of the launch out of ONE allocation (carve): see there for why
-        f32 = torch.float32
         specs = [('neg_score', (M, n), f32)] if keep_scores else []
         if sampler != nat.SAMPLER_GIVEN:
             specs.insert(0, ('neg_ids', (M, n), torch.int64))
@@ -393,11 +407,7 @@ def fused_forward(item_table, query, num_neg, *, query_index=None, pos_ids=None,
             specs.append(('neg_logp', (M, n), f32))
             if pos_ids is not None:
                 specs.append(('pos_logp', (M,), f32))
-        if fused_loss in ('bpr', 'ssm'):
-            specs += [('dneg', (M, n), f32), ('loss', (), f32), ('row_loss', (M,), f32), ('dpos', (M,), f32)]
-            if want_query_grad:
-                specs.append(('query_grad', (M, dim), f32))
-        out = carve(dev, specs)
+        out = carve(dev, specs + loss_specs)
         if sampler != nat.SAMPLER_GIVEN:
             neg_ids = out['neg_ids']
     out['neg_ids'] = neg_ids.view(M, n)
@@ -429,25 +439,18 @@ def fused_forward(item_table, query, num_neg, *, query_index=None, pos_ids=None,
         if n_batches > 1:
             raise ValueError('fused_forward(n_batches=...) with a fused BPR loss needs num_neg == 64, or the inner-product scorer '
                              'and dim in {32, 64, 128, 256} (this configuration is composed of two launches)')
-        nat.check(nat.lib().rsa_fused_sample_gather_score(ctypes.byref(a), _stream()), 'rsa_fused_sample_gather_score')
+        _launch('rsa_fused_sample_gather_score', ctypes.byref(a))
         out['loss'], out['dpos'], out['dneg'], out['row_loss'] = pairwise_loss(nat.LOSS_BPR, out['pos_score'], out['neg_score'])
         return out
     if fused_loss is not None:
         if fused_loss not in ('bpr', 'ssm'):
             raise ValueError("fused_loss must be None, 'bpr' or 'ssm'")
-        if 'loss' not in out:
-            out['loss'] = torch.empty((), dtype=torch.float32, device=dev)
-            out['row_loss'] = torch.empty(M, dtype=torch.float32, device=dev)
-            out['dpos'] = torch.empty(M, dtype=torch.float32, device=dev)
-            out['dneg'] = torch.empty(M, n, dtype=torch.float32, device=dev)
         a.fused_loss = (nat.LOSS_BPR if fused_loss == 'bpr' else nat.LOSS_SSM) + 1
         a.row_loss, a.loss_out = ptr(out['row_loss']), ptr(out['loss'] if want_mean else None)
         if want_mean:
             a.reduce_scratch = ptr(_scratch())
         a.dpos, a.dneg = ptr(out['dpos']), ptr(out['dneg'])
         if want_query_grad:
-            if 'query_grad' not in out:
-                out['query_grad'] = torch.empty(M, dim, dtype=torch.float32, device=dev)
             a.query_grad = ptr(out['query_grad'])
         if inplace_update is not None:
             # (solo_flags, scale): rows touched by exactly one element of the step (sort_step_elements) are updated inside
@@ -458,14 +461,12 @@ def fused_forward(item_table, query, num_neg, *, query_index=None, pos_ids=None,
         raise ValueError('want_query_grad needs a fused loss (fused_bpr=True / fused_loss=...)')
     if n_batches > 1 and (sampler == nat.SAMPLER_GIVEN or rng_state is not None):
         raise ValueError('fused_forward(n_batches=...) draws its negatives in the kernel from the torch generator')
-    nat.check(nat.lib().rsa_fused_sample_gather_score(ctypes.byref(a), _stream()), 'rsa_fused_sample_gather_score')
+    _launch('rsa_fused_sample_gather_score', ctypes.byref(a))
     if n_batches > 1 and fused_loss is not None:
         _queue_losses(out, int(n_batches))
     if _plan is not None:
-        _plan.update(args=a, out=out, device=dev, generator=generator, numel=M * n, n_batches=int(n_batches), keep=(item_table, query, query_index, pos_ids,
-                                                                                         neg_ids, table, pop_prob, guide))
-        _plan['unroll'] = None if sampler == nat.SAMPLER_GIVEN or rng_state is not None else \
-            (4 if sampler == nat.SAMPLER_POPULAR else rng.randint_unroll(1, n_items))
+        _plan.update(args=a, out=out, device=dev, generator=generator, numel=M * n, n_batches=int(n_batches), unroll=unroll,
+                     keep=(item_table, query, query_index, pos_ids, neg_ids, table, pop_prob, guide))
     return out
 
 
@@ -526,71 +527,56 @@ def score_packed_keys(item_table, query, keys):
     a.query, a.n_query_rows = ptr(query), query.shape[0]
     a.n_queries, a.num_neg, a.sampler = m, 1, nat.SAMPLER_GIVEN
     a.packed_keys, a.neg_score = ptr(keys), ptr(out)
-    nat.check(nat.lib().rsa_fused_sample_gather_score(ctypes.byref(a), _stream()), 'rsa_fused_sample_gather_score')
+    _launch('rsa_fused_sample_gather_score', ctypes.byref(a))
     return out
+
+
+def _loss(who, kind, pos_score, neg_score, pos_logp, neg_logp, want_grad=True, shared=False, param0=0.0, param1=0.0):
+    """The one body of the loss wrappers -> (loss, dpos, dneg, row_loss).  ``shared``: rsa_ssm_shared_loss over pos_score [B, L]
+    and neg_score [B, n]; otherwise rsa_pairwise_loss over one positive and n negatives per row."""
+    pos_score = _need(pos_score, torch.float32, 'pos_score')
+    neg_score = _need(neg_score, torch.float32, 'neg_score')
+    if shared:
+        (M, n_pos), n = pos_score.shape, neg_score.shape[1]
+    else:
+        M, n_pos = pos_score.numel(), 0
+        n = neg_score.numel() // max(M, 1)
+        if neg_score.numel() != M * n or M == 0 or n == 0:
+            raise ValueError(f'{who}: pos {tuple(pos_score.shape)} vs neg {tuple(neg_score.shape)}')
+    pos_logp = _need_opt(pos_logp, torch.float32, 'pos_logp')
+    neg_logp = _need_opt(neg_logp, torch.float32, 'neg_logp')
+    dev = pos_score.device
+    row = torch.empty(M, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dpos = torch.empty_like(pos_score) if want_grad else None
+    dneg = torch.empty_like(neg_score) if want_grad else None
+    a = nat.LossArgs()
+    a.loss_kind, a.n_rows, a.num_neg, a.n_pos = int(kind), M, n, n_pos
+    a.pos_score, a.neg_score, a.pos_logp, a.neg_logp = ptr(pos_score), ptr(neg_score), ptr(pos_logp), ptr(neg_logp)
+    a.row_loss, a.loss_out, a.dpos, a.dneg, a.scratch = ptr(row), ptr(loss), ptr(dpos), ptr(dneg), ptr(_scratch())
+    a.param0, a.param1 = float(param0), float(param1)
+    _launch('rsa_ssm_shared_loss' if shared else 'rsa_pairwise_loss', ctypes.byref(a))
+    return loss, dpos, dneg, row
 
 
 @_on_device
 def pairwise_loss(kind, pos_score, neg_score, pos_logp=None, neg_logp=None, want_grad=True):
     """(loss [scalar tensor], dpos [M] | None, dneg [M,n] | None, row_loss [M])."""
-    pos_score = _need(pos_score, torch.float32, 'pos_score')
-    neg_score = _need(neg_score, torch.float32, 'neg_score')
-    M = pos_score.numel()
-    n = neg_score.numel() // max(M, 1)
-    if neg_score.numel() != M * n or M == 0 or n == 0:
-        raise ValueError(f'pairwise_loss: pos {tuple(pos_score.shape)} vs neg {tuple(neg_score.shape)}')
-    pos_logp = _need_opt(pos_logp, torch.float32, 'pos_logp')
-    neg_logp = _need_opt(neg_logp, torch.float32, 'neg_logp')
-    dev = pos_score.device
-    row = torch.empty(M, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    dpos = torch.empty(pos_score.shape, dtype=torch.float32, device=dev) if want_grad else None
-    dneg = torch.empty(neg_score.shape, dtype=torch.float32, device=dev) if want_grad else None
-    a = _loss_args(kind, pos_score, neg_score, pos_logp, neg_logp, M, n, row, loss, dpos, dneg)
-    nat.check(nat.lib().rsa_pairwise_loss(ctypes.byref(a), _stream()), 'rsa_pairwise_loss')
-    return loss, dpos, dneg, row
+    return _loss('pairwise_loss', kind, pos_score, neg_score, pos_logp, neg_logp, want_grad)
 
 
 @_on_device
 def pairwise_loss_ex(kind, pos_score, neg_score, pos_logp=None, neg_logp=None, param0=0.0, param1=0.0):
     """rsa_pairwise_loss, kinds WeightedBPR / WeightedBCE / Hinge / NCE / CCL: (loss, dpos, dneg)."""
-    pos_score = _need(pos_score, torch.float32, 'pos_score')
-    neg_score = _need(neg_score, torch.float32, 'neg_score')
-    M = pos_score.numel()
-    n = neg_score.numel() // max(M, 1)
-    if neg_score.numel() != M * n or M == 0 or n == 0:
-        raise ValueError(f'pairwise_loss_ex: pos {tuple(pos_score.shape)} vs neg {tuple(neg_score.shape)}')
-    pos_logp = _need_opt(pos_logp, torch.float32, 'pos_logp')
-    neg_logp = _need_opt(neg_logp, torch.float32, 'neg_logp')
-    dev = pos_score.device
-    row = torch.empty(M, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    dpos, dneg = torch.empty_like(pos_score), torch.empty_like(neg_score)
     if not nat.LOSS_WBPR <= int(kind) <= nat.LOSS_CCL:
         raise ValueError(f'pairwise_loss_ex: unknown loss kind {kind}')
-    a = _loss_args(kind, pos_score, neg_score, pos_logp, neg_logp, M, n, row, loss, dpos, dneg)
-    a.param0, a.param1 = float(param0), float(param1)
-    nat.check(nat.lib().rsa_pairwise_loss(ctypes.byref(a), _stream()), 'rsa_pairwise_loss')
-    return loss, dpos, dneg
+    return _loss('pairwise_loss_ex', kind, pos_score, neg_score, pos_logp, neg_logp, param0=param0, param1=param1)[:3]
 
 
 @_on_device
 def ssm_shared_loss(pos_score, neg_score, pos_logp=None, neg_logp=None):
     """rsa_ssm_shared_loss: pos_score [B, L], neg_score [B, n].  Returns (loss, dpos, dneg)."""
-    pos_score = _need(pos_score, torch.float32, 'pos_score')
-    neg_score = _need(neg_score, torch.float32, 'neg_score')
-    pos_logp = _need_opt(pos_logp, torch.float32, 'pos_logp')
-    neg_logp = _need_opt(neg_logp, torch.float32, 'neg_logp')
-    B, L = pos_score.shape
-    n = neg_score.shape[1]
-    dev = pos_score.device
-    row = torch.empty(B, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    dpos, dneg = torch.empty_like(pos_score), torch.empty_like(neg_score)
-    a = _loss_args(nat.LOSS_SSM, pos_score, neg_score, pos_logp, neg_logp, B, n, row, loss, dpos, dneg)
-    a.n_pos = L
-    nat.check(nat.lib().rsa_ssm_shared_loss(ctypes.byref(a), _stream()), 'rsa_ssm_shared_loss')
-    return loss, dpos, dneg
+    return _loss('ssm_shared_loss', nat.LOSS_SSM, pos_score, neg_score, pos_logp, neg_logp, shared=True)[:3]
 
 
 @_on_device
@@ -629,8 +615,8 @@ def fused_backward(item_table, query, neg_ids, dneg, *, query_index=None, pos_id
     a.query_table_grad = ptr(_need_opt(query_table_grad, torch.float32, 'query_table_grad'))
     a.query_table_pad_row = int(query_table_pad_row)
     a.item_pad_row = int(item_pad_row)
-    a.score_mode = int(cosine) if not isinstance(cosine, bool) else (nat.SCORE_COS if cosine else nat.SCORE_IP)
-    nat.check(nat.lib().rsa_fused_backward(ctypes.byref(a), _stream()), 'rsa_fused_backward')
+    a.score_mode = _score_mode(cosine)
+    _launch('rsa_fused_backward', ctypes.byref(a))
     return item_grad, rows, qgrad
 
 
@@ -661,14 +647,67 @@ def sort_step_elements(pos_ids, neg_ids, n_items, pad_row=0, want_solo=True):
     M = pos_ids.numel() if pos_ids is not None else neg_ids.shape[0]
     n = neg_ids.numel() // max(M, 1)
     w = n + (1 if pos_ids is not None else 0)
-    ws_bytes = int(nat.lib().rsa_scatter_rows_sorted_workspace_bytes(M, n, int(n_items)))
-    bufs = carve(neg_ids.device, [('ws', (max(ws_bytes, 8),), torch.uint8)] + ([('solo', (M, w), torch.uint8)] if want_solo else []))
+    ws_bytes, ws_alloc = _workspace_bytes('rsa_scatter_rows_sorted_workspace_bytes', M, n, int(n_items))
+    bufs = carve(neg_ids.device, [('ws', (ws_alloc,), torch.uint8)] + ([('solo', (M, w), torch.uint8)] if want_solo else []))
     solo, ws = bufs.get('solo'), bufs['ws']                     # solo None: sort only, nothing flagged
     a = nat.RowsUpdateArgs()
     a.pos_ids, a.neg_ids, a.n_queries, a.num_neg, a.n_items, a.pad_row = ptr(pos_ids), ptr(neg_ids), M, n, int(n_items), int(pad_row)
     a.solo, a.workspace, a.workspace_bytes = ptr(solo), ptr(ws), ws_bytes
-    nat.check(nat.lib().rsa_sort_step_elements(ctypes.byref(a), _stream()), 'rsa_sort_step_elements')
+    _launch('rsa_sort_step_elements', ctypes.byref(a))
     return solo, ws
+
+
+def _rows_update(who, target, query, dneg, *, neg_ids=None, workspace=None, n_queries=None, num_neg=None, adam=None,
+                 query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
+    """The one body of the rows-update wrappers.  No ``workspace``: sort + apply over ``neg_ids`` / ``pos_ids``
+    (rsa_rows_update_sorted; queries and negatives per query derived here, the workspace allocated here).  ``workspace`` given:
+    the apply pass over the pairs ``sort_step_elements`` left in it (rsa_rows_update_presorted).  ``adam``: (exp_avg, exp_avg_sq,
+    lr, betas, eps, step) of the lazy-Adam form."""
+    presorted = workspace is not None
+    target = _need(target, torch.float32, 'weight' if adam else 'target')
+    query = _need(query, torch.float32, 'query')
+    neg_ids = None if presorted else _need(neg_ids, torch.int64, 'neg_ids')
+    dneg = _need(dneg, torch.float32, 'dneg')
+    query_index = _need_opt(query_index, torch.int64, 'query_index')
+    pos_ids = _need_opt(pos_ids, torch.int64, 'pos_ids')
+    dpos = _need_opt(dpos, torch.float32, 'dpos')
+    upstream = _need_opt(upstream, torch.float32, 'upstream')
+    if presorted:
+        M, n = n_queries, num_neg
+    else:
+        M = query_index.numel() if query_index is not None else query.shape[0]
+        if M == 0:
+            return target
+        n = neg_ids.numel() // M
+    a = _rows_update_args(target, query, query_index, M, n, dpos, dneg, upstream, pad_row)
+    if adam:
+        _adam_fields(a, *adam, who)
+    if presorted:
+        a.has_pos, a.workspace_bytes = int(dpos is not None), workspace.numel()
+    else:
+        a.pos_ids, a.neg_ids = ptr(pos_ids), ptr(neg_ids)
+        workspace, a.workspace_bytes = _workspace(target.device, 'rsa_scatter_rows_sorted_workspace_bytes', M, n, target.shape[0])
+    a.workspace = ptr(workspace)
+    _launch('rsa_rows_update_presorted' if presorted else 'rsa_rows_update_sorted', ctypes.byref(a))
+    return target
+
+
+@_on_device
+def scatter_rows_sorted(target, query, neg_ids, dneg, *, query_index=None, pos_ids=None, dpos=None, upstream=None,
+                        pad_row=0):
+    """rsa_rows_update_sorted: target[id] += upstream * sum_e d_e * query[qrow_e], sorted by id, no atomics.
+    ``target``: [n_items, d] (a zeroed dense gradient, or the weight table with upstream = -lr)."""
+    return _rows_update('scatter_rows_sorted', target, query, dneg, neg_ids=neg_ids, query_index=query_index, pos_ids=pos_ids,
+                        dpos=dpos, upstream=upstream, pad_row=pad_row)
+
+
+@_on_device
+def adam_rows_sorted(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, betas=(0.9, 0.999), eps=1e-8, step=1,
+                     query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
+    """rsa_rows_update_sorted with the lazy-Adam state: lazy Adam (torch.optim.SparseAdam's rule) on the rows touched by the step, from the
+    factored gradient (ids, coefficients, query rows) -- no gradient tensor."""
+    return _rows_update('adam_rows_sorted', weight, query, dneg, neg_ids=neg_ids, adam=(exp_avg, exp_avg_sq, lr, betas, eps, step),
+                        query_index=query_index, pos_ids=pos_ids, dpos=dpos, upstream=upstream, pad_row=pad_row)
 
 
 @_on_device
@@ -676,14 +715,8 @@ def scatter_rows_presorted(target, query, workspace, n_queries, num_neg, dneg, *
                            pad_row=0):
     """rsa_rows_update_presorted: the apply pass of scatter_rows_sorted over the pairs ``sort_step_elements`` left in
     ``workspace`` (elements flagged solo there are skipped: the forward has applied them)."""
-    target = _need(target, torch.float32, 'target')
-    query = _need(query, torch.float32, 'query')
-    dneg = _need(dneg, torch.float32, 'dneg')
-    n_items, dim = target.shape
-    a = _rows_update_args(target, query, query_index, n_queries, num_neg, dpos, dneg, upstream, pad_row)
-    a.has_pos, a.workspace, a.workspace_bytes = int(dpos is not None), ptr(workspace), workspace.numel()
-    nat.check(nat.lib().rsa_rows_update_presorted(ctypes.byref(a), _stream()), 'rsa_rows_update_presorted')
-    return target
+    return _rows_update('scatter_rows_presorted', target, query, dneg, workspace=workspace, n_queries=n_queries, num_neg=num_neg,
+                        query_index=query_index, dpos=dpos, upstream=upstream, pad_row=pad_row)
 
 
 @_on_device
@@ -691,15 +724,9 @@ def adam_rows_presorted(weight, exp_avg, exp_avg_sq, query, workspace, n_queries
                         eps=1e-8, step=1, query_index=None, dpos=None, upstream=None, pad_row=0):
     """rsa_rows_update_presorted with the lazy-Adam state: the apply pass of adam_rows_sorted over the pairs ``sort_step_elements(want_solo=False)``
     left in ``workspace``."""
-    weight = _need(weight, torch.float32, 'weight')
-    query = _need(query, torch.float32, 'query')
-    dneg = _need(dneg, torch.float32, 'dneg')
-    n_items, dim = weight.shape
-    a = _rows_update_args(weight, query, query_index, n_queries, num_neg, dpos, dneg, upstream, pad_row)
-    a.has_pos, a.workspace, a.workspace_bytes = int(dpos is not None), ptr(workspace), workspace.numel()
-    _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, 'adam_rows_presorted')
-    nat.check(nat.lib().rsa_rows_update_presorted(ctypes.byref(a), _stream()), 'rsa_rows_update_presorted(adam)')
-    return weight
+    return _rows_update('adam_rows_presorted', weight, query, dneg, workspace=workspace, n_queries=n_queries, num_neg=num_neg,
+                        adam=(exp_avg, exp_avg_sq, lr, betas, eps, step), query_index=query_index, dpos=dpos, upstream=upstream,
+                        pad_row=pad_row)
 
 
 # ------------------------------------------------------------------ full catalog
@@ -709,20 +736,30 @@ def row_lse(x, want_softmax=False, scale=1.0):
     M, n = x.shape
     lse = torch.empty(M, dtype=torch.float32, device=x.device)
     sm = torch.empty_like(x) if want_softmax else None
-    nat.check(nat.lib().rsa_row_lse(ptr(x), M, n, ptr(lse), ptr(sm), float(scale), _stream()), 'rsa_row_lse')
+    _launch('rsa_row_lse', ptr(x), M, n, ptr(lse), ptr(sm), float(scale))
     return lse, sm
 
 
-def _pad_k(item_table, query):
-    """The MFMA kernel is built for d in {32, 64, 128}: zero-pad the k dimension of smaller dims (a copy -- only for
-    unusual dims; the dot products are unchanged).  d > 128 is handled by the callers (k split into chunks)."""
-    dim = item_table.shape[1]
+def _pad_k(*mats):
+    """The MFMA kernel is built for d in {32, 64, 128}: zero-pad the k dimension of ``mats`` [.., d] at smaller dims (a copy --
+    only for unusual dims; the dot products are unchanged) -> (*mats, the dim they have now).  d > 128 is handled by the
+    callers (k split into chunks)."""
+    dim = mats[0].shape[1]
     if dim in (32, 64, 128):
-        return item_table, query, dim
+        return (*mats, dim)
     if dim > 128:
         raise NotImplementedError(f'one MFMA pass covers embed_dim <= 128, got {dim} (ops.fullscore splits it)')
     pad = (32 if dim < 32 else 64 if dim < 64 else 128) - dim
-    return torch.nn.functional.pad(item_table, (0, pad)), torch.nn.functional.pad(query, (0, pad)), dim + pad
+    return (*(torch.nn.functional.pad(m, (0, pad)) for m in mats), dim + pad)
+
+
+def _unpad(res, d_in, out=None):
+    """The other end of ``_pad_k``: ``res`` [.., dim] of a launch at the padded k -> its first ``d_in`` columns, copied into ``out``
+    when given.  Stock dims: no copy -- ``res`` itself (``out`` when the launch wrote straight into it)."""
+    if res.shape[1] == d_in:
+        return res if out is None else out
+    res = res[:, :d_in]
+    return res.contiguous() if out is None else out.copy_(res)
 
 
 @_on_device
@@ -733,12 +770,8 @@ def row_sqnorm(table, score_mode, pad=0):
     n, d = table.shape
     out = torch.zeros(n + pad, dtype=torch.float32, device=table.device) if pad else \
         torch.empty(n, dtype=torch.float32, device=table.device)
-    nat.check(nat.lib().rsa_row_sqnorm(ptr(table), n, d, int(score_mode), ptr(out), _stream()), 'rsa_row_sqnorm')
+    _launch('rsa_row_sqnorm', ptr(table), n, d, int(score_mode), ptr(out))
     return out
-
-
-def _score_mode(cosine):
-    return int(cosine) if not isinstance(cosine, bool) else (nat.SCORE_COS if cosine else nat.SCORE_IP)
 
 
 FULLSCORE_MAX_K = 1024
@@ -775,25 +808,14 @@ def fullscore(item_table, query, *, want_scores=False, want_lse=False, k=0, item
     lse = torch.empty(B, dtype=torch.float32, device=dev) if want_lse else None
     tv = torch.empty(B, k, dtype=torch.float32, device=dev) if k else None
     ti = torch.empty(B, k, dtype=torch.int64, device=dev) if k else None
-    lib = nat.lib()
-
-    def launch(lo, hi, stream):
-        nq = hi - lo
-        ws_bytes = int(lib.rsa_fullscore_workspace_bytes(nq, n_items, int(k)))
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-        a = nat.FullscoreArgs()
-        a.item_table, a.n_items, a.dim, a.score_mode, a.n_query = table_ptr, n_items, dim, score_mode, nq
-        a.query = query.data_ptr() + lo * dim * 4
-        a.scores = None if scores is None else scores.data_ptr() + lo * (n_items - 1) * 4
-        a.lse = None if lse is None else lse.data_ptr() + lo * 4
-        a.topk_val = None if tv is None else tv.data_ptr() + lo * k * 4
-        a.topk_idx = None if ti is None else ti.data_ptr() + lo * k * 8
-        a.k, a.item_aux, a.workspace, a.workspace_bytes = int(k), ptr(ia), ptr(ws), ws_bytes
-        a.query_aux = None if qa is None else qa.data_ptr() + lo * 4
-        nat.check(lib.rsa_fullscore(ctypes.byref(a), stream), 'rsa_fullscore')
-        return ws
-
-    launch(0, B, _stream())
+    a = nat.FullscoreArgs()
+    a.item_table, a.n_items, a.dim, a.score_mode = table_ptr, n_items, dim, score_mode
+    a.query, a.n_query, a.k = ptr(query), B, int(k)
+    a.scores, a.lse, a.topk_val, a.topk_idx = ptr(scores), ptr(lse), ptr(tv), ptr(ti)
+    a.item_aux, a.query_aux = ptr(ia), ptr(qa)
+    ws, a.workspace_bytes = _workspace(dev, 'rsa_fullscore_workspace_bytes', B, n_items, int(k))
+    a.workspace = ptr(ws)
+    _launch('rsa_fullscore', ctypes.byref(a))
     return scores, lse, tv, ti
 
 
@@ -842,15 +864,12 @@ def fullscore_softmax(item_table, query, lse, row_scale=None, want_query_grad=Fa
     probs = torch.empty(B, n_items - 1, dtype=torch.float32, device=item_table.device) if want_probs else None
     if want_query_grad:
         qgrad = torch.empty(B, dim, dtype=torch.float32, device=item_table.device)
-        ws_bytes = int(nat.lib().rsa_fullscore_softmax_dq_workspace_bytes(B, n_items, dim))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=item_table.device)
-        nat.check(nat.lib().rsa_fullscore_softmax_dq(ptr(item_table), n_items, dim, ptr(query), B, ptr(lse),
-                                                     ptr(_need_opt(row_scale, torch.float32, 'row_scale')), ptr(probs),
-                                                     ptr(qgrad), ptr(ws), ws_bytes, _stream()), 'rsa_fullscore_softmax_dq')
-        return probs, (qgrad if dim == d_in else qgrad[:, :d_in].contiguous())
-    nat.check(nat.lib().rsa_fullscore_softmax(ptr(item_table), n_items, dim, ptr(query), B, ptr(lse),
-                                              ptr(_need_opt(row_scale, torch.float32, 'row_scale')), ptr(probs),
-                                              _stream()), 'rsa_fullscore_softmax')
+        ws, ws_bytes = _workspace(item_table.device, 'rsa_fullscore_softmax_dq_workspace_bytes', B, n_items, dim)
+        _launch('rsa_fullscore_softmax_dq', ptr(item_table), n_items, dim, ptr(query), B, ptr(lse),
+                ptr(_need_opt(row_scale, torch.float32, 'row_scale')), ptr(probs), ptr(qgrad), ptr(ws), ws_bytes)
+        return probs, _unpad(qgrad, d_in)
+    _launch('rsa_fullscore_softmax', ptr(item_table), n_items, dim, ptr(query), B, ptr(lse),
+            ptr(_need_opt(row_scale, torch.float32, 'row_scale')), ptr(probs))
     return probs
 
 
@@ -865,11 +884,9 @@ def fullscore_lse_grad(item_table, query):
     n_items, B, dev = tab.shape[0], q.shape[0], tab.device
     lse = torch.empty(B, dtype=torch.float32, device=dev)
     gq = torch.empty(B, dim, dtype=torch.float32, device=dev)
-    ws_bytes = int(nat.lib().rsa_fullscore_lse_grad_workspace_bytes(B, n_items, dim))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    nat.check(nat.lib().rsa_fullscore_lse_grad(ptr(tab), n_items, dim, ptr(q), B, ptr(lse), ptr(gq), ptr(ws), ws_bytes, _stream()),
-              'rsa_fullscore_lse_grad')
-    return lse, (gq if dim == d_in else gq[:, :d_in].contiguous())
+    ws, ws_bytes = _workspace(dev, 'rsa_fullscore_lse_grad_workspace_bytes', B, n_items, dim)
+    _launch('rsa_fullscore_lse_grad', ptr(tab), n_items, dim, ptr(q), B, ptr(lse), ptr(gq), ptr(ws), ws_bytes)
+    return lse, _unpad(gq, d_in)
 
 
 @_on_device
@@ -882,21 +899,13 @@ def fullscore_softmax_dw(item_table, query, lse, row_scale=None, out=None):
     d_in = item_table.shape[1]
     tab, q, dim = _pad_k(item_table, query)
     n_items, B = tab.shape[0], q.shape[0]
-    direct = dim == d_in and out is not None
-    res = out if direct else torch.empty(n_items, dim, dtype=torch.float32, device=tab.device)
+    res = out if dim == d_in and out is not None else torch.empty(n_items, dim, dtype=torch.float32, device=tab.device)
     res = _need(res, torch.float32, 'out')
     if res.shape != (n_items, dim):
         raise ValueError(f'fullscore_softmax_dw: out must be [{n_items}, {dim}]')
-    nat.check(nat.lib().rsa_fullscore_softmax_dw(ptr(tab), n_items, dim, ptr(q), B, ptr(lse),
-                                                 ptr(_need_opt(row_scale, torch.float32, 'row_scale')), ptr(res), _stream()),
-              'rsa_fullscore_softmax_dw')
-    if direct:
-        return out
-    res = res if dim == d_in else res[:, :d_in]
-    if out is not None:
-        out.copy_(res)
-        return out
-    return res.contiguous()
+    _launch('rsa_fullscore_softmax_dw', ptr(tab), n_items, dim, ptr(q), B, ptr(lse),
+            ptr(_need_opt(row_scale, torch.float32, 'row_scale')), ptr(res))
+    return _unpad(res, d_in, out)
 
 
 @_on_device
@@ -909,23 +918,17 @@ def probs_t_query(probs, query, out=None):
     d = query.shape[1]
     if query.shape[0] != B:
         raise ValueError('probs_t_query: probs [B, n] and query [B, d] must share B')
-    if d not in (32, 64, 128):
-        if d > 128:
-            raise NotImplementedError('probs_t_query: embed_dim <= 128')
-        dp = 32 if d <= 32 else (64 if d <= 64 else 128)
-        qp = torch.zeros(B, dp, dtype=torch.float32, device=query.device)
-        qp[:, :d] = query
-        res = probs_t_query(probs, qp)[:, :d]
-        if out is not None:
-            out.copy_(res)
-            return out
-        return res.contiguous()
-    if out is None:
-        out = torch.empty(n, d, dtype=torch.float32, device=probs.device)
+    if d > 128:
+        raise NotImplementedError('probs_t_query: embed_dim <= 128')
+    q, dim = _pad_k(query)
+    if out is None or dim != d:
+        res = torch.empty(n, dim, dtype=torch.float32, device=probs.device)
     elif tuple(out.shape) != (n, d) or not out.is_contiguous() or out.dtype != torch.float32:
         raise ValueError('probs_t_query: out must be a contiguous fp32 [n, d] tensor')
-    nat.check(nat.lib().rsa_probs_t_query(ptr(probs), B, n, probs.stride(0), ptr(query), d, ptr(out), _stream()), 'rsa_probs_t_query')
-    return out
+    else:
+        res = out
+    _launch('rsa_probs_t_query', ptr(probs), B, n, probs.stride(0), ptr(q), dim, ptr(res))
+    return _unpad(res, d, out)
 
 
 @_on_device
@@ -937,8 +940,8 @@ def topk_mask_history(cand_val, cand_idx, user_hist, k):
     B, kc = cand_val.shape
     out_v = torch.empty(B, k, dtype=torch.float32, device=cand_val.device)
     out_i = torch.empty(B, k, dtype=torch.int64, device=cand_val.device)
-    nat.check(nat.lib().rsa_topk_mask_history(ptr(cand_val), ptr(cand_idx), kc, ptr(user_hist), user_hist.shape[1], B,
-                                              int(k), ptr(out_v), ptr(out_i), _stream()), 'rsa_topk_mask_history')
+    _launch('rsa_topk_mask_history', ptr(cand_val), ptr(cand_idx), kc, ptr(user_hist), user_hist.shape[1], B, int(k),
+            ptr(out_v), ptr(out_i))
     return out_v, out_i
 
 
@@ -950,66 +953,11 @@ def row_topk(values, k):
     v2 = values.reshape(-1, n)
     out_v = torch.empty(v2.shape[0], k, dtype=torch.float32, device=values.device)
     out_i = torch.empty(v2.shape[0], k, dtype=torch.int64, device=values.device)
-    nat.check(nat.lib().rsa_row_topk(ptr(v2), v2.shape[0], n, int(k), ptr(out_v), ptr(out_i), _stream()), 'rsa_row_topk')
+    _launch('rsa_row_topk', ptr(v2), v2.shape[0], n, int(k), ptr(out_v), ptr(out_i))
     return out_v.view(*lead, k), out_i.view(*lead, k)
 
 
 @_on_device
 def rng_advance(offset_dev, increment):
     """*offset_dev += increment on the stream (rsa_rng_advance): the device copy of the generator offset."""
-    nat.check(nat.lib().rsa_rng_advance(ptr(offset_dev), int(increment), _stream()), 'rsa_rng_advance')
-
-
-@_on_device
-def scatter_rows_sorted(target, query, neg_ids, dneg, *, query_index=None, pos_ids=None, dpos=None, upstream=None,
-                        pad_row=0):
-    """rsa_rows_update_sorted: target[id] += upstream * sum_e d_e * query[qrow_e], sorted by id, no atomics.
-    ``target``: [n_items, d] (a zeroed dense gradient, or the weight table with upstream = -lr)."""
-    target = _need(target, torch.float32, 'target')
-    query = _need(query, torch.float32, 'query')
-    neg_ids = _need(neg_ids, torch.int64, 'neg_ids')
-    dneg = _need(dneg, torch.float32, 'dneg')
-    query_index = _need_opt(query_index, torch.int64, 'query_index')
-    pos_ids = _need_opt(pos_ids, torch.int64, 'pos_ids')
-    dpos = _need_opt(dpos, torch.float32, 'dpos')
-    upstream = _need_opt(upstream, torch.float32, 'upstream')
-    n_items, dim = target.shape
-    M = query_index.numel() if query_index is not None else query.shape[0]
-    if M == 0:
-        return target
-    n = neg_ids.numel() // M
-    ws_bytes = int(nat.lib().rsa_scatter_rows_sorted_workspace_bytes(M, n, n_items))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=target.device)
-    a = _rows_update_args(target, query, query_index, M, n, dpos, dneg, upstream, pad_row)
-    a.pos_ids, a.neg_ids, a.workspace, a.workspace_bytes = ptr(pos_ids), ptr(neg_ids), ptr(ws), ws_bytes
-    nat.check(nat.lib().rsa_rows_update_sorted(ctypes.byref(a), _stream()), 'rsa_rows_update_sorted')
-    return target
-
-
-@_on_device
-def adam_rows_sorted(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, betas=(0.9, 0.999), eps=1e-8, step=1,
-                     query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
-    """rsa_rows_update_sorted with the lazy-Adam state: lazy Adam (torch.optim.SparseAdam's rule) on the rows touched by the step, from the
-    factored gradient (ids, coefficients, query rows) -- no gradient tensor."""
-    weight = _need(weight, torch.float32, 'weight')
-    exp_avg = _need(exp_avg, torch.float32, 'adam_rows_sorted: exp_avg')
-    exp_avg_sq = _need(exp_avg_sq, torch.float32, 'adam_rows_sorted: exp_avg_sq')
-    query = _need(query, torch.float32, 'query')
-    neg_ids = _need(neg_ids, torch.int64, 'neg_ids')
-    dneg = _need(dneg, torch.float32, 'dneg')
-    query_index = _need_opt(query_index, torch.int64, 'query_index')
-    pos_ids = _need_opt(pos_ids, torch.int64, 'pos_ids')
-    dpos = _need_opt(dpos, torch.float32, 'dpos')
-    upstream = _need_opt(upstream, torch.float32, 'upstream')
-    n_items, dim = weight.shape
-    M = query_index.numel() if query_index is not None else query.shape[0]
-    if M == 0:
-        return weight
-    n = neg_ids.numel() // M
-    ws_bytes = int(nat.lib().rsa_scatter_rows_sorted_workspace_bytes(M, n, n_items))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=weight.device)
-    a = _rows_update_args(weight, query, query_index, M, n, dpos, dneg, upstream, pad_row)
-    a.pos_ids, a.neg_ids, a.workspace, a.workspace_bytes = ptr(pos_ids), ptr(neg_ids), ptr(ws), ws_bytes
-    _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, 'adam_rows_sorted')
-    nat.check(nat.lib().rsa_rows_update_sorted(ctypes.byref(a), _stream()), 'rsa_rows_update_sorted(adam)')
-    return weight
+    _launch('rsa_rng_advance', ptr(offset_dev), int(increment))

@@ -104,12 +104,11 @@ def _probe_us(buf, dev):
     st = _st(dev)
     if st['source'] is None:
         st['source'] = torch.empty(SOURCE_BYTES, dtype=torch.uint8, device=dev)      # (pick() has checked that there is room)
-    lib, src = nat.lib(), st['source']
+    src = st['source']
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
     def launch(salt):
-        nat.check(lib.rsa_placement_probe(ctypes.c_void_p(buf.data_ptr()), buf.numel(), ctypes.c_void_p(src.data_ptr()),
-                                          src.numel(), salt, stream), 'rsa_placement_probe')
+        nat.launch('rsa_placement_probe', stream, nat.ptr(buf), buf.numel(), nat.ptr(src), src.numel(), salt)
     # the chip runs the same launch 7-11 % slower for about a second after it idled: a probe taken cold would read
     # as the slow class.  Keep the GPU busy with the probe itself first when the last probe was a while ago.
     now = time.perf_counter()

@@ -13,6 +13,8 @@ from dataclasses import dataclass
 
 import torch
 
+from ._native import SAMPLER_POPULAR
+
 BLOCK = 256
 
 
@@ -37,6 +39,12 @@ def counter_offset(numel, g, unroll):
 def randint_unroll(low, high):
     """torch.randint uses 64-bit draws (2 per philox call) once the range reaches 2**28."""
     return 2 if (int(high) - int(low)) >= (1 << 28) else 4
+
+
+def sampler_unroll(kind, n_items):
+    """Unroll of the torch call an in-kernel sampler stands for: ``torch.rand`` (4) for the popularity sampler's inverse CDF,
+    ``torch.randint(1, n_items)`` for the uniform one."""
+    return 4 if kind == SAMPLER_POPULAR else randint_unroll(1, n_items)
 
 
 class _no_shard:

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from . import _native as nat
 from . import ops
 
 __all__ = ['Sampler', 'UniformSampler', 'MaskedUniformSampler', 'PopularSamplerModel', 'build_guide_table',
@@ -292,6 +293,16 @@ class PopularSamplerModel(Sampler):
 
     def compute_item_p(self, query, pos_items):
         return ops.item_logp(self.pop_prob, pos_items)                    # sampler.py:257-258
+
+
+def sampler_kind(sampler):
+    """rsa_sampler_kind of the plugin the kernels draw from themselves, None for every other one.  Exact types only: a
+    subclass may override ``forward``, and must then go through the plugin path."""
+    if type(sampler) is UniformSampler:
+        return nat.SAMPLER_UNIFORM
+    if type(sampler) is PopularSamplerModel:
+        return nat.SAMPLER_POPULAR
+    return None
 
 
 class RetrieverSampler(Sampler):

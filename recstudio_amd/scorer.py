@@ -139,8 +139,7 @@ class _FullScoreFn(torch.autograd.Function):
 
 def full_scores(query, items, cosine=False):
     """([B,D],[N,D]) case of the scorers (scorer.py:16, :19-25, :28-34): items has no padding row here."""
-    mode = int(cosine) if not isinstance(cosine, bool) else (nat.SCORE_COS if cosine else nat.SCORE_IP)
-    return _FullScoreFn.apply(query, items.contiguous(), mode)
+    return _FullScoreFn.apply(query, items.contiguous(), ops._score_mode(cosine))
 
 
 # Full-catalog logsumexp under autograd, three forms (RSA_FULL_SOFTMAX_BACKWARD):

@@ -134,11 +134,12 @@ class HipBackend:
     def sampler_spec(self, sampler):
         """The in-kernel form of a Sampler plugin (drawn inside the routing pass), or None: then the plugin itself is
         called and its ids are routed as given.  Exact types only -- a subclass may override ``forward``."""
-        from .sampler import PopularSamplerModel, UniformSampler
-        if type(sampler) is UniformSampler:
-            return {'kind': nat.SAMPLER_UNIFORM, 'n_items': sampler.num_items + 1}
-        if type(sampler) is PopularSamplerModel:
-            return {'kind': nat.SAMPLER_POPULAR, 'n_items': sampler.table.numel(), 'tables': sampler.lookup_kwargs()}
+        from .sampler import sampler_kind
+        kind = sampler_kind(sampler)
+        if kind == nat.SAMPLER_UNIFORM:
+            return {'kind': kind, 'n_items': sampler.num_items + 1}
+        if kind == nat.SAMPLER_POPULAR:
+            return {'kind': kind, 'n_items': sampler.table.numel(), 'tables': sampler.lookup_kwargs()}
         return None
 
     def sample(self, sampler, n_queries, n, device, pos_ids, shard=None):
@@ -181,7 +182,7 @@ class HipBackend:
             a.neg_ids = ptr(neg)
             out['neg_ids'] = neg.view(B, n)
         elif B * n:
-            unroll = 4 if kind == nat.SAMPLER_POPULAR else rng.randint_unroll(1, a.n_items)
+            unroll = rng.sampler_unroll(kind, a.n_items)
             off0 = generator.get_offset() if count_only else None
             with rng.sharded_stream(rank, G, generator):
                 pc = rng.reserve(B * n, unroll, dev)
@@ -214,7 +215,7 @@ class HipBackend:
         if count_only:
             counts = torch.empty(chunks * G * banks, dtype=torch.int32, device=dev)
             a.counts_out = ptr(counts)
-            nat.check(nat.lib().rsa_shard_sample_route(ctypes.byref(a), ops._stream()), 'rsa_shard_sample_route')
+            ops._launch('rsa_shard_sample_route', ctypes.byref(a))
             return counts
         stride = int(capacity) + self.HDR
         out['send'] = torch.empty(chunks * G * banks * stride, dtype=torch.int64, device=dev)
@@ -228,7 +229,7 @@ class HipBackend:
             if wg is None or wg.numel() < ints:
                 wg = state['wg_scratch'] = torch.empty(max(ints, 1), dtype=torch.int32, device=dev)
             a.deterministic, a.wg_scratch, a.wg_scratch_ints = 1, ptr(wg), wg.numel()
-        nat.check(nat.lib().rsa_shard_sample_route(ctypes.byref(a), ops._stream()), 'rsa_shard_sample_route')
+        ops._launch('rsa_shard_sample_route', ctypes.byref(a))
         return out
 
     @ops._on_device
@@ -236,10 +237,9 @@ class HipBackend:
         """Owner side: fp32 scores of the live slots of ``recv_keys`` [n_seg, stride]; ``first``: also publish the
         step's job-wide dropped count (sum of the received headers) into the state words."""
         scores = out if out is not None else torch.empty(n_seg * stride, dtype=torch.float32, device=recv_keys.device)
-        nat.check(nat.lib().rsa_shard_score_segments(
-            ptr(item_local), item_local.shape[0], item_local.shape[1], ptr(q_all), q_all.shape[0], ptr(recv_keys), n_seg,
-            stride, ptr(scores), ptr(state['step_dropped']) if first else None, ptr(state['overflow']) if first else None,
-            ops._stream()), 'rsa_shard_score_segments')
+        ops._launch('rsa_shard_score_segments', ptr(item_local), item_local.shape[0], item_local.shape[1], ptr(q_all),
+                    q_all.shape[0], ptr(recv_keys), n_seg, stride, ptr(scores), ptr(state['step_dropped']) if first else None,
+                    ptr(state['overflow']) if first else None)
         return scores
 
     @ops._on_device
@@ -268,7 +268,7 @@ class HipBackend:
             if want_dsend:
                 out['d_send'] = torch.empty(scores_home.numel(), dtype=torch.float32, device=dev)
                 a.d_send = ptr(out['d_send'])
-        nat.check(nat.lib().rsa_shard_home(ctypes.byref(a), ops._stream()), 'rsa_shard_home')
+        ops._launch('rsa_shard_home', ctypes.byref(a))
         return out
 
     @ops._on_device
@@ -277,8 +277,8 @@ class HipBackend:
         B = dpos.numel()
         n = dneg.numel() // max(B, 1)
         d_send = torch.empty(n_slots, dtype=torch.float32, device=dpos.device)
-        nat.check(nat.lib().rsa_shard_scatter_slots(ptr(ops._need(dpos, torch.float32, 'dpos')), ptr(ops._need(dneg, torch.float32, 'dneg')),
-                                                    ptr(slot_of), B, n, ptr(d_send), ops._stream()), 'rsa_shard_scatter_slots')
+        ops._launch('rsa_shard_scatter_slots', ptr(ops._need(dpos, torch.float32, 'dpos')),
+                    ptr(ops._need(dneg, torch.float32, 'dneg')), ptr(slot_of), B, n, ptr(d_send))
         return d_send
 
     @ops._on_device
@@ -303,16 +303,15 @@ class HipBackend:
             a.item_target, a.item_scale = ptr(item_grad_local), ptr(item_scale)
             a.step_dropped, a.scale_out, a.qgrad_all = ptr(state['step_dropped']), ptr(scale), ptr(qgrad_all)
             a.item_pad_row = int(item_pad_row)
-            nbytes = int(nat.lib().rsa_shard_backward_workspace_bytes(int(n_seg), int(stride), q_all.shape[0]))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=recv_keys.device)
-            a.workspace, a.workspace_bytes = ptr(ws), nbytes
-            nat.check(nat.lib().rsa_shard_backward_segments(ctypes.byref(a), ops._stream()), 'rsa_shard_backward_segments')
+            ws, a.workspace_bytes = ops._workspace(recv_keys.device, 'rsa_shard_backward_workspace_bytes', int(n_seg), int(stride),
+                                                   q_all.shape[0])
+            a.workspace = ptr(ws)
+            ops._launch('rsa_shard_backward_segments', ctypes.byref(a))
             return
         rows = torch.empty(m, dtype=torch.int64, device=recv_keys.device)
         qidx = torch.empty(m, dtype=torch.int64, device=recv_keys.device)
-        nat.check(nat.lib().rsa_shard_unpack_segments(ptr(recv_keys), n_seg, stride, ptr(rows), ptr(qidx), ptr(item_scale),
-                                                      ptr(state['step_dropped']), ptr(scale), ops._stream()),
-                  'rsa_shard_unpack_segments')
+        ops._launch('rsa_shard_unpack_segments', ptr(recv_keys), n_seg, stride, ptr(rows), ptr(qidx), ptr(item_scale),
+                    ptr(state['step_dropped']), ptr(scale))
         if item_scale is not None:
             raise NotImplementedError('in-place item update needs embed_dim in {64, 128, 256}')
         d_owner = torch.where(rows >= 0, d_owner * scale[1], torch.zeros((), device=d_owner.device))
@@ -327,22 +326,21 @@ class HipBackend:
     @ops._on_device
     def pos_scores(self, item_local, q_all, pos_rows):
         """[Q] scores of the positives this rank owns (pos_rows >= 0), 0 for the others."""
-        out = torch.empty(pos_rows.numel(), dtype=torch.float32, device=q_all.device)
-        nat.check(nat.lib().rsa_shard_pos_score(ptr(item_local), item_local.shape[0], item_local.shape[1], ptr(q_all), q_all.shape[0],
-                                                ptr(ops._need(pos_rows, torch.int64, 'pos_rows')), ptr(out), None, 0, 1, 0,
-                                                ops._stream()), 'rsa_shard_pos_score')
-        return out
+        return self._pos_score(item_local, q_all, ops._need(pos_rows, torch.int64, 'pos_rows'), None, 0, 1, 0)[1]
 
     @ops._on_device
     def pos_rows_and_scores(self, item_local, q_all, pos_all, plan, rank):
         """The same from the gathered GLOBAL ids, in one launch: (pos_rows [Q] -- local row of every positive this rank
         owns, -1 for the others --, scores [Q])."""
-        Q = pos_all.numel()
-        rows = torch.empty(Q, dtype=torch.int64, device=q_all.device)
-        out = torch.empty(Q, dtype=torch.float32, device=q_all.device)
-        nat.check(nat.lib().rsa_shard_pos_score(ptr(item_local), item_local.shape[0], item_local.shape[1], ptr(q_all), q_all.shape[0],
-                                                ptr(rows), ptr(out), ptr(ops._need(pos_all, torch.int64, 'pos_all')), plan.rows_arg,
-                                                plan.world, int(rank), ops._stream()), 'rsa_shard_pos_score')
+        rows = torch.empty(pos_all.numel(), dtype=torch.int64, device=q_all.device)
+        return self._pos_score(item_local, q_all, rows, ops._need(pos_all, torch.int64, 'pos_all'), plan.rows_arg, plan.world,
+                               int(rank))
+
+    def _pos_score(self, item_local, q_all, rows, pos_all, rows_arg, world, rank):
+        """rsa_shard_pos_score: ``rows`` read (``pos_all`` None) or written from the global ids; -> (rows, scores [Q])."""
+        out = torch.empty(rows.numel(), dtype=torch.float32, device=q_all.device)
+        ops._launch('rsa_shard_pos_score', ptr(item_local), item_local.shape[0], item_local.shape[1], ptr(q_all),
+                    q_all.shape[0], ptr(rows), ptr(out), ptr(pos_all), rows_arg, world, rank)
         return rows, out
 
     @ops._on_device
@@ -371,9 +369,8 @@ class HipBackend:
         a.step_dropped, a.overflow_sticky, a.scale_out = ptr(state['step_dropped']), ptr(state['overflow']), ptr(state['scale'])
         a.d_slots, a.dsum_part, a.loss_part = ptr(keep['d_slots']), ptr(keep['dsum_part']), ptr(keep['loss_part'])
         a.reduce_scratch, a.item_pad_row, a.keys_grouped = ptr(ops._scratch()), int(item_pad_row), int(bool(keys_grouped))
-        nbytes = int(nat.lib().rsa_shard_backward_workspace_bytes(int(n_seg), int(stride), int(Q)))
-        keep['ws'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        a.workspace, a.workspace_bytes = ptr(keep['ws']), nbytes
+        keep['ws'], a.workspace_bytes = ops._workspace(dev, 'rsa_shard_backward_workspace_bytes', int(n_seg), int(stride), int(Q))
+        a.workspace = ptr(keep['ws'])
         keep['args'] = a
         return keep
 
@@ -384,7 +381,7 @@ class HipBackend:
             ctx['tensors'] += [q_all, qgrad_all]
             a.q_all, a.pos_score, a.qgrad_all = ptr(ops._need(q_all, torch.float32, 'q_all')), ptr(ctx['pos_score']), ptr(qgrad_all)
         a.forward_parts = int(parts)
-        nat.check(nat.lib().rsa_shard_owner_bpr_forward(ctypes.byref(a), ops._stream()), 'rsa_shard_owner_bpr_forward')
+        ops._launch('rsa_shard_owner_bpr_forward', ctypes.byref(a))
         return ctx
 
     @ops._on_device
@@ -406,8 +403,8 @@ class HipBackend:
         """``parts``: 0 = the whole finish; 1 = the positives only (``qgrad_all`` is complete afterwards); 2 = the shared rows'
         sorted apply pass (after a call with 1)."""
         ctx['args'].finish_parts = int(parts)
-        nat.check(nat.lib().rsa_shard_owner_bpr_finish(ctypes.byref(ctx['args']), ptr(ops._need(dsum_all, torch.float32, 'dsum_all')),
-                                                       ops._stream()), 'rsa_shard_owner_bpr_finish')
+        ops._launch('rsa_shard_owner_bpr_finish', ctypes.byref(ctx['args']),
+                    ptr(ops._need(dsum_all, torch.float32, 'dsum_all')))
 
     @ops._on_device
     def owner_ssm_forward(self, state, item_local, q_all, recv_keys, n_seg, stride, pos_rows, n, mean_den, item_target, item_scale,
@@ -425,7 +422,7 @@ class HipBackend:
         a.q_all = ptr(ops._need(q_all, torch.float32, 'q_all'))
         a.logq_rows = ptr(ops._need_opt(logq_rows, torch.float32, 'logq_rows'))
         a.run_max, a.run_sum, a.run_acc = ptr(ctx['run_max']), ptr(ctx['run_sum']), ptr(ctx['run_acc'])
-        nat.check(nat.lib().rsa_shard_owner_ssm_forward(ctypes.byref(a), ops._stream()), 'rsa_shard_owner_ssm_forward')
+        ops._launch('rsa_shard_owner_ssm_forward', ctypes.byref(a))
         return ctx
 
     @ops._on_device
@@ -436,8 +433,7 @@ class HipBackend:
         ctx['pos_score'] = ops._need(z_pos_all, torch.float32, 'z_pos_all')
         ctx['tensors'] += [qgrad_all, lse_all]
         a.pos_score, a.qgrad_all = ptr(ctx['pos_score']), ptr(ops._need(qgrad_all, torch.float32, 'qgrad_all'))
-        nat.check(nat.lib().rsa_shard_owner_ssm_finish(ctypes.byref(a), ptr(ops._need(lse_all, torch.float32, 'lse_all')),
-                                                       ops._stream()), 'rsa_shard_owner_ssm_finish')
+        ops._launch('rsa_shard_owner_ssm_finish', ctypes.byref(a), ptr(ops._need(lse_all, torch.float32, 'lse_all')))
 
     # -- exact (variable-split) exchange ------------------------------------------------------------------------------
     def gather_rows(self, table, ids):
@@ -448,8 +444,7 @@ class HipBackend:
     def count(self, pos, neg, plan):
         counts = torch.empty(plan.world, dtype=torch.int32, device=pos.device)
         n = neg.shape[1]
-        nat.check(nat.lib().rsa_shard_count(ptr(pos), ptr(neg), pos.numel(), n, plan.rows_arg, plan.world,
-                                            ptr(counts), ops._stream()), 'rsa_shard_count')
+        ops._launch('rsa_shard_count', ptr(pos), ptr(neg), pos.numel(), n, plan.rows_arg, plan.world, ptr(counts))
         return counts
 
     def route(self, pos, neg, plan, query_base, starts):
@@ -458,8 +453,8 @@ class HipBackend:
         keys = torch.empty(numel, dtype=torch.int64, device=pos.device)
         positions = torch.empty(numel, dtype=torch.int64, device=pos.device)
         cursor = starts.to(device=pos.device, dtype=torch.int32).clone()
-        nat.check(nat.lib().rsa_shard_route(ptr(pos), ptr(neg), B, n, plan.rows_arg, plan.world, int(query_base),
-                                            ptr(cursor), ptr(keys), ptr(positions), ops._stream()), 'rsa_shard_route')
+        ops._launch('rsa_shard_route', ptr(pos), ptr(neg), B, n, plan.rows_arg, plan.world, int(query_base), ptr(cursor),
+                    ptr(keys), ptr(positions))
         return keys, positions
 
     def score_keys(self, item_local, q_all, keys):
@@ -467,14 +462,12 @@ class HipBackend:
 
     def scatter(self, scores, positions, numel):
         dst = torch.zeros(numel, dtype=torch.float32, device=scores.device)
-        nat.check(nat.lib().rsa_scatter_f32(ptr(scores), ptr(positions), scores.numel(), ptr(dst), ops._stream()),
-                  'rsa_scatter_f32')
+        ops._launch('rsa_scatter_f32', ptr(scores), ptr(positions), scores.numel(), ptr(dst))
         return dst
 
     def gather(self, src, positions):
         dst = torch.empty(positions.numel(), dtype=torch.float32, device=src.device)
-        nat.check(nat.lib().rsa_gather_f32(ptr(src), ptr(positions), positions.numel(), ptr(dst), ops._stream()),
-                  'rsa_gather_f32')
+        ops._launch('rsa_gather_f32', ptr(src), ptr(positions), positions.numel(), ptr(dst))
         return dst
 
     def backward_keys(self, item_local, q_all, keys, dscore, item_grad_local, qgrad_all, item_pad_row=-1, item_scale=None):
@@ -487,7 +480,7 @@ class HipBackend:
             return
         rows = torch.empty(m, dtype=torch.int64, device=keys.device)
         qidx = torch.empty(m, dtype=torch.int64, device=keys.device)
-        nat.check(nat.lib().rsa_shard_unpack(ptr(keys), m, ptr(rows), ptr(qidx), ops._stream()), 'rsa_shard_unpack')
+        ops._launch('rsa_shard_unpack', ptr(keys), m, ptr(rows), ptr(qidx))
         if item_local.shape[1] in (64, 128, 256):
             ops.scatter_rows_sorted(qgrad_all, item_local, qidx.view(m, 1), dscore.view(m, 1), query_index=rows, pad_row=-1)
             ops.scatter_rows_sorted(item_grad_local, q_all, rows.view(m, 1), dscore.view(m, 1), query_index=qidx,
@@ -607,10 +600,6 @@ class ShardedItemTable:
     # With ONE rank every collective of the step is the identity (the all-gather of one block, an all-to-all with
     # itself, a reduce-scatter of one part): unless ``force_collectives`` asks for the calls anyway (tests, and the
     # bench's protocol-cost figure) they are skipped -- no copy through the communicator, no launch.
-    def _all_reduce_max(self, t):
-        if not self._solo:
-            self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
-
     def _all_gather_rows(self, x):
         return self._all_gather_rows_start(x)()
 
