@@ -125,45 +125,65 @@ def bound_ratios(ref, got_w, got_m, got_v):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-def emulate_fp32(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, betas, eps, step, query_index=None, pos_ids=None,
-                 dpos=None, upstream=None, pad_row=0, chunk=16, float_betas=False):
-    """The sorted kernels' arithmetic in numpy fp32, operation for operation: elements stably sorted by id, every chunk of
+def emulate_run_sums(query, neg_ids, dneg, n_rows, *, query_index=None, pos_ids=None, dpos=None, pad_row=0, chunk=16,
+                      drop_element_of=None, partial_scale=None):
+    """The run sums of the sorted apply pass in numpy fp32, operation for operation: elements stably sorted by id, every chunk of
     `chunk` sorted elements summed run by run in element order with one rounding per multiply-add, a run that crosses chunk
-    borders = trailing partial + leading partials in chunk order, g = upstream * sum, then the update of apply_run.
-    ``float_betas``: the hyper-parameters carried as fp32 and 1 - beta taken in fp32 (the ABI 11 form) instead of the
-    caller's doubles.  -> (rows, w, m, v) fp32 arrays of the touched rows."""
+    borders = trailing partial + leading partials in chunk order.  -> ({row: fp32 sum [d]}, {row: element count}).
+    Two planted mistakes for the tests of the bounds: ``drop_element_of`` = a row whose last element is left out;
+    ``partial_scale`` = a factor wrongly applied to every partial of a run of more than one segment.
+    The coefficients are rounded to fp32 first, as the query rows are: the kernels read fp32 coefficients.  A float64 ``dneg`` is
+    therefore NOT multiplied at double precision (every caller passes fp32, for which the cast changes nothing)."""
     f32 = np.float32
     ids, qrow, coef = (t.cpu().numpy() for t in flat_elements(neg_ids, dneg, query_index, pos_ids, dpos))
     q = query.cpu().numpy().astype(f32)
-    n_items = weight.shape[0]
-    key = np.where(ids < 0, n_items, ids)
+    coef = coef.astype(f32)
+    key = np.where(ids < 0, n_rows, ids)
     order = np.argsort(key, kind='stable')
     key = key[order]
-    up = f32(1.0) if upstream is None else f32(upstream.cpu().numpy().reshape(-1)[0])
 
     def fma(c, x, acc):                                   # fl32(c * x + acc): the product of two fp32 numbers is exact in float64
         return (np.float64(c) * x.astype(np.float64) + acc.astype(np.float64)).astype(f32)
 
-    sums = {}
+    sums, counts = {}, {}
     pos = 0
     while pos < len(key):
         end = pos
         while end < len(key) and key[end] == key[pos]:
             end += 1
         k = int(key[pos])
-        if k != n_items and k != pad_row:
+        if k != n_rows and k != pad_row:
             total = None
             lo = pos
-            while lo < end:                               # the run's segments, chunk by chunk
-                hi = min(end, (lo // chunk + 1) * chunk)
+            last = end - 1 if (drop_element_of is not None and k == drop_element_of) else end
+            segments = (last - 1) // chunk - pos // chunk + 1
+            while lo < last:                              # the run's segments, chunk by chunk
+                hi = min(last, (lo // chunk + 1) * chunk)
                 acc = np.zeros(q.shape[1], f32)
                 for i in range(lo, hi):
                     e = order[i]
                     acc = fma(coef[e], q[qrow[e]], acc)
+                if partial_scale is not None and segments > 1:
+                    acc = (f32(partial_scale) * acc).astype(f32)
                 total = acc if total is None else (total + acc).astype(f32)
                 lo = hi
-            sums[k] = total
+            if total is not None:
+                sums[k], counts[k] = total, last - pos
         pos = end
+    return sums, counts
+
+
+def emulate_fp32(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, betas, eps, step, query_index=None, pos_ids=None,
+                 dpos=None, upstream=None, pad_row=0, chunk=16, float_betas=False):
+    """The sorted kernels' arithmetic in numpy fp32, operation for operation: the run sums of emulate_run_sums, g = upstream * sum,
+    then the update of apply_run.
+    ``float_betas``: the hyper-parameters carried as fp32 and 1 - beta taken in fp32 (the ABI 11 form) instead of the
+    caller's doubles.  -> (rows, w, m, v) fp32 arrays of the touched rows."""
+    f32 = np.float32
+    up = f32(1.0) if upstream is None else f32(upstream.cpu().numpy().reshape(-1)[0])
+    sums, _ = emulate_run_sums(query, neg_ids, dneg, weight.shape[0], query_index=query_index, pos_ids=pos_ids, dpos=dpos,
+                               pad_row=pad_row, chunk=chunk)
+    d = query.shape[1]
     rows = np.array(sorted(sums), dtype=np.int64)
     b1, b2 = betas
     if float_betas:
@@ -174,7 +194,7 @@ def emulate_fp32(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, betas
         ss = f32(step_size(lr, betas, step))
     epsf = f32(eps)
     w0, m0, v0 = (t[torch.as_tensor(rows)].cpu().numpy().astype(f32) for t in (weight, exp_avg, exp_avg_sq))
-    g = np.stack([up * sums[int(r)] for r in rows]).astype(f32) if len(rows) else np.zeros((0, q.shape[1]), f32)
+    g = np.stack([up * sums[int(r)] for r in rows]).astype(f32) if len(rows) else np.zeros((0, d), f32)
     m1 = (m0 + ((g - m0).astype(f32) * omb1).astype(f32)).astype(f32)
     v1 = (v0 + (((g * g).astype(f32) - v0).astype(f32) * omb2).astype(f32)).astype(f32)
     w1 = (w0 - (ss * (m1 / (np.sqrt(v1).astype(f32) + epsf).astype(f32)).astype(f32)).astype(f32)).astype(f32)

@@ -293,6 +293,7 @@ def test_bpr_sgd_step_equals_autograd_plus_torch_sgd(ra):
     user2.load_state_dict(user.state_dict())
     uid = torch.randint(1, U, (B,), device=DEV)
     pos = torch.randint(1, N, (B,), device=DEV)
+    iw0, uw0 = item.weight.detach().clone(), user.weight.detach().clone()
     torch.manual_seed(8)
     loss, neg = ra.fused.bpr_sgd_step(item.weight, user.weight, n, lr, user_ids=uid, pos_ids=pos,
                                       sampler=ra.UniformSampler(N))
@@ -306,6 +307,24 @@ def test_bpr_sgd_step_equals_autograd_plus_torch_sgd(ra):
     np.testing.assert_allclose(item.weight.detach().cpu(), item2.weight.detach().cpu(), rtol=1e-4, atol=1e-7)
     np.testing.assert_allclose(user.weight.detach().cpu(), user2.weight.detach().cpu(), rtol=1e-4, atol=1e-7)
     assert not item.weight[0].any() and not user.weight[0].any()
+    # The assertions above judge the WEIGHT (weights N(0, 1), lr = 0.05: the median update is 3.9e-6 of the weight, their
+    # tolerance 25 times that).  The UPDATE: W' - W and U' - U against the float64 step within the end-to-end bound of
+    # tests/sgd_referee.py on every element of every touched row (2u |W'| for the read-modify-write + the gradient's own
+    # bound), no other row moved; and against torch's fp32 update within twice that bound (torch's fp32 autograd + SGD is
+    # one more fp32 implementation of the same step).
+    import sgd_referee as sr
+    c = sr.coefficients(iw0, uw0, uid, pos, neg)
+    allow, _ = sr.torch_sigmoid_allowance(iw0.device, B, n)
+    for ref, got, theirs, start in zip(sr.end_to_end(iw0, uw0, uid, pos, neg, lr, c, allow), (item.weight.data, user.weight.data),
+                                       (item2.weight.data, user2.weight.data), (iw0, uw0)):
+        ratio, moved = sr.judge(ref, got, start)
+        r = ref['rows']
+        upd, upd_t, want = got[r].double() - ref['w0'], theirs[r].double() - ref['w0'], ref['w'] - ref['w0']
+        vs_torch = float(((upd - upd_t).abs() / (2 * ref['tol'])).max())
+        print(f'update against float64: error / bound {ratio:.3f}; against torch fp32: {vs_torch:.3f} of twice the bound; median |update| / |weight| '
+              f'{sr.update_scale(ref):.1e}; max |update - float64 update| / |update| at the median row '
+              f'{float(((upd - want).abs().sum(1) / want.abs().sum(1)).median()):.1e}')
+        assert ratio <= 1.0 and moved == 0 and vs_torch <= 1.0
 
 
 @pytest.mark.parametrize('kind', ['uniform', 'popular'])

@@ -813,6 +813,23 @@ def test_bpr_sgd_step_in_forward_equals_all_sorted(ra, N, d, B, kind):
     gi[0] = 0
     rel_close(it1.cpu(), (iw.to(DEV) - lr * gi).cpu(), rtol=2e-4, atol=1e-6)
     rel_close(l1.cpu(), ref.detach().cpu(), rtol=1e-5)
+    # the UPDATE of BOTH tables and both forms (the comparison above judges the item weight at 10 times the median update, the
+    # user side only as the same code twice): against the float64 step within the end-to-end bound of tests/sgd_referee.py on
+    # every element of every touched row, no other row moved; and against torch's fp32 update within twice that bound
+    import sgd_referee as sr
+    iwd, uwd = iw.to(DEV), uw.to(DEV)
+    gu = user_r.grad.clone()
+    gu[0] = 0
+    c = sr.coefficients(iwd, uwd, uid, pos, i0)
+    allow, _ = sr.torch_sigmoid_allowance(iwd.device, B, n)
+    refs = sr.end_to_end(iwd, uwd, uid, pos, i0, lr, c, allow)
+    for form, tabs in (('all-sorted', (it0, us0)), ('in-forward', (it1, us1))):
+        for ref, got, start, theirs in zip(refs, tabs, (iwd, uwd), (iwd - lr * gi, uwd - lr * gu)):
+            ratio, moved = sr.judge(ref, got, start)
+            r = ref['rows']
+            vs_torch = float((((got[r].double() - ref['w0']) - (theirs[r].double() - ref['w0'])).abs() / (2 * ref['tol'])).max())
+            print(f'{form}: update against float64: error / bound {ratio:.3f}, against torch fp32 {vs_torch:.3f} of twice the bound')
+            assert ratio <= 1.0 and moved == 0 and vs_torch <= 1.0, form
 
 
 @pytest.mark.parametrize('kind', ['uniform', 'popular'])

@@ -334,7 +334,14 @@ def test_sgd_step_headline_shape_properties(ra):
     the user elements, ABI 11) at BASELINE configs[1]'s own size -- N = 1e7 + 1, U = 1e6 + 1, B = 65 536, n = 64, popularity
     sampler: the negatives == torch's stream (``searchsorted(table, rand)``, sampler.py:246-247), loss == the plain forward's on the
     same weights, every touched row moved and no other, rows with ONE element == row - lr * d * q exactly as the all-sorted form
-    computes it, user rows == the all-sorted form's bit for bit (same sorted order, same chunking), run-to-run bit equality."""
+    computes it, user rows == the all-sorted form's bit for bit (same sorted order, same chunking), run-to-run bit equality.
+    The update against the float64 referee of tests/sgd_referee.py: a seeded sample of 2048 solo and 2048 shared item rows and
+    4096 user rows (the planted duplicates among them), in both forms, every element within Stage A and within the
+    end-to-end bound.  This test keeps its rate, lr = 0.046 B, so the update-scale assertion here is 1e-4 of the weight (the
+    other cases, at lr = c B with c >= 0.5: 1e-3); that is still thousands of u, the unit of the bounds.
+    Measured on an MI355X, error / bound, the same in both forms: Stage A items 0.498, users 0.497; end to end items 0.498, users
+    0.316 (runs of up to 7 elements in the sample; sigmoid allowance 4.85 u = twice torch's 2.43 u; median |update| / |weight| items
+    4.5e-04, users 2.3e-02)."""
     N, U, d, B, n, lr = 10_000_001, 1_000_001, 128, 65536, 64, 3000.0      # (BPRLoss is a mean over B * n terms: lr ~ 0.05 per sample)
     g = torch.Generator(device=DEV).manual_seed(11)
     iw0 = torch.empty(N, d, device=DEV).normal_(0, 0.1, generator=g)
@@ -382,3 +389,48 @@ def test_sgd_step_headline_shape_properties(ra):
     um[uid] = True
     um[0] = False
     assert torch.equal((us1 != uw0).any(1), um)
+    # The update itself against the float64 referee of tests/sgd_referee.py: a seeded sample of 2048 solo and 2048 shared item rows
+    # and 4096 user rows (the planted duplicates among them), both forms, every element within Stage A (the kernel's own
+    # coefficients: the plain forward on the start weights writes what the step's forward wrote) and within the end-to-end
+    # bound (float64 coefficients; float64 rows for the sample only).
+    import sgd_referee as sr
+    from test_gpu_adam_rows import _bpr_referee_inputs
+    del res, it2, us2
+    dpos, dneg, qgrad = _bpr_referee_inputs(ra, iw0, uw0, n, uid, pos, i1)
+    gs = torch.Generator(device=DEV).manual_seed(99)
+    one, many = solo.nonzero().view(-1), (cnt > 1).nonzero().view(-1)
+    many = many[many != 0]
+    rows = torch.cat([one[torch.randperm(one.numel(), device=DEV, generator=gs)[:2048]],
+                      many[torch.randperm(many.numel(), device=DEV, generator=gs)[:2048]]])
+    urows = um.nonzero().view(-1)
+    urows = torch.cat([uid[:64].unique(), urows[torch.randperm(urows.numel(), device=DEV, generator=gs)[:4096]]]).unique()
+    it_a, us_a = sr.item_update(iw0, uw0, uid, pos, i1, dpos, dneg, lr, rows=rows), sr.user_update(uw0, uid, qgrad, lr, rows=urows)
+    assert it_a['rows'].numel() == 4096 and int((it_a['K'] > 1).sum()) == 2048 and us_a['rows'].numel() >= 4096 and int(us_a['K'].max()) > 1
+    assert sr.query_grad_ratio(iw0, pos[:4096], i1[:4096], dpos[:4096], dneg[:4096], qgrad[:4096]) <= 1.0
+    c64 = sr.coefficients(iw0, uw0, uid, pos, i1)
+    allow, torch_max = sr.torch_sigmoid_allowance(iw0.device, B, n)
+    it_e, us_e = sr.end_to_end(iw0, uw0, uid, pos, i1, lr, c64, allow, item_rows=rows, user_rows=urows)
+    si, su = sr.update_scale(it_e), sr.update_scale(us_e)
+    print(f'headline: median |update| / |weight| items {si:.1e} users {su:.1e}')
+    assert si > 1e-4 and su > 1e-4          # (this test's rate, lr = 0.046 B: thousands of u, the bounds' unit)
+    assert abs(float(l1) - c64['loss']) <= 1e-5 * abs(c64['loss'])
+
+    def judged(form, a_item, a_user, ti, tu):
+        ratios = [sr.bound_ratio(a_item, ti), sr.bound_ratio(a_user, tu), sr.bound_ratio(it_e, ti), sr.bound_ratio(us_e, tu)]
+        print(f'headline {form}: error / bound  Stage A items {ratios[0]:.3f} users {ratios[1]:.3f} | end to end items {ratios[2]:.3f} users '
+              f'{ratios[3]:.3f} (K max {int(it_a["K"].max())}; sigmoid allowance {allow:.2f} u = twice torch\'s {torch_max:.2f} u)')
+        assert all(v <= 1.0 for v in ratios), (form, ratios)          # (not max(): a NaN ratio must fail)
+
+    judged('all-sorted', it_a, us_a, it0, us0)
+    # The in-forward form's OWN coefficients: the two calls issued from the test with the argument block kept.  The all-sorted
+    # result is released first (``iw`` / ``uw`` still name it, from the loop above): this part holds the start table and two clones.
+    del it0, us0, iw, uw
+    from sgd_step_forms import step_two_calls
+    iw, uw = iw0.clone(), uw0.clone()
+    torch.manual_seed(5)
+    l3, i3, own = step_two_calls(ra, iw, uw, n, lr, uid, pos, ps, None)
+    assert torch.equal(i3, i1) and torch.equal(l3, l1) and torch.equal(iw, it1) and torch.equal(uw, us1)
+    del iw, uw
+    assert sr.query_grad_ratio(iw0, pos[:4096], i1[:4096], own['dpos'][:4096], own['dneg'][:4096], own['query_grad'][:4096]) <= 1.0
+    judged('in-forward', sr.item_update(iw0, uw0, uid, pos, i1, own['dpos'], own['dneg'], lr, rows=rows),
+           sr.user_update(uw0, uid, own['query_grad'], lr, rows=urows), it1, us1)
