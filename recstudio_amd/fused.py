@@ -579,3 +579,42 @@ class FusedBPRAdam:
             ones = torch.ones(M, 1, dtype=torch.float32, device=self.iw.device)
             ops.adam_rows_presorted(self.uw, st['um'], st['uv'], out['query_grad'], ticket['ws_user'], M, 1, ones, pad_row=0, **hp)
         return out['loss'], out['neg_ids']
+
+
+class BPRSGDStep:
+    """``fit``'s whole step for ``train.fused_optimizer: 'sgd'``: calling it with a batch is one ``bpr_sgd_step`` on the batch's
+    user and item columns -> loss; ``stepper`` is the ``PrefetchedBPRSGD`` that ``fit`` drives one batch ahead instead, or None."""
+
+    def __init__(self, item_weight, user_weight, num_neg, lr, sampler, fuid, fiid, lookahead):
+        self.tables, self.num_neg, self.lr, self.sampler = (item_weight, user_weight), num_neg, lr, sampler
+        self.fuid, self.fiid = fuid, fiid
+        self.stepper = PrefetchedBPRSGD(item_weight, user_weight, num_neg, lr, sampler) if lookahead else None
+
+    def __call__(self, batch):
+        return bpr_sgd_step(*self.tables, self.num_neg, self.lr, user_ids=batch[self.fuid], pos_ids=batch[self.fiid],
+                            sampler=self.sampler)[0]
+
+    def set_lr(self, new):
+        self.lr = float(new)
+        if self.stepper is not None:
+            self.stepper.set_lr(new)
+
+
+class BPRAdamStep:
+    """The same for ``train.fused_optimizer: 'adam'`` over one ``FusedBPRAdam``; with ``lookahead`` it is its own ``stepper``."""
+
+    def __init__(self, item_weight, user_weight, num_neg, lr, sampler, fuid, fiid, lookahead):
+        self.opt = FusedBPRAdam(item_weight, user_weight, lr=lr)
+        self.num_neg, self.sampler, self.fuid, self.fiid, self.lookahead = num_neg, sampler, fuid, fiid, lookahead
+        self.step = self.opt.step_prepared
+
+    stepper = property(lambda self: self if self.lookahead else None)
+
+    def __call__(self, batch):
+        return self.opt.step(self.num_neg, user_ids=batch[self.fuid], pos_ids=batch[self.fiid], sampler=self.sampler)[0]
+
+    def prepare(self, user_ids, pos_ids):
+        return self.opt.prepare(self.num_neg, user_ids=user_ids, pos_ids=pos_ids, sampler=self.sampler)
+
+    def set_lr(self, new):
+        self.opt.lr = float(new)

@@ -10,12 +10,6 @@ and output dict layout (:142-192), ``sampling`` / ``_sample`` for ``method='none
 ``topk`` (:374-397), ``training_step`` / ``validation_step`` / ``test_step`` / ``_test_step``
 (:399-431), ``fit`` / ``evaluate`` and the config keys read on the path.  The train/eval loop around
 it is a minimal compatible one (the reference's Recommender loop is out of scope).
-
-Dispatch rule (mirrors the reference's own check at baseretriever.py:122): the fused kernels are
-used when the item tower is a plain ``nn.Embedding`` over the item id, the scorer is exactly
-InnerProductScorer / CosineScorer, the sampler exactly UniformSampler / PopularSamplerModel (or None
-for full-score losses) and ``sampling_method == 'none'``; anything else goes through the per-plugin
-path (sampler / scorer / loss objects called one by one, like the reference does).
 """
 import copy
 import inspect
@@ -31,7 +25,7 @@ from . import _native as nat
 from . import eval as rs_eval
 from . import ops
 from .dataset import SeqDataset, TripletDataset
-from .fused import fused_bpr_loss, fused_ssm_loss, retriever_scores
+from .fused import BPRAdamStep, BPRSGDStep, fused_bpr_loss, fused_ssm_loss, retriever_scores
 from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, PairwiseLoss, PointwiseLoss, SampledSoftmaxLoss,
                         SoftmaxLoss)
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
@@ -111,27 +105,71 @@ def _init_weights(module, method):
     """recstudio/model/init.py: xavier_normal / xavier_uniform / normal(0.02); the padding row is zeroed."""
     if isinstance(module, torch.nn.Embedding) and module.weight.is_meta:
         return          # a sharded catalog: its rows are drawn on the owners' devices (_device_init_block)
-    if isinstance(module, torch.nn.Embedding):
+    if isinstance(module, (torch.nn.Embedding, torch.nn.Linear)):
         if method == 'xavier_normal':
             torch.nn.init.xavier_normal_(module.weight.data)
         elif method == 'xavier_uniform':
             torch.nn.init.xavier_uniform_(module.weight.data)
         else:
             module.weight.data.normal_(mean=0.0, std=0.02)
-        if module.padding_idx is not None:
-            torch.nn.init.constant_(module.weight.data[module.padding_idx], 0.)
-    elif isinstance(module, torch.nn.Linear):
-        if method == 'xavier_normal':
-            torch.nn.init.xavier_normal_(module.weight.data)
-        elif method == 'xavier_uniform':
-            torch.nn.init.xavier_uniform_(module.weight.data)
-        else:
-            module.weight.data.normal_(mean=0.0, std=0.02)
-        if module.bias is not None:
+        if isinstance(module, torch.nn.Linear) and module.bias is not None:
             torch.nn.init.constant_(module.bias.data, 0)
+        elif getattr(module, 'padding_idx', None) is not None:
+            torch.nn.init.constant_(module.weight.data[module.padding_idx], 0.)
     elif isinstance(module, torch.nn.LayerNorm):
         module.bias.data.zero_()
         module.weight.data.fill_(1.0)
+
+
+def _stock_forward(scorer, sampler, item_embedding, n_item_fields, sampling_method, neg_count, **train_only):
+    """Dispatch rule (mirrors the reference's own check at baseretriever.py:122), on plain values: the fused kernels are used
+    when the item tower is a plain ``nn.Embedding`` over the item id, the scorer's TYPE is exactly one of the stock scorers, the
+    sampler's exactly UniformSampler / PopularSamplerModel (None: no sampler, full-score losses) and ``sampling_method`` is
+    'none'; anything else goes through the per-plugin path (sampler / scorer / loss objects called one by one, like the
+    reference does).  ``train_only``: what only ``_stock_train_path`` looks at."""
+    return (item_embedding and n_item_fields == 1 and scorer in (InnerProductScorer, CosineScorer, EuclideanScorer)
+            and (sampler is None or sampler in (UniformSampler, PopularSamplerModel)) and sampling_method == 'none'
+            and not isinstance(neg_count, (list, tuple)))
+
+
+def _stock_train_path(loss, dim, fused_ssm=True, fused_full_softmax=True, **fwd):
+    """The fused training path of a stock configuration, on plain values (``fwd``: ``_stock_forward``'s; ``dim``: the width of
+    an nn.Embedding item tower): 'bpr' / 'ssm' -- stock BPRLoss / SampledSoftmaxLoss on whole 64-negative tiles, one launch --,
+    'full_softmax' -- stock SoftmaxLoss without the [B, N] score matrix --, or None: the per-plugin path."""
+    ip, n = fwd['scorer'] is InnerProductScorer, fwd['neg_count']
+    if fwd['sampler'] is None:
+        full = (loss is SoftmaxLoss and ip and fwd['item_embedding'] and fwd['n_item_fields'] == 1 and dim <= 128
+                and fused_full_softmax)
+        return 'full_softmax' if full else None
+    if not (_stock_forward(**fwd) and ip and n and n % 64 == 0):
+        return None
+    if loss is SampledSoftmaxLoss and dim in (32, 64, 128, 256) and fused_ssm:
+        return 'ssm'
+    return 'bpr' if loss is BPRLoss else None
+
+
+def _stand_in_optimizer(lr):
+    """Carries a learning rate and nothing else: the reference's scheduler objects drive it when the update runs in the
+    kernels, and the rate they set is handed to the kernels after every epoch."""
+    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=lr)
+    opt.step()                                   # (a no-op; the schedulers warn when they step first)
+    return opt
+
+
+def _one_ahead(batches, step, prepare=None):
+    """``[step(b, prepare(b)) for b in batches]`` with the prepare calls issued one batch ahead: prepare(b0), prepare(b1),
+    step(b0), prepare(b2), step(b1), ..., step(b_last); they consume the generator in batch order, so the draws are those of
+    the plain sequence.  ``prepare`` None: no look-ahead, every ticket is None."""
+    if prepare is None:
+        return [step(batch, None) for batch in batches]
+    out, ticket = [], None
+    for k, (batch, batch_next) in enumerate(_with_next(batches)):
+        if k == 0:
+            ticket = prepare(batch)
+        ticket_next = prepare(batch_next) if batch_next is not None else None
+        out.append(step(batch, ticket))
+        ticket = ticket_next
+    return out
 
 
 class BaseRetriever(torch.nn.Module):
@@ -257,53 +295,57 @@ class BaseRetriever(torch.nn.Module):
             self.item_vector = item_vector
 
     # ------------------------------------------------------------------ forward
+    def _stock_values(self):
+        """What ``_stock_forward`` / ``_stock_train_path`` decide on."""
+        tr, embedding = self.config['train'], isinstance(self.item_encoder, torch.nn.Embedding)
+        return dict(loss=type(self.loss_fn), scorer=type(self.score_func), item_embedding=embedding,
+                    sampler=None if self.sampler is None else type(self.sampler), neg_count=getattr(self, 'neg_count', None),
+                    n_item_fields=len(getattr(self, 'item_fields', ())), sampling_method=tr.get('sampling_method', 'none'),
+                    dim=self.item_encoder.weight.shape[1] if embedding else None, fused_ssm=tr.get('fused_ssm', True),
+                    fused_full_softmax=tr.get('fused_full_softmax', True))
+
     def _fused_ok(self):
-        return (isinstance(self.item_encoder, torch.nn.Embedding) and len(self.item_fields) == 1
-                and type(self.score_func) in (InnerProductScorer, CosineScorer, EuclideanScorer)
-                and (self.sampler is None or type(self.sampler) in (UniformSampler, PopularSamplerModel))
-                and self.config['train'].get('sampling_method', 'none') == 'none'
-                and not isinstance(getattr(self, 'neg_count', None), (list, tuple)))
+        return _stock_forward(**self._stock_values())
+
+    def _fused_train_path(self, batch=None):
+        """'bpr' | 'ssm' | 'full_softmax' | None: the fused training path this model (and, if given, this batch) takes."""
+        path = _stock_train_path(**self._stock_values())
+        return path if batch is None or batch[self.fiid].dim() == 1 else None
+
+    def _query_source(self, qfeat, gather_in_kernel=True):
+        """For the fused kernels: (user table, ids) when the kernel can gather the user rows itself, else (encoded queries, None)."""
+        if gather_in_kernel and isinstance(self.query_encoder, torch.nn.Embedding) and isinstance(qfeat, torch.Tensor) \
+                and qfeat.dim() == 1:
+            return self.query_encoder.weight, qfeat
+        return self.query_encoder(qfeat), None
 
     def forward(self, batch: Dict, full_score: bool = False, return_query: bool = False, return_item: bool = False,
                 return_neg_item: bool = False, return_neg_id: bool = False):
-        if not self._fused_ok():
+        if self.sampler is None or not self._fused_ok():      # (without a sampler there is nothing to fuse: one scorer call)
             return self._forward_plugins(batch, full_score, return_query, return_item, return_neg_item, return_neg_id)
         output = {}
         pos_items = self._get_item_feat(batch)
         cosine = self.score_func.cosine      # False / True / rsa_score_mode of the Euclidean scorer
         query = None
-        if self.sampler is not None:
-            if self.neg_count is None:
-                raise ValueError('`negative_count` value is required when `sampler` is not none.')
-            qfeat = self._get_query_feat(batch)
-            if isinstance(self.query_encoder, torch.nn.Embedding) and isinstance(qfeat, torch.Tensor) \
-                    and qfeat.dim() == 1 and pos_items.dim() == 1 and not return_query:
-                qsrc, qidx = self.query_encoder.weight, qfeat          # user-row gather fused into the kernel
-            else:
-                query = self.query_encoder(qfeat)
-                qsrc, qidx = query.reshape(-1, query.shape[-1]), None
-            lead = tuple(pos_items.shape)
-            score, neg_ids = retriever_scores(
-                self.item_encoder.weight, qsrc, self.neg_count, query_index=qidx, pos_ids=pos_items.reshape(-1),
-                sampler=self.sampler, cosine=cosine, mask_pad_pos=pos_items.dim() > 1,
-                sparse_grad=self.config['train'].get('sparse_grad', False))
-            n = self.neg_count
-            output['score'] = {
-                'pos_score': score['pos_score'].view(lead), 'log_pos_prob': score['log_pos_prob'].view(lead).detach(),
-                'neg_score': score['neg_score'].view(*lead, n), 'log_neg_prob': score['log_neg_prob'].view(*lead, n).detach()}
-            neg_ids = neg_ids.view(*lead, n)
-            if return_neg_item:
-                output['neg_item'] = self.item_encoder(neg_ids)
-            if return_neg_id:
-                output['neg_id'] = neg_ids
-        else:
-            query = self.query_encoder(self._get_query_feat(batch))
-            pos_score = self.score_func(query, self.item_encoder(pos_items))
-            if batch[self.fiid].dim() > 1:
-                pos_score = pos_score.masked_fill(batch[self.fiid] == 0, -float('inf'))
-            output['score'] = {'pos_score': pos_score}
-            if full_score:
-                output['score']['all_score'] = self.score_func(query, self._get_item_vector())
+        if self.neg_count is None:
+            raise ValueError('`negative_count` value is required when `sampler` is not none.')
+        qsrc, qidx = self._query_source(self._get_query_feat(batch), pos_items.dim() == 1 and not return_query)
+        if qidx is None:
+            query, qsrc = qsrc, qsrc.reshape(-1, qsrc.shape[-1])
+        lead = tuple(pos_items.shape)
+        score, neg_ids = retriever_scores(
+            self.item_encoder.weight, qsrc, self.neg_count, query_index=qidx, pos_ids=pos_items.reshape(-1),
+            sampler=self.sampler, cosine=cosine, mask_pad_pos=pos_items.dim() > 1,
+            sparse_grad=self.config['train'].get('sparse_grad', False))
+        n = self.neg_count
+        output['score'] = {
+            'pos_score': score['pos_score'].view(lead), 'log_pos_prob': score['log_pos_prob'].view(lead).detach(),
+            'neg_score': score['neg_score'].view(*lead, n), 'log_neg_prob': score['log_neg_prob'].view(*lead, n).detach()}
+        neg_ids = neg_ids.view(*lead, n)
+        if return_neg_item:
+            output['neg_item'] = self.item_encoder(neg_ids)
+        if return_neg_id:
+            output['neg_id'] = neg_ids
         if return_query:
             output['query'] = query
         if return_item:
@@ -502,39 +544,18 @@ class BaseRetriever(torch.nn.Module):
 
     # ------------------------------------------------------------------ steps
     def training_step(self, batch):
-        # single-launch path: stock BPRLoss on the fused kernels with a whole number of 64-negative tiles
-        if (type(self.loss_fn) is BPRLoss and self.sampler is not None and self._fused_ok()
-                and type(self.score_func) is InnerProductScorer and self.neg_count and self.neg_count % 64 == 0
-                and batch[self.fiid].dim() == 1):
-            qfeat = self._get_query_feat(batch)
-            if isinstance(self.query_encoder, torch.nn.Embedding) and isinstance(qfeat, torch.Tensor) and qfeat.dim() == 1:
-                qsrc, qidx = self.query_encoder.weight, qfeat
-            else:
-                qsrc, qidx = self.query_encoder(qfeat), None
-            loss, _ = fused_bpr_loss(self.item_encoder.weight, qsrc, self.neg_count, query_index=qidx,
-                                     pos_ids=batch[self.fiid], sampler=self.sampler,
-                                     sparse_grad=self.config['train'].get('sparse_grad', False))
+        path = self._fused_train_path(batch)
+        if path in ('bpr', 'ssm'):
+            # single launch: stock BPRLoss / SampledSoftmaxLoss (configs[2]) on the fused kernels with a whole number of
+            # 64-negative tiles; the SampledSoftmax logsumexp over the positive and the negatives of a query is carried through
+            # its tiles by one wave, the query gradient is accumulated in the forward
+            qsrc, qidx = self._query_source(self._get_query_feat(batch))
+            fused_loss = fused_bpr_loss if path == 'bpr' else fused_ssm_loss
+            loss, _ = fused_loss(self.item_encoder.weight, qsrc, self.neg_count, query_index=qidx, pos_ids=batch[self.fiid],
+                                 sampler=self.sampler, sparse_grad=self.config['train'].get('sparse_grad', False))
             return loss
-        # the same for stock SampledSoftmaxLoss (configs[2]): the logsumexp over the positive and the negatives of a
-        # query is carried through its tiles by one wave, the query gradient is accumulated in the forward
-        if (type(self.loss_fn) is SampledSoftmaxLoss and self.sampler is not None and self._fused_ok()
-                and type(self.score_func) is InnerProductScorer and self.neg_count and self.neg_count % 64 == 0
-                and batch[self.fiid].dim() == 1 and self.item_encoder.weight.shape[1] in (32, 64, 128, 256)
-                and self.config['train'].get('fused_ssm', True)):
-            qfeat = self._get_query_feat(batch)
-            if isinstance(self.query_encoder, torch.nn.Embedding) and isinstance(qfeat, torch.Tensor) and qfeat.dim() == 1:
-                qsrc, qidx = self.query_encoder.weight, qfeat
-            else:
-                qsrc, qidx = self.query_encoder(qfeat), None
-            loss, _ = fused_ssm_loss(self.item_encoder.weight, qsrc, self.neg_count, query_index=qidx,
-                                     pos_ids=batch[self.fiid], sampler=self.sampler,
-                                     sparse_grad=self.config['train'].get('sparse_grad', False))
-            return loss
-        # full softmax without the [B, N] score matrix: stock SoftmaxLoss over an nn.Embedding catalog
-        if (type(self.loss_fn) is SoftmaxLoss and self.sampler is None and type(self.score_func) is InnerProductScorer
-                and isinstance(self.item_encoder, torch.nn.Embedding) and len(self.item_fields) == 1
-                and self.item_encoder.weight.shape[1] <= 128 and batch[self.fiid].dim() == 1
-                and self.config['train'].get('fused_full_softmax', True)):
+        if path == 'full_softmax':
+            # full softmax without the [B, N] score matrix: stock SoftmaxLoss over an nn.Embedding catalog
             output = self.forward(batch, False, return_query=True)
             lse = full_lse(output['query'], self.item_encoder.weight)
             return (lse - output['score']['pos_score']).mean()       # loss_func.py:39-47, first branch
@@ -543,14 +564,15 @@ class BaseRetriever(torch.nn.Module):
         score['label'] = batch[self.frating]
         return self.loss_fn(**score)
 
-    def validation_step(self, batch):
+    def _cutoffs(self):
         cutoff = self.config['eval']['cutoff']
-        cutoff = cutoff[0] if isinstance(cutoff, list) else cutoff
-        return self._test_step(batch, self.config['eval']['val_metrics'], [cutoff])
+        return cutoff if isinstance(cutoff, list) else [cutoff]
+
+    def validation_step(self, batch):
+        return self._test_step(batch, self.config['eval']['val_metrics'], self._cutoffs()[:1])
 
     def test_step(self, batch):
-        cutoff = self.config['eval']['cutoff']
-        return self._test_step(batch, self.config['eval']['test_metrics'], cutoff if isinstance(cutoff, list) else [cutoff])
+        return self._test_step(batch, self.config['eval']['test_metrics'], self._cutoffs())
 
     def _test_step(self, batch, metric, cutoffs):
         rank_m = rs_eval.get_rank_metrics(metric)
@@ -588,13 +610,11 @@ class BaseRetriever(torch.nn.Module):
 
     def _get_optimizer(self):
         tr = self.config['train']
-        name, lr, wd = tr['learner'].lower(), tr['learning_rate'], tr['weight_decay']
+        name, lr = tr['learner'].lower(), tr['learning_rate']
         params = [p for p in self.parameters() if p.requires_grad]
         if tr.get('sparse_grad', False):
             return torch.optim.SparseAdam(params, lr=lr) if name == 'adam' else torch.optim.SGD(params, lr=lr)
-        table = {'adam': torch.optim.Adam, 'sgd': torch.optim.SGD, 'adagrad': torch.optim.Adagrad,
-                 'rmsprop': torch.optim.RMSprop}
-        return table.get(name, torch.optim.Adam)(params, lr=lr, weight_decay=wd)
+        return self._make_optimizer(params)
 
     def _get_scheduler(self, optimizer):
         """recommender.py:476-494: ``train.scheduler`` = 'exponential' (gamma 0.98) | 'onplateau' | None, stepped once
@@ -797,26 +817,33 @@ class BaseRetriever(torch.nn.Module):
             optimizer = self._make_optimizer(params) if params else None
         if not fused:
             self.item_encoder.weight.grad = trainer.item_grad_local       # the exchange accumulates into the block's .grad
-        sched_opt = optimizer
-        if fused and embed_tower and tr.get('scheduler'):      # no torch optimizer at all: a stand-in carries the rate
-            sched_opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=lr)
-            sched_opt.step()                                   # (a no-op; the schedulers warn when they step first)
-        scheduler = self._get_scheduler(sched_opt)
+        scheduler = self._get_scheduler(_stand_in_optimizer(lr) if fused and embed_tower and tr.get('scheduler') else optimizer)
         sh['trainer'] = trainer
         trainer.table.defer_overflow = True          # report a capacity overflow after the step instead of raising inside it
         if sh['tower_rows'] is not None:
             sh['tower_rows'].bind(trainer)
-        val_metrics = self.config['eval']['val_metrics']
-        cutoff = self.config['eval']['cutoff']
-        cutoff0 = cutoff[0] if isinstance(cutoff, list) else cutoff
-        self.val_metric = f"{(val_metrics[0] if isinstance(val_metrics, list) else val_metrics)}@{cutoff0}"
         on_gpu = device.type == 'cuda'
-        best, best_state, bad = None, None, 0
-        self.train_losses, self.history = [], []
-        for epoch in range(tr['epochs']):
-            t0 = time.time()
-            self.train()
-            losses = []
+        self.train_losses = []
+        prepare = lambda batch: trainer.prepare_step(self._get_query_feat(batch), batch[self.fiid])      # noqa: E731
+
+        def step(batch, ticket):
+            if optimizer is not None:
+                optimizer.zero_grad(set_to_none=False)
+            loss = trainer.training_step(self._get_query_feat(batch), batch[self.fiid], batch[self.frating], ticket=ticket)
+            if optimizer is not None:
+                if tr['grad_clip_norm'] is not None:
+                    self._clip_grad_norm_sharded(params, tr['grad_clip_norm'], dist)
+                optimizer.step()
+            # an id distribution that outgrew the calibrated segment capacity: the poll (every rank sees the job-wide
+            # sticky count at the same step) reports it HERE, after the whole step -- the steps in which elements were
+            # dropped updated nothing (their scale was 0 on the device), the step the lagging poll landed in is a healthy
+            # one and has run to its end, the capacity is recalibrated on the next step; carry on
+            msg = trainer.table.take_overflow()
+            if msg:
+                self.logger.warning(msg)
+            return loss.detach().reshape(1)
+
+        def train_epoch():
             # train.shard_lookahead: the weight-independent half of the NEXT batch's step (negatives, routing, key exchange,
             # the owner's sorts) is issued on a second stream before the current batch is stepped (ShardedRetriever.prepare_step)
             ahead = bool(tr.get('shard_lookahead', False)) and trainer.can_prepare()
@@ -833,53 +860,52 @@ class BaseRetriever(torch.nn.Module):
             else:
                 loader = train_data.train_loader(batch_size=tr['batch_size'], shuffle=True, drop_last=False, ddp=True,
                                                  rank=rank, world=world)
-            ticket = None
             with _above_second_stream(ahead and on_gpu, device, self._shard):
-                for batch, batch_next in _with_next(self._prepared_batches(loader, device)):
-                    if ahead and ticket is None:
-                        ticket = trainer.prepare_step(self._get_query_feat(batch), batch[self.fiid])
-                    ticket_next = trainer.prepare_step(self._get_query_feat(batch_next), batch_next[self.fiid]) \
-                        if ahead and batch_next is not None else None
-                    if optimizer is not None:
-                        optimizer.zero_grad(set_to_none=False)
-                    loss = trainer.training_step(self._get_query_feat(batch), batch[self.fiid], batch[self.frating], ticket=ticket)
-                    ticket = ticket_next
-                    if optimizer is not None:
-                        if tr['grad_clip_norm'] is not None:
-                            self._clip_grad_norm_sharded(params, tr['grad_clip_norm'], dist)
-                        optimizer.step()
-                    losses.append(loss.detach().reshape(1))
-                    # an id distribution that outgrew the calibrated segment capacity: the poll (every rank sees the job-wide
-                    # sticky count at the same step) reports it HERE, after the whole step -- the steps in which elements were
-                    # dropped updated nothing (their scale was 0 on the device), the step the lagging poll landed in is a healthy
-                    # one and has run to its end, the capacity is recalibrated on the next step; carry on
-                    msg = trainer.table.take_overflow()
-                    if msg:
-                        self.logger.warning(msg)
+                losses = _one_ahead(self._prepared_batches(loader, device), step, prepare if ahead else None)
             step_losses = torch.cat(losses)                     # this rank's shares of the global mean losses
-            dist.all_reduce(step_losses)
+            dist.all_reduce(step_losses)      # (the all-reduced loss / metric: the same scheduler decision on every rank)
             self.train_losses.append(step_losses.cpu())
-            log = {'epoch': epoch, 'train_loss': float(step_losses.mean()), 'train_time': time.time() - t0}
-            if val_data is not None and (epoch + 1) % self.config['eval']['val_n_epoch'] == 0:
-                log.update(self._eval_epoch(val_data, self.validation_step, device))
-                cur = log[self.val_metric]
+            return float(step_losses.mean())
+
+        validate = (lambda: self._eval_epoch(val_data, self.validation_step, device)) if val_data is not None else None
+        return self._run_epochs(train_epoch, scheduler, validate, on_lr=trainer.set_sgd_lr if fused else None,
+                                log=self.logger.info if rank == 0 else None,
+                                after_restore=lambda: setattr(table, 'item_local', self.item_encoder.weight.data))
+
+    def _run_epochs(self, train_epoch, scheduler, validate=None, on_lr=None, log=None, after_restore=None):
+        """The epoch loop of ``fit``, single-process and sharded: ``train_epoch() -> loss`` every epoch, ``validate() -> metrics``
+        every ``eval.val_n_epoch`` epochs (None: no validation data), early stopping on ``self.val_metric``, one scheduler step per
+        epoch with the new rate handed to ``on_lr``, one ``history`` entry and one ``log(line)`` per epoch (``log`` None: this
+        process does not log); at the end the best state is restored and ``after_restore()`` called.  Returns the best metric."""
+        tr, val_metrics = self.config['train'], self.config['eval']['val_metrics']
+        self.val_metric = f"{(val_metrics[0] if isinstance(val_metrics, list) else val_metrics)}@{self._cutoffs()[0]}"
+        best, best_state, bad = None, None, 0
+        self.history = []                                  # one dict per epoch: what the reference logs (recommender.py:249-270)
+        for epoch in range(tr['epochs']):
+            t0 = time.time()
+            self.train()
+            entry = {'epoch': epoch, 'train_loss': train_epoch(), 'train_time': time.time() - t0}
+            if validate is not None and (epoch + 1) % self.config['eval']['val_n_epoch'] == 0:
+                entry.update(validate())
+                cur = entry[self.val_metric]
                 better = best is None or (cur > best if tr['early_stop_mode'] == 'max' else cur < best)
                 if better:
                     best, best_state, bad = cur, copy.deepcopy(self.state_dict()), 0
                 else:
                     bad += 1
-            self._step_scheduler(scheduler, log)      # (the all-reduced loss / metric: the same decision on every rank)
-            if fused and scheduler is not None:
-                trainer.set_sgd_lr(log['lr'])
-            self.logged_metrics = log
-            self.history.append(dict(log))
-            if rank == 0:
-                self.logger.info(' '.join(f'{k}={v:.4f}' if isinstance(v, float) else f'{k}={v}' for k, v in log.items()))
-            if val_data is not None and bad >= tr['early_stop_patience']:
+            self._step_scheduler(scheduler, entry)
+            if on_lr is not None and scheduler is not None:
+                on_lr(entry['lr'])
+            self.logged_metrics = entry
+            self.history.append(dict(entry))
+            if log is not None:
+                log(' '.join(f'{k}={v:.4f}' if isinstance(v, float) else f'{k}={v}' for k, v in entry.items()))
+            if validate is not None and bad >= tr['early_stop_patience']:
                 break
         if best_state is not None:
             self.load_state_dict(best_state)
-            table.item_local = self.item_encoder.weight.data
+            if after_restore is not None:
+                after_restore()
         return best
 
     def _clip_grad_norm_sharded(self, params, max_norm, dist):
@@ -925,83 +951,46 @@ class BaseRetriever(torch.nn.Module):
             val_data.use_field = train_data.use_field
         optimizer = self._get_optimizer()
         tr = self.config['train']
-        fused_step = self._fused_optimizer_step(tr)
-        sched_opt = optimizer
-        if fused_step is not None:
-            # train.scheduler with a fused optimizer: the reference's scheduler objects drive a stand-in optimizer whose
-            # learning rate is handed to the kernels after every epoch
-            sched_opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=tr['learning_rate'])
-            sched_opt.step()                                   # (a no-op; the schedulers warn when they step first)
-        scheduler = self._get_scheduler(sched_opt)
-        val_metrics = self.config['eval']['val_metrics']
-        cutoff = self.config['eval']['cutoff']
-        cutoff0 = cutoff[0] if isinstance(cutoff, list) else cutoff
-        self.val_metric = f"{(val_metrics[0] if isinstance(val_metrics, list) else val_metrics)}@{cutoff0}"
-        best, best_state, bad = None, None, 0
-        self.history = []                                  # one dict per epoch: what the reference logs (recommender.py:249-270)
-        self._fused_step = fused_step
+        fused_step = self._fused_step = self._fused_optimizer_step(tr)
+        scheduler = self._get_scheduler(_stand_in_optimizer(tr['learning_rate']) if fused_step is not None else optimizer)
         # the device-resident loader is built once: its columns are uploaded once, every epoch re-draws the order
-        dev_loader = None
-        if tr.get('device_loader', True) and hasattr(train_data, 'device_train_loader'):
-            dev_loader = train_data.device_train_loader(tr['batch_size'], shuffle=True, drop_last=False, device=device)
-        for epoch in range(tr['epochs']):
-            t0 = time.time()
-            self.train()
-            self._update_item_vector()
-            if self.sampler is not None:
-                self.sampler.update(item_embs=self.item_vector)                 # recommender.py:564-570
-            losses = []
-            if dev_loader is not None:
-                loader = dev_loader
-            else:
-                loader = train_data.train_loader(batch_size=tr['batch_size'], shuffle=True, drop_last=False)
-            if getattr(fused_step, 'stepper', None) is not None:
-                # one batch of look-ahead: the next step's negatives are drawn and sorted on a side stream while this
-                # step's forward and apply passes run (fused.PrefetchedBPRSGD; same weights bit for bit)
-                stepper, ticket = fused_step.stepper, None
-                for batch in loader:
-                    batch = self._to_device(batch, device)
-                    nxt = stepper.prepare(batch[self.fuid], batch[self.fiid])
-                    if ticket is not None:
-                        losses.append(stepper.step(ticket)[0])
-                    ticket = nxt
-                if ticket is not None:
-                    losses.append(stepper.step(ticket)[0])
-                loader = ()
-            for batch in loader:
-                batch = self._to_device(batch, device)
+        dev_loader = train_data.device_train_loader(tr['batch_size'], shuffle=True, drop_last=False, device=device) \
+            if tr.get('device_loader', True) and hasattr(train_data, 'device_train_loader') else None
+        prepare = None
+        if fused_step is not None and fused_step.stepper is not None:
+            # one batch of look-ahead: the next step's negatives are drawn and sorted on a side stream while this
+            # step's forward and apply passes run (fused.PrefetchedBPRSGD; same weights bit for bit)
+            stepper = fused_step.stepper
+            prepare = lambda batch: stepper.prepare(batch[self.fuid], batch[self.fiid])      # noqa: E731
+            step = lambda batch, ticket: stepper.step(ticket)[0]                               # noqa: E731
+        else:
+            def step(batch, ticket):
                 if fused_step is not None and batch[self.fiid].dim() == 1:
-                    losses.append(fused_step(batch))        # forward + loss + optimizer update in the kernels
-                    continue
+                    return fused_step(batch)        # forward + loss + optimizer update in the kernels
                 optimizer.zero_grad()
                 loss = self.training_step(batch)
                 loss.backward()
                 if tr['grad_clip_norm'] is not None:
                     torch.nn.utils.clip_grad_norm_(self.parameters(), tr['grad_clip_norm'])
                 optimizer.step()
-                losses.append(loss.detach())
-            log = {'epoch': epoch, 'train_loss': float(torch.stack(losses).mean()), 'train_time': time.time() - t0}
-            if val_data is not None and (epoch + 1) % self.config['eval']['val_n_epoch'] == 0:
-                t1 = time.time()
-                log.update(self._eval_epoch(val_data, self.validation_step, device))
-                log['valid_time'] = time.time() - t1              # the reference logs both (recommender.py:262-266)
-                cur = log[self.val_metric]
-                better = best is None or (cur > best if tr['early_stop_mode'] == 'max' else cur < best)
-                if better:
-                    best, best_state, bad = cur, copy.deepcopy(self.state_dict()), 0
-                else:
-                    bad += 1
-            self._step_scheduler(scheduler, log)
-            if fused_step is not None and scheduler is not None:
-                fused_step.set_lr(log['lr'])
-            self.logged_metrics = log
-            self.history.append(dict(log))
-            self.logger.info(' '.join(f'{k}={v:.4f}' if isinstance(v, float) else f'{k}={v}' for k, v in log.items()))
-            if val_data is not None and bad >= tr['early_stop_patience']:
-                break
-        if best_state is not None:
-            self.load_state_dict(best_state)
-        return best
+                return loss.detach()
+
+        def train_epoch():
+            self._update_item_vector()
+            if self.sampler is not None:
+                self.sampler.update(item_embs=self.item_vector)                 # recommender.py:564-570
+            loader = dev_loader if dev_loader is not None else \
+                train_data.train_loader(batch_size=tr['batch_size'], shuffle=True, drop_last=False)
+            losses = _one_ahead((self._to_device(batch, device) for batch in loader), step, prepare)
+            return float(torch.stack(losses).mean())
+
+        def validate():
+            t1 = time.time()
+            metrics = self._eval_epoch(val_data, self.validation_step, device)
+            return dict(metrics, valid_time=time.time() - t1)     # the reference logs both times (recommender.py:262-266)
+
+        return self._run_epochs(train_epoch, scheduler, validate if val_data is not None else None,
+                                on_lr=fused_step.set_lr if fused_step is not None else None, log=self.logger.info)
 
     def _fused_optimizer_step(self, tr):
         """``train.fused_optimizer: 'sgd' | 'adam'`` (default None = the reference's torch optimizer on autograd
@@ -1013,51 +1002,21 @@ class BaseRetriever(torch.nn.Module):
         kind = tr.get('fused_optimizer')
         if not kind:
             return None
-        ok = (type(self.loss_fn) is BPRLoss and self.sampler is not None and self._fused_ok()
-              and type(self.score_func) is InnerProductScorer and isinstance(self.neg_count, int) and self.neg_count % 64 == 0
-              and isinstance(self.query_encoder, torch.nn.Embedding) and self.item_encoder.weight.shape[1] in (64, 128, 256)
-              and not tr.get('weight_decay') and tr.get('grad_clip_norm') is None)
-        if not ok:
+        if not (self._fused_train_path() == 'bpr' and isinstance(self.neg_count, int)
+                and isinstance(self.query_encoder, torch.nn.Embedding) and self.item_encoder.weight.shape[1] in (64, 128, 256)
+                and not tr.get('weight_decay') and tr.get('grad_clip_norm') is None):
             raise NotImplementedError("train.fused_optimizer needs the stock BPR two-tower configuration "
                                       "(see BaseRetriever._fused_optimizer_step)")
-        from .fused import FusedBPRAdam, bpr_sgd_step
-        iw, uw, lr = self.item_encoder.weight, self.query_encoder.weight, tr['learning_rate']
-        if kind == 'sgd':
-            rate = {'lr': lr}
-
-            def sgd_step(b):
-                return bpr_sgd_step(iw, uw, self.neg_count, rate['lr'], user_ids=b[self.fuid], pos_ids=b[self.fiid],
-                                    sampler=self.sampler)[0]
-            sgd_step.stepper = None
-            if self.neg_count == 64 and tr.get('fused_prefetch', True) and self.fiid is not None:
-                from .fused import PrefetchedBPRSGD
-                sgd_step.stepper = PrefetchedBPRSGD(iw, uw, self.neg_count, lr, self.sampler)
-
-            def set_lr(new):
-                rate['lr'] = float(new)
-                if sgd_step.stepper is not None:
-                    sgd_step.stepper.set_lr(new)
-            sgd_step.set_lr = set_lr
-            return sgd_step
-        if kind == 'adam':
-            opt = FusedBPRAdam(iw, uw, lr=lr)
-
-            def adam_step(b):
-                return opt.step(self.neg_count, user_ids=b[self.fuid], pos_ids=b[self.fiid], sampler=self.sampler)[0]
-            adam_step.stepper = None
-            # (one batch of look-ahead does not pay here -- in-process A/B at the headline shape: 2.61 ms plain, 2.68 ms one
-            # batch ahead: the draw leaves the forward for the stand-alone sampler and the apply pass is the step -- so it is
-            # opt-in for the lazy-Adam step: train.fused_prefetch: 'adam')
-            if tr.get('fused_prefetch', True) == 'adam':
-                class _Ahead:      # the prepare / step pair the fit loop drives one batch ahead
-                    @staticmethod
-                    def prepare(uid, pos):
-                        return opt.prepare(self.neg_count, user_ids=uid, pos_ids=pos, sampler=self.sampler)
-                    step = staticmethod(opt.step_prepared)
-                adam_step.stepper = _Ahead
-            adam_step.set_lr = lambda new: setattr(opt, 'lr', float(new))
-            return adam_step
-        raise ValueError(f"train.fused_optimizer must be 'sgd' or 'adam', got {kind!r}")
+        if kind not in ('sgd', 'adam'):
+            raise ValueError(f"train.fused_optimizer must be 'sgd' or 'adam', got {kind!r}")
+        # look-ahead: 'sgd' only on the in-forward step (one 64-negative tile); it does not pay for lazy Adam -- in-process A/B
+        # at the headline shape: 2.61 ms plain, 2.68 ms one batch ahead: the draw leaves the forward for the stand-alone sampler
+        # and the apply pass is the step -- so there it is opt-in: train.fused_prefetch: 'adam'
+        prefetch = tr.get('fused_prefetch', True)
+        ahead = bool(self.neg_count == 64 and prefetch and self.fiid is not None) if kind == 'sgd' else prefetch == 'adam'
+        cls = BPRSGDStep if kind == 'sgd' else BPRAdamStep
+        return cls(self.item_encoder.weight, self.query_encoder.weight, self.neg_count, tr['learning_rate'], self.sampler,
+                   self.fuid, self.fiid, ahead)
 
     @torch.no_grad()
     def _eval_epoch(self, data, step, device):
