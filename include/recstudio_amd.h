@@ -153,6 +153,73 @@ int rsa_sample_popular(const rsa_popular_args* args, rsa_stream_t stream);
  * parity tests to hit exact table edges). */
 int rsa_popular_lookup(const rsa_popular_args* args, rsa_stream_t stream);
 
+/* MIDXSamplerUniform / ClusterSamplerUniform .forward and .compute_item_p -- recstudio/ann/sampler.py:308-388, :460-510:
+ * negatives from a proposal that follows the query through a k-means codebook.  n_parts = 2 (MIDX): the query's two halves
+ * q0, q1 against centres[0], centres[1]; P(k0, k1) ~ wkk[k0][k1] * exp(<q0, c0[k0]>) * exp(<q1, c1[k1]>), k0 from its marginal,
+ * k1 from the conditional, then an item uniform in bucket k0 * K + k1.  n_parts = 1 (Cluster): P(k) ~ wkk[k] * exp(<q, c[k]>).
+ * RSA_SCORE_COS: the query is divided by max(||q||, 1e-12) first.  neg_logp = the (unnormalised) logits of the chosen clusters,
+ * pos_logp[q][t] = the logits of the clusters of pos_ids[q][t] (0 for the padding id).  An empty bucket (wkk == 0) is never
+ * returned; the exact draw and tie rule: recstudio_amd/csrc/rsa_midx.hip.  Uniforms: element ((q * num_neg + j) * (n_parts + 1)
+ * + t) of ONE torch.rand(n_queries, num_neg, n_parts + 1) on the device stream ("Philox state").  num_neg = 0 with n_pos > 0 is
+ * compute_item_p on its own.  Limits: dim % 8 == 0, dim <= 256, 2 <= n_clusters <= 64. */
+typedef struct rsa_midx_args {
+  int64_t size;                /* sizeof(rsa_midx_args) */
+  const float* query;          /* [n_queries, dim] */
+  int64_t n_queries;
+  int32_t dim;
+  int32_t n_parts;             /* 2: MIDX, 1: Cluster */
+  int32_t n_clusters;          /* K */
+  int32_t score_mode;          /* RSA_SCORE_IP or RSA_SCORE_COS */
+  const float* centres;        /* [n_parts, K, dim / n_parts] */
+  const float* wkk;            /* [K, K] (MIDX) or [K] (Cluster): items per bucket */
+  const int32_t* indptr;       /* [K^n_parts + 1] bucket b holds indices[indptr[b] .. indptr[b + 1]) */
+  const int32_t* indices;      /* [n_items] item ids - 1, grouped by bucket */
+  int64_t n_items;             /* items WITHOUT the padding id */
+  const int32_t* cd0;          /* [n_items + 1] cluster + 1 of every id in part 0, 0 for the padding id */
+  const int32_t* cd1;          /* the same for part 1 (MIDX) */
+  int32_t num_neg;
+  int32_t n_pos;               /* positives per query (0: none) */
+  const int64_t* pos_ids;      /* nullable [n_queries, n_pos] */
+  const float* u_in;           /* rsa_midx_lookup: the uniforms [n_queries, num_neg, n_parts + 1] */
+  int64_t* neg_ids;            /* [n_queries, num_neg] out */
+  float* neg_logp;             /* nullable [n_queries, num_neg] out */
+  float* pos_logp;             /* [n_queries, n_pos] out */
+  float* u_out;                /* nullable out (rsa_midx_sample: the uniforms drawn) */
+  uint64_t seed, offset;       /* "Philox state" (rsa_midx_sample) */
+  uint32_t grid_threads;
+  uint32_t _pad;
+  uint64_t elem_base;
+} rsa_midx_args;
+int rsa_midx_sample(const rsa_midx_args* args, rsa_stream_t stream);
+/* The same draw for caller-supplied uniforms (the tests hit exact CDF edges with it). */
+int rsa_midx_lookup(const rsa_midx_args* args, rsa_stream_t stream);
+
+/* One assignment pass of kmeans() -- recstudio/ann/sampler.py:19-31 -- over rows [row_offset, row_offset + n_rows) of `table`
+ * (row_stride floats apart), for n_parts column groups at once; every row is read once.  normalize: rows are divided by
+ * max(||row||, 1e-12) (whole row) first.  Per part: assign[part][row] = argmin_k ||x - c[k]||^2 (lowest k on a tie),
+ * sums[part][k] = sum of the rows assigned to k, counts[part][k], loss[part] = sum of the minimal squared distances.  No
+ * [n_rows, K] matrix and no float atomics: results are bit-equal run to run.  Same limits as rsa_midx_args. */
+typedef struct rsa_kmeans_args {
+  int64_t size;                /* sizeof(rsa_kmeans_args) */
+  const float* table;
+  int64_t n_rows;
+  int64_t row_stride;          /* floats, a multiple of 4 */
+  int64_t row_offset;          /* first row (1 for an embedding table whose row 0 is the padding row) */
+  int32_t dim;
+  int32_t n_parts;
+  int32_t n_clusters;
+  int32_t normalize;
+  const float* centres;        /* [n_parts, K, dim / n_parts] */
+  int32_t* assign;             /* [n_parts, n_rows] out */
+  float* sums;                 /* [n_parts, K, dim / n_parts] out */
+  int32_t* counts;             /* [n_parts, K] out */
+  double* loss;                /* [n_parts] out */
+  void* workspace;
+  int64_t workspace_bytes;     /* >= rsa_kmeans_workspace_bytes(n_rows, dim, n_clusters) */
+} rsa_kmeans_args;
+int64_t rsa_kmeans_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_clusters);
+int rsa_kmeans_step(const rsa_kmeans_args* args, rsa_stream_t stream);
+
 /* PopularSamplerModel.compute_item_p -- recstudio/ann/sampler.py:257-258:
  * logp[i] = log(pop_prob[ids[i]]). */
 int rsa_item_logp(const float* pop_prob, int64_t n_items, const int64_t* ids, int64_t numel,

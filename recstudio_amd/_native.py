@@ -180,6 +180,28 @@ class FullscoreArgs(_Sized):
     ]
 
 
+class MidxArgs(_Sized):
+    """struct rsa_midx_args."""
+    _fields_ = [
+        ('size', c_int64), ('query', c_void_p), ('n_queries', c_int64), ('dim', c_int32), ('n_parts', c_int32),
+        ('n_clusters', c_int32), ('score_mode', c_int32), ('centres', c_void_p), ('wkk', c_void_p), ('indptr', c_void_p),
+        ('indices', c_void_p), ('n_items', c_int64), ('cd0', c_void_p), ('cd1', c_void_p), ('num_neg', c_int32), ('n_pos', c_int32),
+        ('pos_ids', c_void_p), ('u_in', c_void_p), ('neg_ids', c_void_p), ('neg_logp', c_void_p), ('pos_logp', c_void_p),
+        ('u_out', c_void_p), ('seed', c_uint64), ('offset', c_uint64), ('grid_threads', c_uint32), ('_pad', c_uint32),
+        ('elem_base', c_uint64),
+    ]
+
+
+class KmeansArgs(_Sized):
+    """struct rsa_kmeans_args."""
+    _fields_ = [
+        ('size', c_int64), ('table', c_void_p), ('n_rows', c_int64), ('row_stride', c_int64), ('row_offset', c_int64),
+        ('dim', c_int32), ('n_parts', c_int32), ('n_clusters', c_int32), ('normalize', c_int32), ('centres', c_void_p),
+        ('assign', c_void_p), ('sums', c_void_p), ('counts', c_void_p), ('loss', c_void_p), ('workspace', c_void_p),
+        ('workspace_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -187,7 +209,7 @@ STRUCTS = {
     'rsa_shard_home_args': ShardHomeArgs, 'rsa_shard_backward_args': ShardBackwardArgs,
     'rsa_shard_owner_bpr_args': ShardOwnerBprArgs, 'rsa_popular_args': PopularArgs, 'rsa_loss_args': LossArgs,
     'rsa_rows_update_args': RowsUpdateArgs, 'rsa_bpr_sgd_args': BprSgdArgs, 'rsa_seg_gather_args': SegGatherArgs,
-    'rsa_fullscore_args': FullscoreArgs,
+    'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -201,6 +223,10 @@ SIGNATURES = {
                                           c_uint32, c_uint64, c_void_p]),
     'rsa_sample_popular': (c_int, [POINTER(PopularArgs), c_void_p]),
     'rsa_popular_lookup': (c_int, [POINTER(PopularArgs), c_void_p]),
+    'rsa_midx_sample': (c_int, [POINTER(MidxArgs), c_void_p]),
+    'rsa_midx_lookup': (c_int, [POINTER(MidxArgs), c_void_p]),
+    'rsa_kmeans_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
+    'rsa_kmeans_step': (c_int, [POINTER(KmeansArgs), c_void_p]),
     'rsa_item_logp': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     'rsa_embedding_gather': (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     'rsa_fused_sample_gather_score': (c_int, [POINTER(FusedArgs), c_void_p]),

@@ -132,7 +132,8 @@ def _scratch_for(dev, raw_stream):
     return t
 
 
-def _need(t, dtype, name):
+def _need_view(t, dtype, name):
+    """The checks of ``_need`` for a tensor that the kernel reads in place through its strides (no contiguous copy)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f'{name}: expected a tensor, got {type(t)}')
     if not t.is_cuda:
@@ -140,6 +141,11 @@ def _need(t, dtype, name):
                            'there is no CPU fallback')
     if t.dtype != dtype:
         raise TypeError(f'{name}: expected {dtype}, got {t.dtype}')
+    return t
+
+
+def _need(t, dtype, name):
+    t = _need_view(t, dtype, name)
     return t if t.is_contiguous() else t.contiguous()
 
 
@@ -239,6 +245,118 @@ def item_logp(pop_prob, ids):
     ids = _need(ids, torch.int64, 'ids')
     out = torch.empty(ids.shape, dtype=torch.float32, device=ids.device)
     _launch('rsa_item_logp', ptr(pop_prob), pop_prob.numel(), ptr(ids), ids.numel(), ptr(out))
+    return out
+
+
+def _codebook_shape(centres, who):
+    """(n_parts, K, d_sub) of a stacked codebook [n_parts, K, d_sub], with the limits of rsa_midx_args checked."""
+    if centres.dim() != 3 or centres.shape[0] not in (1, 2):
+        raise ValueError(f'{who}: centres must be [n_parts (1 or 2), K, dim / n_parts], got {tuple(centres.shape)}')
+    parts, K, dsub = (int(v) for v in centres.shape)
+    dim = parts * dsub
+    if not 2 <= K <= 64:
+        raise ValueError(f'{who}: the number of clusters must be in [2, 64], got {K}')
+    if dim % 8 or dim > 256:
+        raise ValueError(f'{who}: embed_dim must be a multiple of 8 and at most 256, got {dim}')
+    return parts, K, dsub
+
+
+@_on_device
+def kmeans_step(table, centres, *, normalize=False):
+    """rsa_kmeans_step: one assignment pass of k-means over the rows of ``table`` [N, d] (any row stride: ``weight[1:]`` is
+    read in place) against ``centres`` [n_parts, K, d / n_parts] -> (assign int32 [n_parts, N], sums fp32 [n_parts, K, d_sub],
+    counts int32 [n_parts, K], loss float64 [n_parts]).  ``normalize``: rows divided by max(||row||, 1e-12) first."""
+    centres = _need(centres, torch.float32, 'centres')
+    table = _need_view(table, torch.float32, 'table')
+    parts, K, dsub = _codebook_shape(centres, 'kmeans_step')
+    dim = parts * dsub
+    if table.dim() != 2 or table.shape[1] != dim or table.shape[0] < 1:
+        raise ValueError(f'kmeans_step: table must be [N >= 1, {dim}], got {tuple(table.shape)}')
+    if table.stride(1) != 1 or table.stride(0) % 4 or table.stride(0) < dim or table.data_ptr() % 16:
+        table = table.contiguous()
+    n, dev = table.shape[0], table.device
+    assign = torch.empty(parts, n, dtype=torch.int32, device=dev)
+    sums = torch.empty(parts, K, dsub, dtype=torch.float32, device=dev)
+    counts = torch.empty(parts, K, dtype=torch.int32, device=dev)
+    loss = torch.empty(parts, dtype=torch.float64, device=dev)
+    a = nat.KmeansArgs()
+    # a view that starts a whole number of rows into its storage (``weight[1:]``) goes down as base pointer + row offset
+    stride = table.stride(0)
+    skip = table.storage_offset() // stride if table.storage_offset() % stride == 0 else 0
+    a.table, a.n_rows, a.row_stride, a.row_offset = table.data_ptr() - skip * stride * 4, n, stride, skip
+    a.dim, a.n_parts, a.n_clusters, a.normalize = dim, parts, K, int(bool(normalize))
+    a.centres, a.assign, a.sums, a.counts, a.loss = ptr(centres), ptr(assign), ptr(sums), ptr(counts), ptr(loss)
+    ws, a.workspace_bytes = _workspace(dev, 'rsa_kmeans_workspace_bytes', n, dim, K)
+    a.workspace = ptr(ws)
+    _launch('rsa_kmeans_step', ctypes.byref(a))
+    return assign, sums, counts, loss
+
+
+def _midx_args(query, centres, wkk, indptr, indices, cd, num_neg, pos_ids, cosine, who):
+    query = _need(query, torch.float32, 'query')
+    centres = _need(centres, torch.float32, 'centres')
+    parts, K, dsub = _codebook_shape(centres, who)
+    dim = parts * dsub
+    if query.dim() != 2 or query.shape[1] != dim:
+        raise ValueError(f'{who}: query must be [M, {dim}], got {tuple(query.shape)}')
+    M, n = query.shape[0], int(num_neg)
+    a = nat.MidxArgs()
+    a.query, a.n_queries, a.dim, a.n_parts, a.n_clusters = ptr(query), M, dim, parts, K
+    a.score_mode = nat.SCORE_COS if cosine else nat.SCORE_IP
+    a.centres, a.num_neg = ptr(centres), n
+    if len(cd) != parts:
+        raise ValueError(f'{who}: one cluster map per part')
+    cd = [_need(c, torch.int32, 'cd') for c in cd]
+    a.n_items = cd[0].numel() - 1
+    a.cd0, a.cd1 = ptr(cd[0]), ptr(cd[1] if parts == 2 else None)
+    if n:
+        wkk, indptr, indices = _need(wkk, torch.float32, 'wkk'), _need(indptr, torch.int32, 'indptr'), _need(indices, torch.int32, 'indices')
+        if wkk.numel() != K ** parts or indptr.numel() != K ** parts + 1 or indices.numel() != a.n_items:
+            raise ValueError(f'{who}: wkk / indptr / indices do not match K = {K}, n_items = {a.n_items}')
+        a.wkk, a.indptr, a.indices = ptr(wkk), ptr(indptr), ptr(indices)
+    dev = query.device
+    out = dict(neg_ids=torch.empty(M, n, dtype=torch.int64, device=dev), neg_logp=torch.empty(M, n, dtype=torch.float32, device=dev))
+    if n:
+        a.neg_ids, a.neg_logp = ptr(out['neg_ids']), ptr(out['neg_logp'])
+    if pos_ids is not None:
+        pos_ids = _need(pos_ids, torch.int64, 'pos_ids')
+        if pos_ids.dim() != 2 or pos_ids.shape[0] != M:
+            raise ValueError(f'{who}: pos_ids must be [M, T]')
+        out['pos_logp'] = torch.empty(pos_ids.shape, dtype=torch.float32, device=dev)
+        a.n_pos, a.pos_ids, a.pos_logp = pos_ids.shape[1], ptr(pos_ids), ptr(out['pos_logp'])
+    return a, out
+
+
+@_on_device
+def midx_sample(query, centres, wkk, indptr, indices, cd, num_neg, *, pos_ids=None, cosine=False, generator=None,
+                want_u=False):
+    """rsa_midx_sample: negatives of MIDXSamplerUniform (``centres`` [2, K, d / 2]) / ClusterSamplerUniform ([1, K, d]) for
+    ``query`` [M, d], the uniforms those of ``torch.rand(M, num_neg, n_parts + 1)`` on the device generator (advanced as that
+    call would).  ``cd``: the int32 cluster maps [N + 1] per part; ``pos_ids`` [M, T]: also their ``compute_item_p``.
+    -> dict(neg_ids [M, n] int64, neg_logp [M, n], pos_logp [M, T], u [M, n, n_parts + 1] with ``want_u``)."""
+    a, out = _midx_args(query, centres, wkk, indptr, indices, cd, num_neg, pos_ids, cosine, 'midx_sample')
+    numel = a.n_queries * a.num_neg * (a.n_parts + 1)
+    if numel:
+        pc = rng.reserve(numel, 4, query.device, generator)
+        a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
+        if want_u:
+            out['u'] = torch.empty(a.n_queries, a.num_neg, a.n_parts + 1, dtype=torch.float32, device=query.device)
+            a.u_out = ptr(out['u'])
+    _launch('rsa_midx_sample', ctypes.byref(a))
+    return out
+
+
+@_on_device
+def midx_lookup(query, centres, wkk, indptr, indices, cd, u, *, pos_ids=None, cosine=False):
+    """rsa_midx_lookup: the draw of ``midx_sample`` for caller-supplied uniforms ``u`` [M, n, n_parts + 1]."""
+    u = _need(u, torch.float32, 'u')
+    if u.dim() != 3:
+        raise ValueError('midx_lookup: u must be [M, n, n_parts + 1]')
+    a, out = _midx_args(query, centres, wkk, indptr, indices, cd, u.shape[1], pos_ids, cosine, 'midx_lookup')
+    if u.shape[0] != a.n_queries or u.shape[2] != a.n_parts + 1:
+        raise ValueError('midx_lookup: u must be [M, n, n_parts + 1]')
+    a.u_in = ptr(u)
+    _launch('rsa_midx_lookup', ctypes.byref(a))
     return out
 
 

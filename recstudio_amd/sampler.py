@@ -17,7 +17,7 @@ from . import _native as nat
 from . import ops
 
 __all__ = ['Sampler', 'UniformSampler', 'MaskedUniformSampler', 'PopularSamplerModel', 'build_guide_table',
-           'build_cdf_lines']
+           'build_cdf_lines', 'MIDXSamplerUniform', 'ClusterSamplerUniform']
 
 
 class Sampler(torch.nn.Module):
@@ -293,6 +293,150 @@ class PopularSamplerModel(Sampler):
 
     def compute_item_p(self, query, pos_items):
         return ops.item_logp(self.pop_prob, pos_items)                    # sampler.py:257-258
+
+
+class MIDXSamplerUniform(Sampler):
+    """recstudio/ann/sampler.py:261-388: negatives from a proposal that follows the query through two k-means half-codebooks,
+    the final item uniform inside the chosen bucket.  ``update`` (once per epoch) runs the reference's Lloyd loop on
+    ``rsa_kmeans_step``; ``forward`` is one launch of ``rsa_midx_sample`` (ids, log_neg_prob and log_pos_prob).  The uniforms are
+    those of one ``torch.rand(M, n, 3)`` on the device generator, so the ids are distribution-equal to the reference's
+    ``torch.multinomial`` draws, not stream-equal (DESIGN.md)."""
+
+    N_PARTS = 2
+
+    def __init__(self, num_items, num_clusters, scorer_fn=None):
+        from .scorer import CosineScorer, InnerProductScorer
+        if scorer_fn is not None and type(scorer_fn) not in (InnerProductScorer, CosineScorer):
+            raise NotImplementedError(f'{type(self).__name__}: scorer must be None, InnerProductScorer or CosineScorer '
+                                      f'(got {type(scorer_fn).__name__}; the Euclidean form needs the in-bucket popularity draw)')
+        super().__init__(num_items, scorer_fn)
+        if not 2 <= int(num_clusters) <= 64:
+            raise ValueError(f'{type(self).__name__}: num_clusters must be in [2, 64], got {num_clusters}')
+        self.K = int(num_clusters)
+        self._cosine = isinstance(scorer_fn, CosineScorer)
+
+    # -------------------------------------------------------------- update
+    def _centre_names(self):
+        return ('c0', 'c1')
+
+    @torch.no_grad()
+    def _rows(self, X, idx):
+        """Rows ``idx`` of the (normalised, for the cosine scorer) table, as the Lloyd loop seeds centres from them."""
+        rows = X[idx.to(X.device)]
+        return torch.nn.functional.normalize(rows, dim=-1) if self._cosine else rows
+
+    @torch.no_grad()
+    def update(self, item_embs, max_iter=30):
+        X = item_embs.detach()
+        if not X.is_cuda or X.dtype != torch.float32 or X.dim() != 2:
+            raise RuntimeError(f'{type(self).__name__}.update: item_embs must be an fp32 [N, d] tensor on the GPU')
+        N, d = X.shape
+        P, K = self.N_PARTS, self.K
+        if d % 8 or d > 256:
+            raise ValueError(f'{type(self).__name__}: embed_dim must be a multiple of 8 and at most 256, got {d}')
+        dsub = d // P
+        names = self._centre_names()
+        C = []
+        for p, name in enumerate(names):                       # kmeans(): given centres, or K random rows (half 0 first)
+            if hasattr(self, name):
+                C.append(getattr(self, name).detach().to(X.device, torch.float32))
+            else:
+                C.append(self._rows(X, torch.randperm(N)[:K])[:, p * dsub:(p + 1) * dsub])
+        C = torch.stack(C).contiguous()
+        prev = [np.inf] * P
+        live = [True] * P
+        assign = torch.empty(P, N, dtype=torch.int32, device=X.device)
+        for _ in range(max_iter):
+            a, sums, counts, loss = ops.kmeans_step(X, C, normalize=self._cosine)
+            loss = loss.tolist()
+            counts_f = counts.to(torch.float32)
+            C_next = C.clone()
+            for p in range(P):
+                if not live[p]:
+                    continue
+                assign[p] = a[p]
+                if (prev[p] - loss[p]) < prev[p] * 1e-6:        # sampler.py:27: centres and assignment of this pass
+                    live[p] = False
+                    continue
+                prev[p] = loss[p]
+                C_next[p] = sums[p] / counts_f[p].unsqueeze(-1)
+                dead = counts[p] == 0
+                ndead = int(dead.sum())
+                if ndead:                                       # sampler.py:32-34, ascending cluster order
+                    C_next[p][dead] = self._rows(X, torch.randperm(N)[:ndead])[:, p * dsub:(p + 1) * dsub]
+            C = C_next
+            if not any(live):
+                break
+        self._build_index(C, assign.to(torch.int64))
+
+    @torch.no_grad()
+    def _build_index(self, C, cd):
+        """The reference's attributes (names, dtypes) from the centres [P, K, d_sub] and assignments [P, N], plus the compact
+        device copies the kernel reads (derived, rebuilt by every update)."""
+        P, K = self.N_PARTS, self.K
+        dev = C.device
+        for p, name in enumerate(self._centre_names()):
+            setattr(self, name, C[p].clone())
+            setattr(self, name + '_', torch.cat([C.new_zeros(1, C.shape[2]), C[p]], dim=0))
+        shifted = [torch.cat([cd.new_zeros(1), cd[p] + 1]) for p in range(P)]
+        if P == 2:
+            self.cd0, self.cd1 = shifted
+            bucket = cd[0] * K + cd[1]
+        else:
+            self.cd, = shifted
+            bucket = cd[0]
+        nb = K ** P
+        self.indices = torch.sort(bucket, stable=True)[1]                      # construct_index, sampler.py:38-45
+        count = torch.bincount(bucket, minlength=nb)
+        self.indptr = torch.cat([count.new_zeros(1), count.cumsum(0)])
+        self.wkk = count.to(torch.float32).view(K, K) if P == 2 else count.to(torch.float32)
+        self._centres = C.contiguous()
+        self._cd32 = [c.to(torch.int32) for c in shifted]
+        self._indices32, self._indptr32 = self.indices.to(torch.int32), self.indptr.to(torch.int32)
+        self._wkk_dev = self.wkk.to(dev).contiguous()
+
+    # -------------------------------------------------------------- draw
+    def _check_ready(self):
+        if not hasattr(self, '_centres'):
+            raise RuntimeError(f'{type(self).__name__}: call update(item_embs) before sampling (fit does, once per epoch)')
+
+    def forward(self, query, num_neg, pos_items=None):
+        self._check_ready()
+        with torch.no_grad():
+            if query.dim() not in (2, 3):
+                raise ValueError('`query` need to be 2-dimensional or 3-dimensional.')
+            if query.dim() == 3 and pos_items is not None:
+                raise ValueError(f'{type(self).__name__}: a 3-dimensional query takes no pos_items (the reference fails in view_as)')
+            lead = tuple(query.shape[:-1])
+            pos2 = None
+            if pos_items is not None:
+                if pos_items.dim() not in (1, 2) or pos_items.shape[0] != query.shape[0]:
+                    raise ValueError('`pos_items` must be [B] or [B, T]')
+                pos2 = pos_items.reshape(query.shape[0], -1)
+            out = ops.midx_sample(query.detach().reshape(-1, query.shape[-1]), self._centres, self._wkk_dev, self._indptr32,
+                                  self._indices32, self._cd32, int(num_neg), pos_ids=pos2, cosine=self._cosine)
+            neg, neg_prob = out['neg_ids'].view(*lead, num_neg), out['neg_logp'].view(*lead, num_neg)
+            if pos_items is not None:
+                return out['pos_logp'].view(pos_items.shape), neg, neg_prob
+            return neg, neg_prob
+
+    def compute_item_p(self, query, pos_items):
+        """log-proposal (unnormalised) of ``pos_items`` [B] / [B, T] under ``query`` [B, d]: the draw kernel with no draws."""
+        self._check_ready()
+        with torch.no_grad():
+            q = query.detach().reshape(-1, query.shape[-1])
+            out = ops.midx_sample(q, self._centres, None, None, None, self._cd32, 0, pos_ids=pos_items.reshape(q.shape[0], -1),
+                                  cosine=self._cosine)
+            return out['pos_logp'].view(pos_items.shape)
+
+
+class ClusterSamplerUniform(MIDXSamplerUniform):
+    """recstudio/ann/sampler.py:426-510: the same with ONE codebook over the whole vector (``c``, ``cd``, ``wkk`` [K])."""
+
+    N_PARTS = 1
+
+    def _centre_names(self):
+        return ('c',)
 
 
 def sampler_kind(sampler):
