@@ -261,6 +261,31 @@ __device__ __forceinline__ int32_t cdf_lookup_line(const float* __restrict__ lin
   return lo;
 }
 
+// ---------------------------------------------------------------- 32-bit division by a launch constant
+// x / d for 32-bit x by ONE 32-bit multiply-high and a correction: with magic = floor(2^32 / d) (d == 1: 2^32 - 1) the
+// estimate floor(x * magic / 2^32) is the quotient or one below it (x * magic / 2^32 > x / d - x / 2^32 > x / d - 1).  The
+// routing kernel divides four times per element (query of an element, owner of an id, modulo of the uniform draw): the
+// 64-bit forms (a 64 x 64 multiply-high is four quarter-rate multiplies, a 64-bit % a ~150-instruction subroutine)
+// were most of its time.
+struct Div32 {
+  uint32_t d, magic;
+  __device__ __forceinline__ uint32_t div(uint32_t x) const {
+    const uint32_t q = __umulhi(x, magic);
+    return (x - q * d >= d) ? q + 1 : q;
+  }
+  __device__ __forceinline__ uint32_t mod(uint32_t x) const { return x - div(x) * d; }
+};
+inline Div32 make_div32(uint64_t d) {
+  Div32 v;
+  v.d = (uint32_t)d;
+  v.magic = d <= 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / d);
+  return v;
+}
+
+// a key of the sharded exchange is (query << 32) | local row, negative for an empty slot
+__device__ __forceinline__ int64_t key_query(int64_t k) { return (k >> 32) & 0x7fffffffll; }
+__device__ __forceinline__ int64_t key_row(int64_t k) { return k & 0xffffffffll; }
+
 // ---------------------------------------------------------------- wave helpers
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 

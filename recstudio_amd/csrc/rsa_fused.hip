@@ -191,7 +191,7 @@ __device__ __forceinline__ void tile_rows_qg(const float* table, int32_t id_lane
   const int sub = lane % LPR;
   const int gbase = lane - sub;
   dot = 0.f;
-  // batch b+1 requested while batch b is consumed; order pinned by data dependences (see tile_rows_ssm)
+  // batch b+1 requested while batch b is consumed; order pinned by data dependences (see tile_rows_ssm_qg)
   F x[2][BATCH];
   int gb = gbase;
   auto request = [&](int b) __attribute__((always_inline)) {
@@ -409,7 +409,7 @@ void fused_fwd_kernel(const FwdParams p) {
             if (within < RSA_SHARD_HDR || (int64_t)(within - RSA_SHARD_HDR) >= live) g = -1;
           }
           key_lane = g;
-          g = g < 0 ? 0 : (g & 0xffffffffll);   // a negative key is an empty slot (row 0, query 0)
+          g = g < 0 ? 0 : key_row(g);           // a negative key is an empty slot (row 0, query 0)
         }
         g = g < 0 ? 0 : (g >= p.n_items ? p.n_items - 1 : g);   // clamp: never fault on a bad id
         id = (int32_t)g;
@@ -477,8 +477,7 @@ void fused_fwd_kernel(const FwdParams p) {
         qacc.z += __shfl_xor(qacc.z, mk, 64); qacc.w += __shfl_xor(qacc.w, mk, 64);
       }
       const float4 pv = px.v[0];
-      qacc.x = __fmaf_rn(-tg, pv.x, qacc.x); qacc.y = __fmaf_rn(-tg, pv.y, qacc.y);
-      qacc.z = __fmaf_rn(-tg, pv.z, qacc.z); qacc.w = __fmaf_rn(-tg, pv.w, qacc.w);
+      axpy4(qacc, -tg, pv);
       if (lane < LPR) *reinterpret_cast<float4*>(p.qgrad + (size_t)m_lane * D + sub * 4) = qacc;    // n == 64: one tile per query
       if constexpr (UPD) {
         // the positive row: d loss/d pos = -sum_j dneg_j, all of it known here (one tile per query)
@@ -522,11 +521,7 @@ void fused_fwd_kernel(const FwdParams p) {
           if (fuse) {
             // BPRLoss (loss_func.py:55-59): -mean_m (1/n) sum_j logsigmoid(pos - neg_j), with its gradient
             const float w = 1.f / (float)n, inv_m = 1.f / (float)p.mean_queries;
-            // one hardware exp + one log per element: t = exp(-|x|) serves logsigmoid and sigmoid(-x)
-            // (absolute error ~1e-7 on terms of O(1), far inside the 1e-4 contract)
-            const float xd = s - neg_s;
-            const float t = __expf(-fabsf(xd));
-            const float ls = fminf(xd, 0.f) - __logf(1.f + t);
+            const float ls = bpr_row_loss(s, neg_s);
             const float sg = bpr_dneg(s, neg_s, w, inv_m);
             if (p.dneg) st_out(&p.dneg[e], sg);
             const float tl = group_sum<64>(ls * w), tg = group_sum<64>(sg);
@@ -576,8 +571,8 @@ void fused_fwd_kernel(const FwdParams p) {
 // then never reads an item row.
 
 template <int LPR, bool NT>
-__device__ __forceinline__ void tile_rows_ssm(const float* __restrict__ table, int32_t id_lane, float lq_lane, bool has_lq,
-                                              const Frag<LPR, false>& qf, float& dot, float& gm, float4& qacc) {
+__device__ __forceinline__ void tile_rows_ssm_qg(const float* __restrict__ table, int32_t id_lane, float lq_lane, bool has_lq,
+                                                 const Frag<LPR, false>& qf, float& dot, float& gm, float4& qacc) {
   using F = Frag<LPR, false>;
   constexpr int D = LPR * 4;
   constexpr int BATCH = LPR < RSA_SSM_BATCH ? LPR : RSA_SSM_BATCH;
@@ -689,7 +684,7 @@ __global__ __launch_bounds__(256, QG ? RSA_SSM_MIN_WAVES : 1) void fused_ssm_ker
       }
       float dot;
       if constexpr (QG) {
-        tile_rows_ssm<LPR, NT>(p.item_table, id, lq, has_lq, qf, dot, gm, qacc);
+        tile_rows_ssm_qg<LPR, NT>(p.item_table, id, lq, has_lq, qf, dot, gm, qacc);
       } else {
         tile_rows_pipe<LPR, NT, RSA_SSM_PIPE_BATCH>(p.item_table, id, qf, dot);      // (the transposed-fold tile needs 164 VGPRs in this frame)
       }
@@ -730,9 +725,7 @@ __global__ __launch_bounds__(256, QG ? RSA_SSM_MIN_WAVES : 1) void fused_ssm_ker
         qacc.x += __shfl_xor(qacc.x, mk, 64); qacc.y += __shfl_xor(qacc.y, mk, 64);
         qacc.z += __shfl_xor(qacc.z, mk, 64); qacc.w += __shfl_xor(qacc.w, mk, 64);
       }
-      const float4 pv = px.v[0];
-      qacc.x = __fmaf_rn(dp, pv.x, qacc.x); qacc.y = __fmaf_rn(dp, pv.y, qacc.y);
-      qacc.z = __fmaf_rn(dp, pv.z, qacc.z); qacc.w = __fmaf_rn(dp, pv.w, qacc.w);
+      axpy4(qacc, dp, px.v[0]);
       if (lane < LPR) *reinterpret_cast<float4*>(p.qgrad + (size_t)m * D + sub * 4) = qacc;
     }
   }
@@ -814,9 +807,7 @@ __global__ __launch_bounds__(256, QG ? RSA_WALK_MIN_WAVES : RSA_WALK_FWD_MIN_WAV
           tile_rows_pipe<LPR, NT, RSA_WALK_PIPE_BATCH>(p.item_table, id, qf, dot);
         }
         if (p.neg_score) st_out(&p.neg_score[e], dot);
-        const float xd = pos_s - dot;
-        const float tt = __expf(-fabsf(xd));
-        lsum += (fminf(xd, 0.f) - __logf(1.f + tt)) * w;
+        lsum += bpr_row_loss(pos_s, dot) * w;
         const float sg = bpr_dneg(pos_s, dot, w, inv_m);
         if (p.dneg) st_out(&p.dneg[e], sg);
         gsum += sg;
@@ -865,9 +856,7 @@ __global__ __launch_bounds__(256, QG ? RSA_WALK_MIN_WAVES : RSA_WALK_FWD_MIN_WAV
         if (p.dpos) p.dpos[m] = -gsum;
       }
       if constexpr (QG) {
-        const float4 pv = px.v[0];        // d loss/d query = sum_j dneg_j item_j + dpos item_pos, dpos = -sum_j dneg_j
-        qacc.x = __fmaf_rn(-gsum, pv.x, qacc.x); qacc.y = __fmaf_rn(-gsum, pv.y, qacc.y);
-        qacc.z = __fmaf_rn(-gsum, pv.z, qacc.z); qacc.w = __fmaf_rn(-gsum, pv.w, qacc.w);
+        axpy4(qacc, -gsum, px.v[0]);      // d loss/d query = sum_j dneg_j item_j + dpos item_pos, dpos = -sum_j dneg_j
         if (lane < LPR) *reinterpret_cast<float4*>(p.qgrad + (size_t)m * D + sub * 4) = qacc;
       }
     }

@@ -27,7 +27,7 @@
 #include "rsa_tile.hpp"
 
 #ifndef RSA_OWN_BATCH
-#define RSA_OWN_BATCH 4      // rows per load batch (double-buffered, order pinned by data dependences like tile_rows_qg)
+#define RSA_OWN_BATCH 4      // rows per load batch (double-buffered, order pinned by data dependences: see tile_rows_ssm_qg, rsa_fused.hip)
 #endif
 #ifndef RSA_OWN_MIN_WAVES
 #define RSA_OWN_MIN_WAVES 1
@@ -69,6 +69,15 @@ struct OwnArgs {
   float* run_acc;              // [n_queries, D]
 };
 
+// Element i of the walk by query: its slot in the received segments (through the query-sorted pairs; query-grouped
+// segments: the runs are runs of slots) and the local row its key names, clamped: never fault on a bad key
+struct OwnElem { uint32_t slot; int64_t row; };
+__device__ __forceinline__ OwnElem own_elem(const OwnArgs& a, int32_t i) {
+  const uint32_t slot = a.qpairs ? rdx_val(a.qpairs[i]) : (uint32_t)i;
+  const int64_t row = key_row(a.keys[slot]);
+  return {slot, row >= a.n_rows ? a.n_rows - 1 : row};
+}
+
 // keys != nullptr: step_dropped / overflow_sticky are first PUBLISHED from the received segments' header word 1 (what each
 // source could not place this step) -- in the score-at-home protocol rsa_shard_score_segments does that
 __global__ void owner_scale_kernel(const float* __restrict__ scale_in, int32_t* __restrict__ step_dropped,
@@ -103,7 +112,7 @@ __global__ __launch_bounds__(256) void query_runs_kernel(const uint64_t* __restr
 
 // The same from QUERY-GROUPED segments (rsa_shard_route_args.group_by_query): every query's elements for this owner are one
 // contiguous run of one segment already, so the runs are read off the slots in place -- no sort by query
-__global__ __launch_bounds__(256) void query_runs_segments_kernel(const int64_t* __restrict__ keys, int64_t slots, RdxDiv32 by_stride,
+__global__ __launch_bounds__(256) void query_runs_segments_kernel(const int64_t* __restrict__ keys, int64_t slots, Div32 by_stride,
                                                                   int32_t n_queries, int32_t* __restrict__ run_start,
                                                                   int32_t* __restrict__ run_end) {
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
@@ -113,10 +122,10 @@ __global__ __launch_bounds__(256) void query_runs_segments_kernel(const int64_t*
     const int64_t live = keys[(size_t)seg * by_stride.d];
     const int64_t at = (int64_t)(within - RSA_SHARD_HDR);
     if (at >= live) continue;
-    const uint32_t k = (uint32_t)((keys[i] >> 32) & 0x7fffffffll);
+    const uint32_t k = (uint32_t)key_query(keys[i]);
     if (k >= (uint32_t)n_queries) continue;
-    const uint32_t before = at > 0 ? (uint32_t)((keys[i - 1] >> 32) & 0x7fffffffll) : 0xffffffffu;
-    const uint32_t after = at + 1 < live ? (uint32_t)((keys[i + 1] >> 32) & 0x7fffffffll) : 0xffffffffu;
+    const uint32_t before = at > 0 ? (uint32_t)key_query(keys[i - 1]) : 0xffffffffu;
+    const uint32_t after = at + 1 < live ? (uint32_t)key_query(keys[i + 1]) : 0xffffffffu;
     if (k != before) run_start[k] = (int32_t)i;
     if (k != after) run_end[k] = (int32_t)(i + 1);
   }
@@ -219,10 +228,9 @@ __global__ __launch_bounds__(256, RSA_OWN_MIN_WAVES) void owner_backward_walk_ke
         float dv = 0.f;
         uint32_t slot = 0;
         if (act) {
-          slot = a.qpairs ? rdx_val(a.qpairs[i]) : (uint32_t)i;      // (query-grouped segments: the runs are runs of slots)
-          int64_t row = a.keys[slot] & 0xffffffffll;
-          row = row >= a.n_rows ? a.n_rows - 1 : row;        // never fault on a bad key
-          id = (int32_t)row;
+          const OwnElem el = own_elem(a, i);
+          slot = el.slot;
+          id = (int32_t)el.row;
           dv = SCORE ? a.bw : a.d[slot];
           if (UPD && a.solo[slot]) id |= (int32_t)0x80000000;
         }
@@ -232,7 +240,7 @@ __global__ __launch_bounds__(256, RSA_OWN_MIN_WAVES) void owner_backward_walk_ke
           // the lane's own element: the same float operations as inside the tile, so d_out is the value the updates used
           const float g = bpr_dneg(pos_s, dot, dv, a.binv);
           if (act) st_out(&a.d_out[slot], g);
-          const float xd = pos_s - dot;
+          const float xd = pos_s - dot;             // bpr_row_loss (rsa_tile.hpp) written out: through the helper this kernel compiles to other code
           const float tt = __expf(-fabsf(xd));
           wave_loss -= group_sum<64>(act ? (fminf(xd, 0.f) - __logf(1.f + tt)) * a.bw : 0.f);
           gsum += group_sum<64>(g);
@@ -265,8 +273,7 @@ __global__ __launch_bounds__(256, RSA_OWN_MIN_WAVES) void owner_backward_walk_ke
     if (re > rs && part == 0 && lane < LPR) {
       float4* gp = reinterpret_cast<float4*>(a.qgrad_all + (size_t)m * D + sub * 4);
       float4 o = *gp;
-      o.x = __fmaf_rn(gate, qacc.x, o.x); o.y = __fmaf_rn(gate, qacc.y, o.y);
-      o.z = __fmaf_rn(gate, qacc.z, o.z); o.w = __fmaf_rn(gate, qacc.w, o.w);
+      axpy4(o, gate, qacc);
       *gp = o;
     }
   }
@@ -285,8 +292,8 @@ __global__ __launch_bounds__(256, RSA_OWN_MIN_WAVES) void owner_backward_walk_ke
 // registers, owner_ssm_update_walk_kernel), the shared ones from the sorted apply pass -- one read-modify-write per touched row.
 // 64 elements of one query: lane r holds element r's row and log q (+inf for an idle lane: z = -inf, weight 0).
 template <int LPR, bool NT>
-__device__ __forceinline__ void tile_rows_ssm(const float* table, int32_t id_lane, float lq_lane, const Frag<LPR, false>& qf,
-                                              float4& acc, float& mg, float& sg, float& z_out) {
+__device__ __forceinline__ void tile_rows_ssm_run(const float* table, int32_t id_lane, float lq_lane, const Frag<LPR, false>& qf,
+                                                  float4& acc, float& mg, float& sg, float& z_out) {
   using F = Frag<LPR, false>;
   constexpr int D = LPR * 4;
   constexpr int BATCH = LPR < RSA_OWN_BATCH ? LPR : RSA_OWN_BATCH;
@@ -373,14 +380,13 @@ __global__ __launch_bounds__(256, RSA_OWN_MIN_WAVES) void owner_ssm_walk_kernel(
         float lq = INFINITY;
         uint32_t slot = 0;
         if (act) {
-          slot = a.qpairs ? rdx_val(a.qpairs[i]) : (uint32_t)i;
-          int64_t row = a.keys[slot] & 0xffffffffll;
-          row = row >= a.n_rows ? a.n_rows - 1 : row;        // never fault on a bad key
-          id = (int32_t)row;
-          lq = a.logq_rows ? a.logq_rows[row] : 0.f;
+          const OwnElem el = own_elem(a, i);
+          slot = el.slot;
+          id = (int32_t)el.row;
+          lq = a.logq_rows ? a.logq_rows[el.row] : 0.f;
         }
         float z = -INFINITY;
-        tile_rows_ssm<LPR, NT>(a.item, id, lq, qf, acc, mg, sg, z);
+        tile_rows_ssm_run<LPR, NT>(a.item, id, lq, qf, acc, mg, sg, z);
         if (act) st_out(&a.d_out[slot], z);
       }
       // the lane groups' partials (each group walked its own rows of every tile): xor-butterfly over the group bits.  The
@@ -420,7 +426,7 @@ __global__ __launch_bounds__(256, RSA_OWN_MIN_WAVES) void owner_ssm_walk_kernel(
 
 // phase 2, per slot: z -> d loss/d score = exp(z - lse_query) / M for live slots, 0 for the slack (the apply pass reads d of
 // every sorted element, and dead slots sort behind every real row)
-__global__ __launch_bounds__(256) void owner_ssm_d_kernel(const int64_t* __restrict__ keys, int64_t slots, RdxDiv32 by_stride,
+__global__ __launch_bounds__(256) void owner_ssm_d_kernel(const int64_t* __restrict__ keys, int64_t slots, Div32 by_stride,
                                                           int32_t n_queries, const float* __restrict__ lse, float binv,
                                                           float* __restrict__ d_slots) {
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
@@ -428,7 +434,7 @@ __global__ __launch_bounds__(256) void owner_ssm_d_kernel(const int64_t* __restr
     const uint32_t seg = by_stride.div((uint32_t)i), within = (uint32_t)i - seg * by_stride.d;
     float d = 0.f;
     if (within >= RSA_SHARD_HDR && (int64_t)(within - RSA_SHARD_HDR) < keys[(size_t)seg * by_stride.d]) {
-      const uint32_t k = (uint32_t)((keys[i] >> 32) & 0x7fffffffll);
+      const uint32_t k = (uint32_t)key_query(keys[i]);
       if (k < (uint32_t)n_queries) d = __expf(d_slots[i] - lse[k]) * binv;
     }
     d_slots[i] = d;
@@ -453,7 +459,7 @@ __global__ __launch_bounds__(256) void owner_ssm_query_kernel(const float* __res
     const float4 av = *reinterpret_cast<const float4*>(run_acc + (size_t)i * D + sub * 4);
     float4* gp = reinterpret_cast<float4*>(qgrad_all + (size_t)i * D + sub * 4);
     float4 o = *gp;
-    o.x = __fmaf_rn(c, av.x, o.x); o.y = __fmaf_rn(c, av.y, o.y); o.z = __fmaf_rn(c, av.z, o.z); o.w = __fmaf_rn(c, av.w, o.w);
+    axpy4(o, c, av);
     *gp = o;
   }
 }
@@ -498,10 +504,9 @@ __global__ __launch_bounds__(256, RSA_OWN_MIN_WAVES) void owner_ssm_update_walk_
       float dv = 0.f;
       bool solo = false;
       if (act) {
-        const uint32_t slot = a.qpairs ? rdx_val(a.qpairs[i]) : (uint32_t)i;
-        int64_t row = a.keys[slot] & 0xffffffffll;
-        row = row >= a.n_rows ? a.n_rows - 1 : row;              // never fault on a bad key
-        id = (int32_t)row;
+        const OwnElem el = own_elem(a, i);
+        const uint32_t slot = el.slot;
+        id = (int32_t)el.row;
         dv = __expf(a.d_out[slot] - lse_m) * a.binv;
         solo = a.solo[slot] != 0;
         if (!solo) st_out(&a.d_out[slot], dv);                   // the apply pass's coefficient
@@ -571,8 +576,7 @@ __global__ __launch_bounds__(256) void owner_pos_finish_kernel(const float* item
     float4* gp = reinterpret_cast<float4*>(qgrad_all + (size_t)i * D + sub * 4);
     float4 o = *gp;
     const float gd = gate * dp;
-    o.x = __fmaf_rn(gd, xv.x, o.x); o.y = __fmaf_rn(gd, xv.y, o.y);
-    o.z = __fmaf_rn(gd, xv.z, o.z); o.w = __fmaf_rn(gd, xv.w, o.w);
+    axpy4(o, gd, xv);
     *gp = o;
     if (item_rw != nullptr && solo_pos[i]) {
       *reinterpret_cast<float4*>(item_rw + (size_t)row * D + sub * 4) =
@@ -739,7 +743,7 @@ static int owner_prepare(const OwnCommon& c, OwnPrepared& P, OwnPrep mode, hipSt
   if (mode == OWN_PREP_SCALE) return RSA_OK;
   if (P.row_total == 0) return RSA_OK;
   // 1. elements by row (dead slots: key n_rows, behind every real row), solo classification for the in-place update
-  const RdxDiv32 by_stride = rdx_make_div32((uint64_t)c.stride);
+  const Div32 by_stride = make_div32((uint64_t)c.stride);
   const SrcSegments<false> by_row{c.keys, c.pos_rows, P.slots, by_stride, (uint32_t)c.n_rows};
   if (radix_sort_pairs(by_row, P.L.pairs_a, P.L.pairs_b, P.row_total, row_bits, P.L.temp, s) != hipSuccess) {
     rsa::set_error("%s: row sort failed: %s", who, hipGetErrorString(hipGetLastError()));
@@ -966,7 +970,7 @@ extern "C" int rsa_shard_owner_ssm_finish(const rsa_shard_owner_bpr_args* a, con
   });
   RSA_CHECK_LAUNCH("rsa_shard_owner_ssm_finish");
   if (P.slots > 0 && !P.inplace) {          // z -> d for every slot
-    hipLaunchKernelGGL(owner_ssm_d_kernel, dim3(grid_1d(P.slots, 256, 8192)), dim3(256), 0, s, a->keys, P.slots, rdx_make_div32((uint64_t)a->stride),
+    hipLaunchKernelGGL(owner_ssm_d_kernel, dim3(grid_1d(P.slots, 256, 8192)), dim3(256), 0, s, a->keys, P.slots, make_div32((uint64_t)a->stride),
                        (int32_t)Q, lse_all, binv, a->d_slots);
     RSA_CHECK_LAUNCH("rsa_shard_owner_ssm_finish(d)");
   } else if (P.slots > 0) {                 // the second walk by query: z -> d, solo rows rewritten with the query row in registers

@@ -117,21 +117,6 @@ struct SrcStepAll {
   }
 };
 
-// x / d for 32-bit x by one multiply-high and a correction (magic = floor(2^32 / d); d == 1: magic = 2^32 - 1)
-struct RdxDiv32 {
-  uint32_t d, magic;
-  __device__ __forceinline__ uint32_t div(uint32_t x) const {
-    const uint32_t q = __umulhi(x, magic);
-    return (x - q * d >= d) ? q + 1 : q;
-  }
-};
-inline RdxDiv32 rdx_make_div32(uint64_t d) {
-  RdxDiv32 v;
-  v.d = (uint32_t)d;
-  v.magic = d <= 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / d);
-  return v;
-}
-
 // Received exchange segments [n_seg][stride] of 8-byte keys (query << 32 | local row) behind RSA_SHARD_HDR header
 // words: element = slot number; BY_QUERY: key = query index, else the local row; a slot outside its segment's live
 // range gets `dead_key` (sorts last).  Elements past the `slots` segment slots (row sort only) are the step's POSITIVES,
@@ -141,7 +126,7 @@ struct SrcSegments {
   const int64_t* keys;
   const int64_t* extra_rows;
   int64_t slots;
-  RdxDiv32 by_stride;
+  Div32 by_stride;
   uint32_t dead_key;
   __device__ __forceinline__ uint64_t operator()(int64_t i) const {
     uint32_t key = dead_key;
@@ -154,7 +139,7 @@ struct SrcSegments {
     const int64_t k = keys[i];                        // unconditional (the slack is readable): not behind the header's round trip
     const int64_t live = keys[(size_t)seg * by_stride.d];
     if (within >= RSA_SHARD_HDR && (int64_t)(within - RSA_SHARD_HDR) < live) {
-      key = BY_QUERY ? (uint32_t)((k >> 32) & 0x7fffffffll) : (uint32_t)(k & 0xffffffffll);
+      key = (uint32_t)(BY_QUERY ? key_query(k) : key_row(k));
       key = key > dead_key ? dead_key : key;          // never index past the tables on a bad key
     }
     return rdx_pack(key, (uint32_t)i);

@@ -13,6 +13,7 @@
 // Fixed-capacity exchange, version 2 (the default; second half of this file):
 //   rsa_shard_sample_route / rsa_shard_score_segments (rsa_fused.hip) / rsa_shard_home / rsa_shard_unpack_segments
 #include "rsa_launch.hpp"
+#include "rsa_tile.hpp"
 
 namespace rsa {
 
@@ -27,26 +28,6 @@ static inline FastDiv make_fastdiv(uint64_t d) {
   FastDiv f;
   f.magic = d <= 1 ? 0 : (~0ull / d) + 1;     // floor((2^64 - 1) / d) + 1 == floor(2^64 / d) + 1 unless d | 2^64 (then exact too)
   return f;
-}
-
-// x / d for 32-bit x by ONE 32-bit multiply-high and a correction: with magic = floor(2^32 / d) the estimate
-// floor(x * magic / 2^32) is the quotient or one below it (x * magic / 2^32 > x / d - x / 2^32 > x / d - 1).  The
-// routing kernel divides four times per element (query of an element, owner of an id, modulo of the uniform draw): the
-// 64-bit forms (a 64 x 64 multiply-high is four quarter-rate multiplies, a 64-bit % a ~150-instruction subroutine)
-// were most of its time.
-struct Div32 {
-  uint32_t d, magic;
-  __device__ __forceinline__ uint32_t div(uint32_t x) const {
-    const uint32_t q = __umulhi(x, magic);
-    return (x - q * d >= d) ? q + 1 : q;
-  }
-  __device__ __forceinline__ uint32_t mod(uint32_t x) const { return x - div(x) * d; }
-};
-static inline Div32 make_div32(uint64_t d) {
-  Div32 v;
-  v.d = (uint32_t)d;
-  v.magic = d <= 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / d);
-  return v;
 }
 
 struct RouteShape {
@@ -687,11 +668,8 @@ __global__ __launch_bounds__(256) void shard_home_kernel(const HomeArgs a) {
           const int j = ((t0 + i) << 6) + lane;
           const bool in = t0 + i < T && j < n;
           const bool live = s[i] >= 0 && sp >= 0;
-          const float xd = pos - sc[i];
-          const float tt = __expf(-fabsf(xd));
-          const float ls = live ? fminf(xd, 0.f) - __logf(1.f + tt) : 0.f;
-          const float r = __frcp_rn(1.f + tt);
-          const float sg = live ? (xd >= 0.f ? tt * r : r) * w * inv_m : 0.f;
+          const float ls0 = bpr_row_loss(pos, sc[i]), sg0 = bpr_dneg(pos, sc[i], w, inv_m);
+          const float ls = live ? ls0 : 0.f, sg = live ? sg0 : 0.f;
           if (in) {
             if (a.neg_score != nullptr) a.neg_score[m * n + j] = sc[i];
             if (a.dneg != nullptr) a.dneg[m * n + j] = sg;
@@ -824,11 +802,8 @@ __global__ __launch_bounds__(256) void shard_home_small_kernel(const HomeArgs a)
         for (int t = 0; t < TPQ; ++t) {
           const int j = (t << 6) + lane;
           const bool live = s[q][t] >= 0 && sp[q] >= 0;
-          const float xd = pos[q] - sc[q][t];
-          const float tt = __expf(-fabsf(xd));
-          const float ls = live ? fminf(xd, 0.f) - __logf(1.f + tt) : 0.f;
-          const float r = __frcp_rn(1.f + tt);
-          const float sg = live ? (xd >= 0.f ? tt * r : r) * w * inv_m : 0.f;
+          const float ls0 = bpr_row_loss(pos[q], sc[q][t]), sg0 = bpr_dneg(pos[q], sc[q][t], w, inv_m);
+          const float ls = live ? ls0 : 0.f, sg = live ? sg0 : 0.f;
           if (j < n && a.dneg != nullptr) a.dneg[m * n + j] = sg;
           if (s[q][t] >= 0 && a.d_send != nullptr) a.d_send[s[q][t]] = sg;
           lsum += ls;
