@@ -189,10 +189,41 @@ typedef struct rsa_midx_args {
   uint32_t grid_threads;
   uint32_t _pad;
   uint64_t elem_base;
+  /* Popularity-in-bucket form (MIDXSamplerPop / ClusterSamplerPop; tables of rsa_midx_weights).  Both null: the item is uniform in
+   * its bucket, as above.  Both set: inside bucket [start, end) the item sits at the FIRST position with cp[pos] > u2 (the last
+   * position whose cp exceeds its predecessor's when rounding leaves none), and item_logp[id] is added to neg_logp and pos_logp. */
+  const float* cp;             /* nullable [n_items] in-bucket CDF by sorted position */
+  const float* item_logp;      /* nullable [n_items + 1] log of the in-bucket weight of every id, 0 for the padding id */
 } rsa_midx_args;
 int rsa_midx_sample(const rsa_midx_args* args, rsa_stream_t stream);
 /* The same draw for caller-supplied uniforms (the tests hit exact CDF edges with it). */
 int rsa_midx_lookup(const rsa_midx_args* args, rsa_stream_t stream);
+
+/* The per-epoch tables of MIDXSamplerPop / ClusterSamplerPop._update -- recstudio/ann/sampler.py:407-423, :545-559 -- from the
+ * index of the last update.  Item i (id i + 1) weighs w = pop[i], times exp(-||row i||^2 / 2) when `table` is given (the
+ * Euclidean scorer; norm and exp in double, the product rounded to fp32 once).  p = [1, w...], item_logp = fl(log((double)p)),
+ * wkk[b] = the sum of w over bucket b and cp[pos] = prefix(pos) / wkk[b] inside each bucket, both accumulated in double in the
+ * order of `indices` and rounded once; a bucket of weight 0 gets wkk = 0 and cp = 0 throughout.  The summation order depends on
+ * the bucket layout alone: two runs are bit-equal.  Same limits as rsa_midx_args. */
+typedef struct rsa_midx_weights_args {
+  int64_t size;                /* sizeof(rsa_midx_weights_args) */
+  const float* pop;            /* [n_items] popularity weight of ids 1 .. n_items */
+  const float* table;          /* nullable: rows [row_offset, row_offset + n_items) give the Euclidean factor */
+  int64_t n_items;             /* items WITHOUT the padding id */
+  int64_t row_stride;          /* floats, a multiple of 4 */
+  int64_t row_offset;
+  int32_t dim;
+  int32_t n_parts;
+  int32_t n_clusters;
+  int32_t _pad;
+  const int32_t* indptr;       /* [K^n_parts + 1] */
+  const int32_t* indices;      /* [n_items] */
+  float* p;                    /* [n_items + 1] out */
+  float* item_logp;            /* [n_items + 1] out */
+  float* wkk;                  /* [K^n_parts] out */
+  float* cp;                   /* [n_items] out */
+} rsa_midx_weights_args;
+int rsa_midx_weights(const rsa_midx_weights_args* args, rsa_stream_t stream);
 
 /* One assignment pass of kmeans() -- recstudio/ann/sampler.py:19-31 -- over rows [row_offset, row_offset + n_rows) of `table`
  * (row_stride floats apart), for n_parts column groups at once; every row is read once.  normalize: rows are divided by

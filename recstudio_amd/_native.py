@@ -188,7 +188,16 @@ class MidxArgs(_Sized):
         ('indices', c_void_p), ('n_items', c_int64), ('cd0', c_void_p), ('cd1', c_void_p), ('num_neg', c_int32), ('n_pos', c_int32),
         ('pos_ids', c_void_p), ('u_in', c_void_p), ('neg_ids', c_void_p), ('neg_logp', c_void_p), ('pos_logp', c_void_p),
         ('u_out', c_void_p), ('seed', c_uint64), ('offset', c_uint64), ('grid_threads', c_uint32), ('_pad', c_uint32),
-        ('elem_base', c_uint64),
+        ('elem_base', c_uint64), ('cp', c_void_p), ('item_logp', c_void_p),
+    ]
+
+
+class MidxWeightsArgs(_Sized):
+    """struct rsa_midx_weights_args."""
+    _fields_ = [
+        ('size', c_int64), ('pop', c_void_p), ('table', c_void_p), ('n_items', c_int64), ('row_stride', c_int64),
+        ('row_offset', c_int64), ('dim', c_int32), ('n_parts', c_int32), ('n_clusters', c_int32), ('_pad', c_int32),
+        ('indptr', c_void_p), ('indices', c_void_p), ('p', c_void_p), ('item_logp', c_void_p), ('wkk', c_void_p), ('cp', c_void_p),
     ]
 
 
@@ -210,6 +219,7 @@ STRUCTS = {
     'rsa_shard_owner_bpr_args': ShardOwnerBprArgs, 'rsa_popular_args': PopularArgs, 'rsa_loss_args': LossArgs,
     'rsa_rows_update_args': RowsUpdateArgs, 'rsa_bpr_sgd_args': BprSgdArgs, 'rsa_seg_gather_args': SegGatherArgs,
     'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
+    'rsa_midx_weights_args': MidxWeightsArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -225,6 +235,7 @@ SIGNATURES = {
     'rsa_popular_lookup': (c_int, [POINTER(PopularArgs), c_void_p]),
     'rsa_midx_sample': (c_int, [POINTER(MidxArgs), c_void_p]),
     'rsa_midx_lookup': (c_int, [POINTER(MidxArgs), c_void_p]),
+    'rsa_midx_weights': (c_int, [POINTER(MidxWeightsArgs), c_void_p]),
     'rsa_kmeans_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
     'rsa_kmeans_step': (c_int, [POINTER(KmeansArgs), c_void_p]),
     'rsa_item_logp': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

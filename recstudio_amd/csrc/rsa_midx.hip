@@ -18,6 +18,12 @@
 // row of wkk) holds an item.  An empty bucket (wkk == 0) is therefore never returned, whatever u is.
 // The item: idx = min(floor(float(cnt) * u2), cnt - 1) inside bucket k0 * K + k1, id = indices[indptr[b] + idx] + 1.
 // Uniforms: element ((q * n + j) * 3 + t) of ONE torch.rand(M, n, 3) on the device stream (Cluster: (M, n, 2)).
+// WEIGHTED ITEM (MIDXSamplerPop / ClusterSamplerPop; cp and item_logp given).  Inside bucket [start, end) the item sits at the FIRST
+// position with cp[pos] > u2: an upper-bound binary search over the bucket's slice of cp.  cp is non-decreasing and stays where it
+// is across an item of weight 0 (rsa_midx_weights), so such an item is never the first to exceed anything.  When no position
+// exceeds u2 (a bucket of weight 0 chosen because every weight is 0) the answer is the last position whose cp exceeds its
+// predecessor's, the first position when there is none.  id = indices[pos] + 1, log-prob = fl(fl(r0 + r1) + item_logp[id]);
+// compute_item_p adds item_logp[pos_id] the same way (0 for the padding id).
 // With a CosineScorer the query is divided by max(||q||, 1e-12) first (the sum of squares in double, one rounding per element).
 //
 // LLOYD STEP.  One pass over the rows for 1 or 2 parts (column halves): tiles of 16 rows are staged in LDS, a wave scores 4 rows
@@ -89,6 +95,8 @@ struct MidxParams {
   float* pos_logp;
   float* u_out;
   PhiloxCall pc;
+  const float* cp;
+  const float* item_logp;
 };
 
 // first k with w(k) > 0 whose running sum exceeds `target` (see TIE RULE above); w(k) / has(k): weight / "holds an item"
@@ -108,7 +116,27 @@ __device__ __forceinline__ int pick_cluster(int K, float target, W&& w, H&& has)
   return sel >= 0 ? sel : (last >= 0 ? last : (first_has >= 0 ? first_has : 0));
 }
 
-template <bool FROM_U>
+// first position of [start, end) with cp[pos] > u (see WEIGHTED ITEM above)
+__device__ __forceinline__ int32_t pick_weighted(const float* __restrict__ cp, int32_t start, int32_t end, float u) {
+  int32_t lo = start, hi = end;
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (cp[mid] > u) hi = mid;
+    else lo = mid + 1;
+  }
+  if (lo < end) return lo;
+  const float top = cp[end - 1];                           // nothing exceeds u: the first position that reaches the last value
+  if (!(top > 0.f)) return start;
+  lo = start, hi = end - 1;
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (cp[mid] >= top) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+template <bool FROM_U, bool WEIGHTED>
 __global__ __launch_bounds__(256) void midx_draw_kernel(const MidxParams p) {
   const int K = p.K, d = p.dim, parts = p.parts, dsub = d / parts, stride = dsub + CPAD;
   const int wrow = parts == 2 ? K + 1 : 1;                 // MIDX: row k0 of wkk, then the row's sum
@@ -203,7 +231,16 @@ __global__ __launch_bounds__(256) void midx_draw_kernel(const MidxParams p) {
         }
         const int32_t start = p.indptr[bucket], cnt = p.indptr[bucket + 1] - start;
         int64_t id = 0;                                    // (an index without items: the padding id, nothing is read)
-        if (cnt > 0) {
+        if (WEIGHTED) {
+          const int32_t lim = (int32_t)p.n_items;          // (a bucket is a range of positions: never read past the tables)
+          const int32_t s0 = start < 0 ? 0 : (start > lim ? lim : start);
+          const int32_t e0 = start + cnt > lim ? lim : start + cnt;
+          if (e0 > s0) {
+            id = (int64_t)p.indices[pick_weighted(p.cp, s0, e0, u[nu - 1])] + 1;
+            id = id < 1 ? 1 : (id > p.n_items ? p.n_items : id);
+            logp = logp + p.item_logp[id];
+          }
+        } else if (cnt > 0) {
           int32_t idx = (int32_t)floorf((float)cnt * u[nu - 1]);
           idx = idx < 0 ? 0 : (idx > cnt - 1 ? cnt - 1 : idx);
           const int64_t at = (int64_t)start + idx;
@@ -225,6 +262,7 @@ __global__ __launch_bounds__(256) void midx_draw_kernel(const MidxParams p) {
           b = b < 0 ? 0 : (b > K ? K : b);
           v = v + (b > 0 ? r1[b - 1] : 0.f);
         }
+        if (WEIGHTED) v = v + p.item_logp[id];
         p.pos_logp[q * T + t] = v;
       }
     }
@@ -404,6 +442,126 @@ static KmeansLayout kmeans_layout(void* base, int64_t n_rows, int dim, int K) {
   return L;
 }
 
+// ---------------------------------------------------------------- per-epoch tables of the popularity-in-bucket form
+struct WeightParams {
+  const float* pop;
+  const float* x;            // first row, or null
+  int64_t n_items, row_stride;
+  int dim;
+  const int32_t* indptr;
+  const int32_t* indices;
+  float* p;
+  float* item_logp;
+  float* wkk;
+  float* cp;
+};
+
+// ROW PASS.  One wave per item (a lane per float4 of its row): w = pop, times exp(-||x||^2 / 2) in double; p and log p.
+__global__ __launch_bounds__(256) void midx_weight_rows_kernel(const WeightParams p) {
+  const int lane = lane_id(), q4 = p.dim >> 2;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
+  if (wave == 0 && lane == 0) {
+    p.p[0] = 1.f;
+    p.item_logp[0] = 0.f;
+  }
+  if (p.x == nullptr) {                                    // no rows to read: a lane per item
+    for (int64_t i = wave * 64 + lane; i < p.n_items; i += n_waves * 64) {
+      const float w = p.pop[i];
+      p.p[i + 1] = w;
+      p.item_logp[i + 1] = (float)log((double)w);
+    }
+    return;
+  }
+  for (int64_t i = wave; i < p.n_items; i += n_waves) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < q4) v = reinterpret_cast<const float4*>(p.x + i * p.row_stride)[lane];
+    const double ss = wave_sum_f64((double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w);
+    if (lane == 0) {
+      const float w = (float)((double)p.pop[i] * exp(-0.5 * ss));
+      p.p[i + 1] = w;
+      p.item_logp[i + 1] = (float)log((double)w);
+    }
+  }
+}
+
+// BUCKET PASS.  One workgroup of 1024 threads per bucket walks its positions in chunks of 8192, a thread 8 consecutive ones.  The
+// running sum of position (chunk, wave, lane, j) is  B[wave] + (E[lane] + L[j])  in double, with
+//   L[j]   the thread's own weights added one by one,
+//   E[l+1] = E[l] + L[7] of lane l      (sequential over the wave's lanes, E[0] = 0),
+//   B[w+1] = B[w] + E[64] of wave w     (sequential over the waves, B[0] = the previous chunk's B[16]).
+// Every level only ever adds, so the sums never decrease, and an item of weight 0 gets EXACTLY its predecessor's sum also across
+// a thread, wave or chunk boundary (the last sum of a thread is by construction the E of the next one, and so on up).  The first
+// walk leaves the bucket's total T (the sum at its last position), the second writes cp = fl32(sum / T), which ends at 1.  The
+// order of the additions is a function of the bucket's start and length alone.
+constexpr int WB_THREADS = 1024, WB_ITEMS = 8;
+
+template <bool WRITE>
+__device__ __forceinline__ double bucket_walk(const WeightParams& p, int32_t start, int32_t end, double total, double* tot,
+                                              double* wbase) {
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  double carry = 0.0;
+  for (int64_t c0 = start; c0 < end; c0 += WB_THREADS * WB_ITEMS) {
+    const int64_t at = (int64_t)c0 + (int64_t)threadIdx.x * WB_ITEMS;
+    double L[WB_ITEMS];
+#pragma unroll
+    for (int j = 0; j < WB_ITEMS; ++j) {
+      double w = 0.0;
+      if (at + j < end) {
+        int32_t it = p.indices[at + j];
+        it = it < 0 ? 0 : (it >= p.n_items ? (int32_t)p.n_items - 1 : it);
+        w = (double)p.p[it + 1];
+      }
+      L[j] = w;
+    }
+#pragma unroll
+    for (int j = 1; j < WB_ITEMS; ++j) L[j] = L[j - 1] + L[j];
+    __syncthreads();                                       // the previous chunk's tot / wbase have been read
+    tot[threadIdx.x] = L[WB_ITEMS - 1];
+    __syncthreads();
+    if (lane == 0) {                                       // E of this wave's lanes, in place
+      double e = 0.0;
+      for (int l = 0; l < 64; ++l) {
+        const double t = tot[wave * 64 + l];
+        tot[wave * 64 + l] = e;
+        e = e + t;
+      }
+      wbase[wave] = e;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                // B of the waves, in place
+      double b = carry;
+      for (int w = 0; w < WB_THREADS / 64; ++w) {
+        const double t = wbase[w];
+        wbase[w] = b;
+        b = b + t;
+      }
+      wbase[WB_THREADS / 64] = b;
+    }
+    __syncthreads();
+    carry = wbase[WB_THREADS / 64];
+    if (WRITE) {
+      const double B = wbase[wave], E = tot[threadIdx.x];
+#pragma unroll
+      for (int j = 0; j < WB_ITEMS; ++j)
+        if (at + j < end) p.cp[at + j] = total > 0.0 ? (float)((B + (E + L[j])) / total) : 0.f;
+    }
+  }
+  return carry;
+}
+
+__global__ __launch_bounds__(WB_THREADS) void midx_weight_buckets_kernel(const WeightParams p) {
+  __shared__ double tot[WB_THREADS];
+  __shared__ double wbase[WB_THREADS / 64 + 1];
+  const int b = blockIdx.x;
+  const int32_t lim = (int32_t)p.n_items;
+  int32_t start = p.indptr[b], end = p.indptr[b + 1];
+  start = start < 0 ? 0 : (start > lim ? lim : start);
+  end = end > lim ? lim : end;
+  const double total = end > start ? bucket_walk<false>(p, start, end, 0.0, tot, wbase) : 0.0;
+  if (threadIdx.x == 0) p.wkk[b] = (float)total;
+  if (end > start) bucket_walk<true>(p, start, end, total, tot, wbase);
+}
+
 static int check_codebook(const char* fn, int dim, int parts, int K) {
   RSA_CHECK_ARG(parts == 1 || parts == 2, "%s: n_parts must be 1 (Cluster) or 2 (MIDX), got %d", fn, parts);
   RSA_CHECK_ARG(K >= 2 && K <= MIDX_MAX_K, "%s: n_clusters must be in [2, %d], got %d", fn, MIDX_MAX_K, K);
@@ -447,15 +605,21 @@ static int midx_entry(const rsa_midx_args* args, rsa_stream_t stream, const char
   if (a.n_pos > 0) {
     RSA_CHECK_ARG(a.pos_ids && a.pos_logp && a.cd0 && (a.n_parts == 1 || a.cd1), "%s: pos_ids/pos_logp/cd is null", fn);
   }
+  RSA_CHECK_ARG((a.cp != nullptr) == (a.item_logp != nullptr), "%s: cp and item_logp go together (both set or both null)", fn);
+  const bool weighted = a.cp != nullptr;
   const int64_t lds = draw_lds_bytes(a.dim, a.n_parts, a.n_clusters);
   RSA_CHECK_ARG(lds <= LDS_LIMIT, "%s: codebook does not fit the LDS", fn);
   MidxParams p{a.query, a.n_queries, a.dim, a.n_parts, a.n_clusters, a.score_mode == RSA_SCORE_COS, a.centres, a.wkk, a.indptr,
                a.indices, a.n_items, a.cd0, a.cd1, a.num_neg, a.n_pos, a.pos_ids, a.u_in, a.neg_ids, a.neg_logp, a.pos_logp,
-               U_GIVEN ? nullptr : a.u_out, PhiloxCall{a.seed, a.offset >> 2, a.grid_threads ? a.grid_threads : 1, a.elem_base}};
-  if (int rc = allow_lds<midx_draw_kernel<U_GIVEN>>(lds, fn)) return rc;
+               U_GIVEN ? nullptr : a.u_out, PhiloxCall{a.seed, a.offset >> 2, a.grid_threads ? a.grid_threads : 1, a.elem_base},
+               a.cp, a.item_logp};
+  if (int rc = weighted ? allow_lds<midx_draw_kernel<U_GIVEN, true>>(lds, fn) : allow_lds<midx_draw_kernel<U_GIVEN, false>>(lds, fn))
+    return rc;
   // the codebook is staged once per workgroup, so at most 1024 workgroups stride over the queries: 4 per CU, of which the
   // LDS lets 2 be resident at K = 64, d = 128 (58 KB each) and 1 at d = 256 (93 KB)
-  hipLaunchKernelGGL(midx_draw_kernel<U_GIVEN>, dim3(grid_1d(a.n_queries, 4, 1024)), dim3(256), (size_t)lds, (hipStream_t)stream, p);
+  const dim3 grid(grid_1d(a.n_queries, 4, 1024));
+  if (weighted) hipLaunchKernelGGL((midx_draw_kernel<U_GIVEN, true>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((midx_draw_kernel<U_GIVEN, false>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, p);
   RSA_CHECK_LAUNCH(fn);
   return RSA_OK;
 }
@@ -470,6 +634,29 @@ extern "C" int rsa_midx_sample(const rsa_midx_args* args, rsa_stream_t stream) {
 
 extern "C" int rsa_midx_lookup(const rsa_midx_args* args, rsa_stream_t stream) {
   return midx_entry<true>(args, stream, "rsa_midx_lookup");
+}
+
+extern "C" int rsa_midx_weights(const rsa_midx_weights_args* args, rsa_stream_t stream) {
+  const char* fn = "rsa_midx_weights";
+  rsa_midx_weights_args a;
+  if (int rc = load_args(a, args, fn)) return rc;
+  if (int rc = check_codebook(fn, a.dim, a.n_parts, a.n_clusters)) return rc;
+  RSA_CHECK_ARG(a.n_items >= 1 && a.n_items < (1ll << 31) - 1, "%s: n_items out of range", fn);
+  RSA_CHECK_ARG(a.pop && a.indptr && a.indices && a.p && a.item_logp && a.wkk && a.cp, "%s: null pointer", fn);
+  const float* x = nullptr;
+  if (a.table != nullptr) {
+    RSA_CHECK_ARG(a.row_stride >= a.dim && a.row_stride % 4 == 0 && a.row_offset >= 0, "%s: row_stride must be a multiple of 4 >= dim, row_offset >= 0", fn);
+    x = a.table + a.row_offset * a.row_stride;
+    RSA_CHECK_ARG(((uintptr_t)x & 15) == 0, "%s: table must be 16-byte aligned", fn);
+  }
+  WeightParams p{a.pop, x, a.n_items, a.row_stride, a.dim, a.indptr, a.indices, a.p, a.item_logp, a.wkk, a.cp};
+  const int64_t per_block = x ? 4 : 256;
+  hipLaunchKernelGGL(midx_weight_rows_kernel, dim3(grid_1d(a.n_items, per_block, 8192)), dim3(256), 0, (hipStream_t)stream, p);
+  RSA_CHECK_LAUNCH("rsa_midx_weights (row pass)");
+  const int buckets = a.n_parts == 2 ? a.n_clusters * a.n_clusters : a.n_clusters;
+  hipLaunchKernelGGL(midx_weight_buckets_kernel, dim3(buckets), dim3(WB_THREADS), 0, (hipStream_t)stream, p);
+  RSA_CHECK_LAUNCH("rsa_midx_weights (bucket pass)");
+  return RSA_OK;
 }
 
 extern "C" int64_t rsa_kmeans_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_clusters) {

@@ -272,18 +272,14 @@ def kmeans_step(table, centres, *, normalize=False):
     dim = parts * dsub
     if table.dim() != 2 or table.shape[1] != dim or table.shape[0] < 1:
         raise ValueError(f'kmeans_step: table must be [N >= 1, {dim}], got {tuple(table.shape)}')
-    if table.stride(1) != 1 or table.stride(0) % 4 or table.stride(0) < dim or table.data_ptr() % 16:
-        table = table.contiguous()
+    base, stride, skip, table = _table_view(table, dim)
     n, dev = table.shape[0], table.device
     assign = torch.empty(parts, n, dtype=torch.int32, device=dev)
     sums = torch.empty(parts, K, dsub, dtype=torch.float32, device=dev)
     counts = torch.empty(parts, K, dtype=torch.int32, device=dev)
     loss = torch.empty(parts, dtype=torch.float64, device=dev)
     a = nat.KmeansArgs()
-    # a view that starts a whole number of rows into its storage (``weight[1:]``) goes down as base pointer + row offset
-    stride = table.stride(0)
-    skip = table.storage_offset() // stride if table.storage_offset() % stride == 0 else 0
-    a.table, a.n_rows, a.row_stride, a.row_offset = table.data_ptr() - skip * stride * 4, n, stride, skip
+    a.table, a.n_rows, a.row_stride, a.row_offset = base, n, stride, skip
     a.dim, a.n_parts, a.n_clusters, a.normalize = dim, parts, K, int(bool(normalize))
     a.centres, a.assign, a.sums, a.counts, a.loss = ptr(centres), ptr(assign), ptr(sums), ptr(counts), ptr(loss)
     ws, a.workspace_bytes = _workspace(dev, 'rsa_kmeans_workspace_bytes', n, dim, K)
@@ -292,7 +288,49 @@ def kmeans_step(table, centres, *, normalize=False):
     return assign, sums, counts, loss
 
 
-def _midx_args(query, centres, wkk, indptr, indices, cd, num_neg, pos_ids, cosine, who):
+def _table_view(table, dim):
+    """(base pointer, row stride, row offset, the tensor to keep alive) of a row table read in place: a view that starts a whole
+    number of rows into its storage (``weight[1:]``) goes down as base pointer + row offset; anything the kernels cannot stride
+    over is copied."""
+    if table.stride(1) != 1 or table.stride(0) % 4 or table.stride(0) < dim or table.data_ptr() % 16:
+        table = table.contiguous()
+    stride = table.stride(0)
+    skip = table.storage_offset() // stride if table.storage_offset() % stride == 0 else 0
+    return table.data_ptr() - skip * stride * 4, stride, skip, table
+
+
+@_on_device
+def midx_weights(pop, indptr, indices, n_clusters, n_parts, *, table=None, dim=8):
+    """rsa_midx_weights: the per-epoch tables of the popularity-in-bucket samplers from ``pop`` [N] (the weight of ids 1 .. N) and
+    the index of the last update (int32 ``indptr`` [K^n_parts + 1], ``indices`` [N]).  ``table`` [N, d] (any row stride): the
+    weight is multiplied by exp(-||row||^2 / 2), the Euclidean scorer's form.
+    -> (p [N + 1], item_logp [N + 1], wkk [K^n_parts], cp [N]), all fp32."""
+    pop = _need(pop, torch.float32, 'pop')
+    indptr, indices = _need(indptr, torch.int32, 'indptr'), _need(indices, torch.int32, 'indices')
+    K, parts, n = int(n_clusters), int(n_parts), pop.numel()
+    if parts not in (1, 2) or not 2 <= K <= 64:
+        raise ValueError(f'midx_weights: n_parts must be 1 or 2 and the number of clusters in [2, 64], got {parts}, {K}')
+    if n < 1 or pop.dim() != 1 or indices.numel() != n or indptr.numel() != K ** parts + 1:
+        raise ValueError(f'midx_weights: pop [N >= 1], indices [N] and indptr [K^n_parts + 1] do not match (N = {n}, K = {K})')
+    dev = pop.device
+    a = nat.MidxWeightsArgs()
+    if table is not None:
+        table = _need_view(table, torch.float32, 'table')
+        dim = int(table.shape[1]) if table.dim() == 2 else 0
+        if table.dim() != 2 or table.shape[0] != n or dim % 8 or not 8 <= dim <= 256:
+            raise ValueError(f'midx_weights: table must be [{n}, d] with d a multiple of 8 and at most 256, got {tuple(table.shape)}')
+        base, a.row_stride, a.row_offset, table = _table_view(table, dim)
+        a.table = base
+    out = carve(dev, [('p', (n + 1,), torch.float32), ('logp', (n + 1,), torch.float32), ('wkk', (K ** parts,), torch.float32),
+                      ('cp', (n,), torch.float32)])
+    a.pop, a.n_items, a.dim, a.n_parts, a.n_clusters = ptr(pop), n, int(dim), parts, K
+    a.indptr, a.indices = ptr(indptr), ptr(indices)
+    a.p, a.item_logp, a.wkk, a.cp = ptr(out['p']), ptr(out['logp']), ptr(out['wkk']), ptr(out['cp'])
+    _launch('rsa_midx_weights', ctypes.byref(a))
+    return out['p'], out['logp'], out['wkk'], out['cp']
+
+
+def _midx_args(query, centres, wkk, indptr, indices, cd, num_neg, pos_ids, cosine, who, cp=None, item_logp=None):
     query = _need(query, torch.float32, 'query')
     centres = _need(centres, torch.float32, 'centres')
     parts, K, dsub = _codebook_shape(centres, who)
@@ -324,17 +362,26 @@ def _midx_args(query, centres, wkk, indptr, indices, cd, num_neg, pos_ids, cosin
             raise ValueError(f'{who}: pos_ids must be [M, T]')
         out['pos_logp'] = torch.empty(pos_ids.shape, dtype=torch.float32, device=dev)
         a.n_pos, a.pos_ids, a.pos_logp = pos_ids.shape[1], ptr(pos_ids), ptr(out['pos_logp'])
+    if cp is not None or item_logp is not None:
+        if cp is None or item_logp is None:
+            raise ValueError(f'{who}: cp and item_logp go together')
+        cp, item_logp = _need(cp, torch.float32, 'cp'), _need(item_logp, torch.float32, 'item_logp')
+        if cp.numel() != a.n_items or item_logp.numel() != a.n_items + 1:
+            raise ValueError(f'{who}: cp must hold n_items = {a.n_items} entries and item_logp one more')
+        a.cp, a.item_logp = ptr(cp), ptr(item_logp)
     return a, out
 
 
 @_on_device
 def midx_sample(query, centres, wkk, indptr, indices, cd, num_neg, *, pos_ids=None, cosine=False, generator=None,
-                want_u=False):
+                want_u=False, cp=None, item_logp=None):
     """rsa_midx_sample: negatives of MIDXSamplerUniform (``centres`` [2, K, d / 2]) / ClusterSamplerUniform ([1, K, d]) for
     ``query`` [M, d], the uniforms those of ``torch.rand(M, num_neg, n_parts + 1)`` on the device generator (advanced as that
     call would).  ``cd``: the int32 cluster maps [N + 1] per part; ``pos_ids`` [M, T]: also their ``compute_item_p``.
+    ``cp`` [N] / ``item_logp`` [N + 1] (``midx_weights``): the item is drawn from the bucket's CDF instead of uniformly, and its
+    log-weight is added to both log-probabilities (MIDXSamplerPop / ClusterSamplerPop).
     -> dict(neg_ids [M, n] int64, neg_logp [M, n], pos_logp [M, T], u [M, n, n_parts + 1] with ``want_u``)."""
-    a, out = _midx_args(query, centres, wkk, indptr, indices, cd, num_neg, pos_ids, cosine, 'midx_sample')
+    a, out = _midx_args(query, centres, wkk, indptr, indices, cd, num_neg, pos_ids, cosine, 'midx_sample', cp, item_logp)
     numel = a.n_queries * a.num_neg * (a.n_parts + 1)
     if numel:
         pc = rng.reserve(numel, 4, query.device, generator)
@@ -347,12 +394,12 @@ def midx_sample(query, centres, wkk, indptr, indices, cd, num_neg, *, pos_ids=No
 
 
 @_on_device
-def midx_lookup(query, centres, wkk, indptr, indices, cd, u, *, pos_ids=None, cosine=False):
+def midx_lookup(query, centres, wkk, indptr, indices, cd, u, *, pos_ids=None, cosine=False, cp=None, item_logp=None):
     """rsa_midx_lookup: the draw of ``midx_sample`` for caller-supplied uniforms ``u`` [M, n, n_parts + 1]."""
     u = _need(u, torch.float32, 'u')
     if u.dim() != 3:
         raise ValueError('midx_lookup: u must be [M, n, n_parts + 1]')
-    a, out = _midx_args(query, centres, wkk, indptr, indices, cd, u.shape[1], pos_ids, cosine, 'midx_lookup')
+    a, out = _midx_args(query, centres, wkk, indptr, indices, cd, u.shape[1], pos_ids, cosine, 'midx_lookup', cp, item_logp)
     if u.shape[0] != a.n_queries or u.shape[2] != a.n_parts + 1:
         raise ValueError('midx_lookup: u must be [M, n, n_parts + 1]')
     a.u_in = ptr(u)

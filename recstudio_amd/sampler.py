@@ -17,7 +17,7 @@ from . import _native as nat
 from . import ops
 
 __all__ = ['Sampler', 'UniformSampler', 'MaskedUniformSampler', 'PopularSamplerModel', 'build_guide_table',
-           'build_cdf_lines', 'MIDXSamplerUniform', 'ClusterSamplerUniform']
+           'build_cdf_lines', 'MIDXSamplerUniform', 'ClusterSamplerUniform', 'MIDXSamplerPop', 'ClusterSamplerPop']
 
 
 class Sampler(torch.nn.Module):
@@ -303,12 +303,15 @@ class MIDXSamplerUniform(Sampler):
     ``torch.multinomial`` draws, not stream-equal (DESIGN.md)."""
 
     N_PARTS = 2
+    EUCLIDEAN = False            # the Euclidean scorer weighs the items inside a bucket: the Pop classes
 
     def __init__(self, num_items, num_clusters, scorer_fn=None):
-        from .scorer import CosineScorer, InnerProductScorer
-        if scorer_fn is not None and type(scorer_fn) not in (InnerProductScorer, CosineScorer):
-            raise NotImplementedError(f'{type(self).__name__}: scorer must be None, InnerProductScorer or CosineScorer '
-                                      f'(got {type(scorer_fn).__name__}; the Euclidean form needs the in-bucket popularity draw)')
+        from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer
+        allowed = (InnerProductScorer, CosineScorer) + ((EuclideanScorer,) if self.EUCLIDEAN else ())
+        if scorer_fn is not None and type(scorer_fn) not in allowed:
+            names = ', '.join(c.__name__ for c in allowed)
+            raise NotImplementedError(f'{type(self).__name__}: scorer must be None or one of {names} (got {type(scorer_fn).__name__}'
+                                      '; the Euclidean form draws by weight inside a bucket: MIDXSamplerPop / ClusterSamplerPop)')
         super().__init__(num_items, scorer_fn)
         if not 2 <= int(num_clusters) <= 64:
             raise ValueError(f'{type(self).__name__}: num_clusters must be in [2, 64], got {num_clusters}')
@@ -368,6 +371,14 @@ class MIDXSamplerUniform(Sampler):
             if not any(live):
                 break
         self._build_index(C, assign.to(torch.int64))
+        self._update(X)
+
+    def _update(self, X):
+        """What follows the index in the reference's ``_update``: nothing for the uniform forms (``wkk`` is the bucket counts)."""
+
+    def _draw_tables(self):
+        """The in-bucket tables handed to the draw kernel: none, the item is uniform in its bucket."""
+        return {}
 
     @torch.no_grad()
     def _build_index(self, C, cd):
@@ -414,7 +425,8 @@ class MIDXSamplerUniform(Sampler):
                     raise ValueError('`pos_items` must be [B] or [B, T]')
                 pos2 = pos_items.reshape(query.shape[0], -1)
             out = ops.midx_sample(query.detach().reshape(-1, query.shape[-1]), self._centres, self._wkk_dev, self._indptr32,
-                                  self._indices32, self._cd32, int(num_neg), pos_ids=pos2, cosine=self._cosine)
+                                  self._indices32, self._cd32, int(num_neg), pos_ids=pos2, cosine=self._cosine,
+                                  **self._draw_tables())
             neg, neg_prob = out['neg_ids'].view(*lead, num_neg), out['neg_logp'].view(*lead, num_neg)
             if pos_items is not None:
                 return out['pos_logp'].view(pos_items.shape), neg, neg_prob
@@ -426,7 +438,7 @@ class MIDXSamplerUniform(Sampler):
         with torch.no_grad():
             q = query.detach().reshape(-1, query.shape[-1])
             out = ops.midx_sample(q, self._centres, None, None, None, self._cd32, 0, pos_ids=pos_items.reshape(q.shape[0], -1),
-                                  cosine=self._cosine)
+                                  cosine=self._cosine, **self._draw_tables())
             return out['pos_logp'].view(pos_items.shape)
 
 
@@ -437,6 +449,62 @@ class ClusterSamplerUniform(MIDXSamplerUniform):
 
     def _centre_names(self):
         return ('c',)
+
+
+class _PopInBucket:
+    """The popularity-in-bucket form shared by ``MIDXSamplerPop`` and ``ClusterSamplerPop`` (recstudio/ann/sampler.py:391-423,
+    :533-559): the final item is drawn inside the chosen bucket in proportion to a weight -- the transformed popularity, times
+    exp(-||x||^2 / 2) with an ``EuclideanScorer`` -- and ``log`` of that weight enters both log-probabilities.
+
+    ``pop_count`` holds N entries, the counts of ids 1 .. N (``item_freq[1:]``, no padding entry), as the reference's ``_update``
+    requires; ``num_items`` is therefore N - 1 as in the reference (where nothing reads it either).  ``update`` builds the
+    reference's ``p`` [N + 1], ``cp`` [N] and weighted ``wkk`` on ``rsa_midx_weights``.
+
+    DEVIATION: the draw is the one that agrees with ``compute_item_p`` -- position = first with ``cp > u`` inside the bucket,
+    ``id = indices[pos] + 1``, ``log_neg_prob = logits + log p[id]`` -- not the reference's ``_sample_item_with_pop``
+    (``sampler.py:349-365``), which returns ids without the ``+ 1``, reads ``p`` at the sorted position and clamps an in-bucket
+    offset against an absolute position."""
+
+    EUCLIDEAN = True
+
+    def __init__(self, pop_count: Tensor, num_clusters, scorer=None, mode=1):
+        super().__init__(pop_count.shape[0], num_clusters, scorer)
+        from .scorer import EuclideanScorer
+        self._euclidean = isinstance(scorer, EuclideanScorer)
+        if mode == 0:                                           # sampler.py:399-404
+            pop_count = torch.log(pop_count + 1)
+        elif mode == 1:
+            pop_count = torch.log(pop_count + 1) + 1e-6
+        elif mode == 2:
+            pop_count = pop_count ** 0.75
+        self.pop_count = torch.nn.Parameter(pop_count, requires_grad=False)
+
+    @torch.no_grad()
+    def update(self, item_embs, max_iter=30):
+        if item_embs.dim() == 2 and self.pop_count.shape[0] != item_embs.shape[0]:
+            raise ValueError(f'{type(self).__name__}: pop_count has {self.pop_count.shape[0]} entries for {item_embs.shape[0]} rows '
+                             'of item_embs; it takes one count per item id 1 .. N and none for the padding id: item_freq[1:]')
+        super().update(item_embs, max_iter)
+
+    @torch.no_grad()
+    def _update(self, X):
+        P, K = self.N_PARTS, self.K
+        pop = self.pop_count.detach().to(X.device, torch.float32)
+        self.p, self._logp, wkk, self.cp = ops.midx_weights(pop, self._indptr32, self._indices32, K, P,
+                                                            table=X if self._euclidean else None, dim=X.shape[1])
+        self.wkk = wkk.view(K, K) if P == 2 else wkk
+        self._wkk_dev = wkk
+
+    def _draw_tables(self):
+        return dict(cp=self.cp, item_logp=self._logp)
+
+
+class MIDXSamplerPop(_PopInBucket, MIDXSamplerUniform):
+    """recstudio/ann/sampler.py:391-423: ``MIDXSamplerUniform`` with the popularity-weighted item inside the bucket."""
+
+
+class ClusterSamplerPop(_PopInBucket, ClusterSamplerUniform):
+    """recstudio/ann/sampler.py:533-559: ``ClusterSamplerUniform`` with the popularity-weighted item inside the bucket."""
 
 
 def sampler_kind(sampler):

@@ -11,6 +11,13 @@ lloyd   : one rsa_kmeans_step over N rows, two halves  vs  one k-means iteration
           membership matrices of the reference's kmeans(), sampler.py:19-31), at the largest N (<= --items, halved on
           out-of-memory) where those fit; reported per row.
 forward : ops.fused_forward with the drawn ids given, the launch the sampler's ids go to.
+weighted: the popularity-in-bucket draw (MIDXSamplerPop: cp / item_logp given)  vs  the uniform draw of the same library  vs  the
+          uniform draw of ANOTHER build of the library (--parent-lib, e.g. the parent commit's, built into a second directory with
+          tools/build_variant.sh or its own make) loaded into the same process  vs  the corrected weighted draw with torch ops
+          (the codebook stages as above, then one searchsorted over the bucket-offset CDF and two gathers) -- all four alternating.
+weights : rsa_midx_weights (p, log p, wkk, cp of one epoch)  vs  the reference's loop over the K^2 buckets with torch ops
+          (sampler.py:413-423: a cumsum and a division per bucket), and the same kernel for a Cluster index of K = 2 (two buckets of
+          N / 2 items, one workgroup each) next to one Lloyd pass of that codebook.
 Times are device events around each call, --reps calls after 3 warm-up calls, the two sides of a comparison interleaved
 (a, b, a, b, ...); the mean is reported, and the fastest and slowest call next to it as the spread."""
 import argparse
@@ -71,6 +78,59 @@ def torch_lloyd(rows, centres):
     return torch.mm(member.t(), rows) / member.sum(dim=0)[:, None], nearest, inertia
 
 
+def torch_weighted_draw(q, book0, book1, wkk, indptr, indices, cp_keyed, logp, n):
+    """The corrected popularity-in-bucket draw with torch ops: the two codebook stages of ``torch_draw`` from the weighted wkk, then
+    the first position of the bucket whose cp exceeds the uniform -- one searchsorted over ``cp_keyed`` = cp + 2 * (bucket of the
+    position), which is sorted over the whole table -- the id there and its log-weight."""
+    clusters, half = wkk.shape[0], q.shape[1] // 2
+    logit0 = torch.mm(q[:, :half], book0.t())
+    logit1 = torch.mm(q[:, half:], book1.t())
+    pr0, pr1 = logit0.softmax(dim=1), logit1.softmax(dim=1)
+    marginal = pr0 * torch.nn.functional.linear(pr1, wkk)
+    first = torch.multinomial(marginal, n, replacement=True)
+    conditional = (wkk[first] * pr1[:, None, :]).flatten(0, 1)
+    second = torch.multinomial(conditional, 1).view_as(first)
+    bucket = first * clusters + second
+    u = torch.rand(bucket.shape, device=q.device, dtype=torch.float64)
+    pos = torch.searchsorted(cp_keyed, u + 2.0 * bucket, right=True)
+    pos = torch.minimum(pos, indptr[bucket + 1] - 1)
+    ids = indices[pos] + 1
+    return ids, logit0.gather(1, first) + logit1.gather(1, second) + logp[ids]
+
+
+def torch_weights(w, indices, indptr_host, bucket_of_pos, n_buckets):
+    """The reference's _update with torch ops (sampler.py:413-423): p, the weighted wkk and the per-bucket cumsum / total loop
+    (the bucket bounds as host integers: no device read-back inside the loop)."""
+    p = torch.cat([w.new_ones(1), w])
+    cp = w[indices]
+    wkk = torch.zeros(n_buckets, dtype=w.dtype, device=w.device).index_add_(0, bucket_of_pos, cp)
+    for b in range(n_buckets):
+        start, end = indptr_host[b], indptr_host[b + 1]
+        if end > start:
+            run = cp[start:end].cumsum(0)
+            cp[start:end] = run / run[-1]
+    return p, torch.log(p), wkk, cp
+
+
+def parent_sampler(path):
+    """``midx_sample`` of another build of the library (the argument block is versioned: an older build reads the fields it knows)."""
+    import ctypes
+    from recstudio_amd import _native as nat, ops, rng
+    lib = ctypes.CDLL(path)
+    lib.rsa_midx_sample.restype = ctypes.c_int
+    lib.rsa_midx_sample.argtypes = [ctypes.POINTER(nat.MidxArgs), ctypes.c_void_p]
+
+    def sample(query, centres, wkk, indptr, indices, cd, n):
+        a, out = ops._midx_args(query, centres, wkk, indptr, indices, cd, n, None, False, 'parent midx_sample')
+        pc = rng.reserve(a.n_queries * a.num_neg * (a.n_parts + 1), 4, query.device, None)
+        a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
+        rc = lib.rsa_midx_sample(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f'parent rsa_midx_sample: status {rc}')
+        return out
+    return sample
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--items', type=int, default=10_000_000)
@@ -79,6 +139,7 @@ def main():
     ap.add_argument('--queries', type=int, default=65536)
     ap.add_argument('--neg', type=int, default=64)
     ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--parent-lib', default=None, help="another build of librecstudio_amd.so: its uniform draw is timed in the same run")
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'midx_bench.json'))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -127,6 +188,52 @@ def main():
     (fwd, *_), = timed([lambda: ops.fused_forward(weight, q, n, neg_ids=ids, pos_ids=pos)], a.reps)
     res['forward_given_ids_ms'] = fwd
     res['sampler_share_of_sample_plus_forward'] = ours / (ours + fwd)
+    del s, ids
+    torch.cuda.empty_cache()
+
+    # ---- the popularity-in-bucket form: the tables of one epoch, then the four draws
+    def row(t):
+        return dict(ms=t[0], ms_min_max=t[1:])
+    counts = torch.randint(0, 50, (N,), device=dev)
+    sp = ra.MIDXSamplerPop(counts, K, ra.InnerProductScorer(), mode=1)
+    sp.c0, sp.c1 = centres[0].clone(), centres[1].clone()
+    sp.update(X, max_iter=1)
+    pop = sp.pop_count.detach()
+    bucket_of_pos = torch.repeat_interleave(torch.arange(K * K, device=dev), sp.indptr[1:] - sp.indptr[:-1])
+    indptr_host = sp.indptr.tolist()
+    k_t, t_t = timed([lambda: ops.midx_weights(pop, sp._indptr32, sp._indices32, K, 2),
+                      lambda: torch_weights(pop, sp.indices, indptr_host, bucket_of_pos, K * K)], a.reps)
+    res['weights'] = dict(kernel=row(k_t), torch_bucket_loop=row(t_t), speedup=t_t[0] / k_t[0], buckets=K * K)
+    uniform_wkk = (sp.indptr[1:] - sp.indptr[:-1]).to(torch.float32)
+    state_u = (sp._centres, uniform_wkk, sp._indptr32, sp._indices32, sp._cd32)
+    state_w = (sp._centres, sp._wkk_dev, sp._indptr32, sp._indices32, sp._cd32)
+    cp_keyed = sp.cp.double() + 2.0 * bucket_of_pos
+    fns = [lambda: ops.midx_sample(q, *state_w, n, cp=sp.cp, item_logp=sp._logp), lambda: ops.midx_sample(q, *state_u, n),
+           lambda: torch_weighted_draw(q, sp.c0, sp.c1, sp.wkk, sp.indptr, sp.indices, cp_keyed, sp._logp, n)]
+    names = ['weighted', 'uniform', 'torch_weighted']
+    if a.parent_lib:
+        parent = parent_sampler(a.parent_lib)
+        fns.append(lambda: parent(q, *state_u, n))
+        names.append('uniform_parent_build')
+    times = timed(fns, a.reps)
+    res['draw_weighted'] = {k_: row(t) for k_, t in zip(names, times)}
+    res['draw_weighted']['speedup_over_torch'] = times[2][0] / times[0][0]
+    if a.parent_lib:
+        band = times[3][2] - times[3][1]
+        res['draw_weighted']['uniform_minus_parent_ms'] = times[1][0] - times[3][0]
+        res['draw_weighted']['parent_band_ms'] = band
+        res['draw_weighted']['uniform_within_parent_band'] = bool(times[1][0] - times[3][0] <= band)
+    del sp, cp_keyed, bucket_of_pos
+    torch.cuda.empty_cache()
+
+    # ---- Cluster, K = 2: two buckets of about N / 2 items, one workgroup each, next to one Lloyd pass of that codebook
+    c2 = X[torch.randperm(N, device=dev)[:2]].unsqueeze(0).contiguous()
+    sc = ra.ClusterSamplerPop(counts, 2, ra.InnerProductScorer(), mode=1)
+    sc.c = c2[0].clone()
+    sc.update(X, max_iter=1)
+    k_t, l_t = timed([lambda: ops.midx_weights(pop, sc._indptr32, sc._indices32, 2, 1), lambda: ops.kmeans_step(X, c2)], a.reps)
+    res['weights_cluster_k2'] = dict(kernel=row(k_t), lloyd_pass_same_codebook=row(l_t),
+                                     bucket_sizes=(sc.indptr[1:] - sc.indptr[:-1]).tolist())
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, 'w') as f:
         json.dump(res, f, indent=1)
