@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define RSA_ABI_VERSION 12  /* 12: rsa_rows_update_args.lr / beta1 / beta2 / eps are DOUBLES (the caller's own values: 1 - beta and the bias corrections are derived from them in double and rounded to fp32 once; as floats, 1 - float(0.999) was 1.29e-5 short of 0.001 on every touched row);
+#define RSA_ABI_VERSION 13  /* 13: rsa_scatter_rows_sorted_pairs_offset / rsa_bpr_sgd_pairs_offset / rsa_shard_backward_workspace_offsets (read-only: where the sorts leave their pairs, runs and flags inside the caller's workspaces);
+                               12: rsa_rows_update_args.lr / beta1 / beta2 / eps are DOUBLES (the caller's own values: 1 - beta and the bias corrections are derived from them in double and rounded to fp32 once; as floats, 1 - float(0.999) was 1.29e-5 short of 0.001 on every touched row);
                                11: rsa_bpr_sgd_prepare / _apply sort the step's user rows WITH its item rows (one radix sort; item_workspace = rsa_scatter_rows_sorted_workspace_bytes(n_queries, num_neg + 1, n_items), user_workspace unused) and draw the negatives inside that sort's first launch; sampler RSA_SAMPLER_GIVEN accepted (neg_ids is an input);
                                10: rsa_fullscore_lse_grad (flash forward: logsumexp + d/d query in one pass); rsa_fullscore_softmax_dw (d/d items of the full softmax with the softmax tile recomputed on the matrix cores: no
                                [B, N] matrix anywhere in the backward); rsa_fullscore_softmax_dq: probs may be NULL (not written);
@@ -526,6 +527,12 @@ int rsa_rows_update_sorted(const rsa_rows_update_args* args, rsa_stream_t stream
 int rsa_sort_step_elements(const rsa_rows_update_args* args, rsa_stream_t stream);
 int rsa_rows_update_presorted(const rsa_rows_update_args* args, rsa_stream_t stream);
 
+/* Read-only (ABI 13): byte offset of the sorted pairs -- n_queries * (num_neg + has_pos) 8-byte words (key << 32 | element),
+ * ascending by key, equal keys in element order; bit 31 of the element word set on the elements flagged solo -- inside the
+ * workspace of rsa_sort_step_elements / rsa_rows_update_sorted, from the workspace pointer rounded UP to 256 bytes.  Which of
+ * the sort's two buffers holds the result depends on the number of passes, i.e. on n_items.  < 0: bad sizes. */
+int64_t rsa_scatter_rows_sorted_pairs_offset(int64_t n_queries, int32_t num_neg, int64_t n_items);
+
 /* ---- The whole in-place SGD training step of a BPR two-tower model (nn.Embedding user and item tables, inner product,
  * BPRLoss, num_neg == 64) as TWO calls -- what `fit(train.fused_optimizer: 'sgd')` issues per batch.  Replaces, per step of
  * recstudio/model/basemodel/recommender.py:596-646: sampler.forward (ann/sampler.py:86-111 / :243-258), the two tower
@@ -579,6 +586,9 @@ typedef struct rsa_bpr_sgd_args {
 } rsa_bpr_sgd_args;
 int rsa_bpr_sgd_prepare(const rsa_bpr_sgd_args* args, rsa_stream_t stream);
 int rsa_bpr_sgd_apply(const rsa_bpr_sgd_args* args, rsa_stream_t stream);
+/* Read-only (ABI 13): the same for rsa_bpr_sgd_prepare's item_workspace: the n_queries * (num_neg + 1) item pairs (keys 0 ..
+ * n_items) followed by the n_queries user pairs (element n_queries * (num_neg + 1) + m, key n_items + 1 + user id). */
+int64_t rsa_bpr_sgd_pairs_offset(int64_t n_queries, int32_t num_neg, int64_t n_items, int64_t n_users);
 
 /* embedding_dense_backward: dst[ids[i]] += src[i] for ids != 0 (padding_idx=0).
  * Used for the user-table gradient.  dst [n_rows, dim] caller-zeroed. */
@@ -896,6 +906,11 @@ typedef struct rsa_shard_backward_args {
   int64_t workspace_bytes;
 } rsa_shard_backward_args;
 int64_t rsa_shard_backward_workspace_bytes(int64_t n_segments, int64_t stride, int64_t n_query_rows);
+/* Read-only (ABI 13): out5 <- byte offsets (from the workspace pointer rounded UP to 256 bytes) of what the owner entry points
+ * leave in that workspace: [0] the row-sorted pairs (n_segments * stride slots + the n_query_rows positives when pos_rows is
+ * given), [1] the query-sorted pairs of the slots, [2] run_start and [3] run_end (int32 [n_query_rows]), [4] the solo flags
+ * (uint8, element order).  n_rows: rows of the local item table (its key width picks the buffer of [0]). */
+int rsa_shard_backward_workspace_offsets(int64_t n_segments, int64_t stride, int64_t n_query_rows, int64_t n_rows, int64_t* out5);
 int rsa_shard_backward_segments(const rsa_shard_backward_args* args, rsa_stream_t stream);
 
 /* The stock BPR training step (loss_func.py:55-59 on the scores of baseretriever.py:153-171, and its backward) evaluated

@@ -256,9 +256,11 @@ SIGNATURES = {
     'rsa_fullscore_softmax_dq': (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_int64, c_void_p]),
     'rsa_scatter_rows_sorted_workspace_bytes': (c_int64, [c_int64, c_int32, c_int64]),
+    'rsa_scatter_rows_sorted_pairs_offset': (c_int64, [c_int64, c_int32, c_int64]),
     'rsa_rows_update_sorted': (c_int, [POINTER(RowsUpdateArgs), c_void_p]),
     'rsa_bpr_sgd_prepare': (c_int, [POINTER(BprSgdArgs), c_void_p]),
     'rsa_bpr_sgd_apply': (c_int, [POINTER(BprSgdArgs), c_void_p]),
+    'rsa_bpr_sgd_pairs_offset': (c_int64, [c_int64, c_int32, c_int64, c_int64]),
     'rsa_probs_t_query': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     'rsa_fullscore_lse_grad_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32]),
     'rsa_fullscore_lse_grad': (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -282,6 +284,7 @@ SIGNATURES = {
     'rsa_shard_unpack_segments': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
     'rsa_shard_backward_workspace_bytes': (c_int64, [c_int64, c_int64, c_int64]),
+    'rsa_shard_backward_workspace_offsets': (c_int, [c_int64, c_int64, c_int64, c_int64, POINTER(c_int64)]),
     'rsa_shard_backward_segments': (c_int, [POINTER(ShardBackwardArgs), c_void_p]),
     'rsa_shard_pos_score': (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                     c_int32, c_void_p]),
@@ -313,7 +316,7 @@ def build(verbose=False):
     return LIB_PATH
 
 
-ABI_VERSION = 12     # RSA_ABI_VERSION of include/recstudio_amd.h this binding was written against
+ABI_VERSION = 13     # RSA_ABI_VERSION of include/recstudio_amd.h this binding was written against
 
 
 def lib():

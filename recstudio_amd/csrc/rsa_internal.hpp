@@ -20,6 +20,11 @@ struct SortedLayout {        // a sorted scatter's workspace (sorted_workspace_b
 int64_t sorted_workspace_bytes(int64_t max_total);
 SortedLayout sorted_layout(void* workspace, int64_t max_total);
 
+// The *_offset entry points place a workspace over a made-up, 256-byte aligned base that is never dereferenced and report where
+// a region landed relative to it.
+inline char* layout_probe_base() { return reinterpret_cast<char*>((uintptr_t)1 << 20); }
+inline int64_t layout_probe_offset(const void* p) { return (int64_t)(reinterpret_cast<const char*>(p) - layout_probe_base()); }
+
 // flags[e] <- 1 for the elements that are alone on their row (and bit 31 of the pair's payload is set)
 int classify_solo(uint64_t* pairs, int64_t total, int64_t pad_row, int64_t drop_key, uint8_t* solo, hipStream_t s, const char* who);
 

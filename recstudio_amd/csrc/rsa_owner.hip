@@ -662,6 +662,10 @@ static int64_t own_workspace_bytes(int64_t slots, int64_t n_queries) {
   return align256(sizing.bytes()) + 256;
 }
 
+// key widths of the two sorts: rows 0 .. n_rows - 1 / queries 0 .. n_query_rows - 1 and the dead key behind them
+static unsigned own_row_bits(int64_t n_rows) { return radix_key_bits(n_rows + 1); }
+static unsigned own_query_bits(int64_t n_query_rows) { return radix_key_bits(n_query_rows + 1); }
+
 // run_start and run_end, both cleared
 static int clear_runs(const OwnLayout& W, int64_t n_queries, hipStream_t s, const char* who) {
   RSA_CHECK_HIP(hipMemsetAsync(W.run_start, 0, (size_t)(2 * align256(n_queries * 4)), s), who);
@@ -730,9 +734,9 @@ static int owner_prepare(const OwnCommon& c, OwnPrepared& P, OwnPrep mode, hipSt
   P.row_total = P.slots + (c.pos_rows ? c.n_query_rows : 0);
   P.L = sorted_layout(P.W.sorted_ws, P.slots + c.n_query_rows);
   P.inplace = c.item_target == c.item_local;
-  const unsigned row_bits = radix_key_bits(c.n_rows + 1);
+  const unsigned row_bits = own_row_bits(c.n_rows);
   P.row_sorted = radix_result(P.L.pairs_a, P.L.pairs_b, row_bits);
-  const unsigned q_bits = radix_key_bits(c.n_query_rows + 1);
+  const unsigned q_bits = own_query_bits(c.n_query_rows);
   P.q_sorted = c.keys_grouped ? nullptr : radix_result(P.W.qa, P.W.qb, q_bits);
   if (mode == OWN_PREP_LAYOUT) return RSA_OK;
   if (mode != OWN_PREP_SORTS) {
@@ -799,6 +803,26 @@ using namespace rsa;
 extern "C" int64_t rsa_shard_backward_workspace_bytes(int64_t n_segments, int64_t stride, int64_t n_query_rows) {
   if (n_segments < 0 || stride <= 0 || n_query_rows <= 0) return 0;
   return own_workspace_bytes(n_segments * stride, n_query_rows);
+}
+
+// Read-only: byte offsets (from the workspace pointer rounded up to 256 bytes) of what owner_prepare leaves behind -- row_sorted,
+// q_sorted, run_start, run_end, solo -- placed by owner_prepare's own calls over a made-up base
+extern "C" int rsa_shard_backward_workspace_offsets(int64_t n_segments, int64_t stride, int64_t n_query_rows, int64_t n_rows,
+                                                    int64_t* out5) {
+  RSA_CHECK_ARG(out5 != nullptr, "rsa_shard_backward_workspace_offsets: out5 is null");
+  RSA_CHECK_ARG(n_segments >= 0 && stride > RSA_SHARD_HDR && n_query_rows >= 1 && n_query_rows < (1ll << 31) && n_rows >= 1 &&
+                    n_rows < (1ll << 31) && n_segments * stride < (1ll << 31) - n_query_rows,
+                "rsa_shard_backward_workspace_offsets: bad sizes");
+  const int64_t slots = n_segments * stride;
+  Carver ws(layout_probe_base());
+  const OwnLayout W = carve_own(ws, slots, n_query_rows);
+  const SortedLayout L = sorted_layout(W.sorted_ws, slots + n_query_rows);
+  out5[0] = layout_probe_offset(radix_result(L.pairs_a, L.pairs_b, own_row_bits(n_rows)));
+  out5[1] = layout_probe_offset(radix_result(W.qa, W.qb, own_query_bits(n_query_rows)));
+  out5[2] = layout_probe_offset(W.run_start);
+  out5[3] = layout_probe_offset(W.run_end);
+  out5[4] = layout_probe_offset(W.solo);
+  return RSA_OK;
 }
 
 extern "C" int rsa_shard_backward_segments(const rsa_shard_backward_args* a, rsa_stream_t stream) {

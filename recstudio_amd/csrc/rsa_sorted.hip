@@ -467,6 +467,21 @@ static uint64_t* step_sorted(const SortedLayout& L, int64_t n_items) {
   return radix_result(L.pairs_a, L.pairs_b, radix_key_bits(n_items + 1));      // ids 0 .. n_items-1 and the drop key n_items
 }
 
+// Read-only: where a sort leaves its pairs, as a byte offset from the workspace pointer rounded up to 256 bytes (Carver's rule).
+// Laid out over a made-up base (layout_probe_base) by the very calls the sorts make, so the two cannot disagree.
+extern "C" int64_t rsa_scatter_rows_sorted_pairs_offset(int64_t n_queries, int32_t num_neg, int64_t n_items) {
+  if (n_queries <= 0 || num_neg < 0 || n_items < 1 || n_items >= (1ll << 31)) return -1;
+  const SortedLayout L = sorted_layout(layout_probe_base(), n_queries * (int64_t)(num_neg + 1));
+  return layout_probe_offset(step_sorted(L, n_items));
+}
+
+extern "C" int64_t rsa_bpr_sgd_pairs_offset(int64_t n_queries, int32_t num_neg, int64_t n_items, int64_t n_users) {
+  if (n_queries <= 0 || num_neg < 0 || n_items < 1 || n_users < 1 || n_items + n_users + 2 >= (1ll << 31)) return -1;
+  const int64_t total = n_queries * (int64_t)(num_neg + 1) + n_queries;      // sort_step_all's
+  const SortedLayout L = sorted_layout(layout_probe_base(), total);
+  return layout_probe_offset(radix_result(L.pairs_a, L.pairs_b, step_all_bits(n_items, n_users)));
+}
+
 // (item id, element) pairs of a step, radix-sorted by id into the workspace; with `solo` also the classification pass
 static int sort_step_elements(const rsa_rows_update_args& a, uint8_t* solo, hipStream_t s, const char* who) {
   RSA_CHECK_ARG(a.n_queries >= 0 && a.num_neg >= 1 && a.n_items >= 1 && a.n_items < (1ll << 31), "%s: bad sizes", who);

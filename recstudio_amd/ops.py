@@ -806,7 +806,9 @@ def _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, who):
 def sort_step_elements(pos_ids, neg_ids, n_items, pad_row=0, want_solo=True):
     """rsa_sort_step_elements: the step's (item id, element) pairs sorted by id in a workspace, and the classification
     ``solo [M, 1 + n]`` uint8 (column 0 = the positive): 1 where no other element of the step touches that item row.
-    -> (solo, workspace) for ``fused_forward(inplace_update=...)`` + ``scatter_rows_presorted``."""
+    -> (solo, workspace) for ``fused_forward(inplace_update=...)`` + ``scatter_rows_presorted``.
+    The sorted pairs (int64 ``key << 32 | element``, bit 31 of the element word set on the solo ones) start
+    ``rsa_scatter_rows_sorted_pairs_offset(M, n, n_items)`` bytes into ``workspace``."""
     neg_ids = _need(neg_ids, torch.int64, 'neg_ids')
     pos_ids = _need_opt(pos_ids, torch.int64, 'pos_ids')
     M = pos_ids.numel() if pos_ids is not None else neg_ids.shape[0]

@@ -208,7 +208,7 @@ def midx_block(nat, **kw):
 def test_cp_and_item_logp_go_together(nat, entry):
     lib = nat.lib()
     assert nat.MidxArgs._fields_[-2:] == [('cp', ctypes.c_void_p), ('item_logp', ctypes.c_void_p)]
-    assert nat.ABI_VERSION == 12
+    assert nat.ABI_VERSION == 13
     for kw in (dict(cp=4096), dict(item_logp=4096)):
         assert getattr(lib, entry)(ctypes.byref(midx_block(nat, **kw)), None) == -1
         assert b'cp' in lib.rsa_last_error()
