@@ -252,6 +252,64 @@ typedef struct rsa_kmeans_args {
 int64_t rsa_kmeans_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_clusters);
 int rsa_kmeans_step(const rsa_kmeans_args* args, rsa_stream_t stream);
 
+/* LSHSampler.update, the hash -- recstudio/ann/sampler.py:600-604 -- over rows [row_offset, row_offset + n_rows) of `table`
+ * (row_stride floats apart); every row is read once.  Bit (k, l) of a row x is <x, W[:, k, l]> > 0 (strict; the reference
+ * normalises x first, which does not move the sign), codes[l][row] = sum_k bit(k, l) * 2^(n_bits - 1 - k).  The dot product's
+ * summation order: recstudio_amd/csrc/rsa_lsh.hip.  No atomics and no accumulation across rows: two runs are bit-equal.
+ * Limits: dim % 8 == 0, dim <= 256, 1 <= n_bits <= 16, n_bits * n_table <= 64 (one lane of a wave per projection). */
+typedef struct rsa_lsh_hash_args {
+  int64_t size;                /* sizeof(rsa_lsh_hash_args) */
+  const float* table;
+  int64_t n_rows;
+  int64_t row_stride;          /* floats, a multiple of 4 */
+  int64_t row_offset;          /* first row (1 for an embedding table whose row 0 is the padding row) */
+  int32_t dim;
+  int32_t n_bits;              /* K */
+  int32_t n_table;             /* L */
+  int32_t _pad;
+  const float* weight_vectors; /* [dim, n_bits, n_table], LSHSampler.weight_vectors */
+  int32_t* codes;              /* [n_table, n_rows] out */
+} rsa_lsh_hash_args;
+int rsa_lsh_hash(const rsa_lsh_hash_args* args, rsa_stream_t stream);
+
+/* LSHSampler.forward -- recstudio/ann/sampler.py:609-677: negatives from the union (with multiplicity) of the query's buckets
+ * in the n_table hash tables.  The query is hashed as above; cnt_l = size of its bucket in table l, cum = inclusive prefix of
+ * cnt over l, len = cum[n_table - 1] (64 bits).  Draw j of query q with its uniform u:
+ *   r = floor(fl32(u * fl32(len))) (ONE fp32 multiply), clamped to len - 1;  t = #{l : cum_l <= r} (an empty table is never
+ *   chosen);  item = indices[t][indptr[t][code_t] + r - cum_{t-1}];  neg_ids = item + 1.
+ *   c = cos(query, item_embs[item]) clamped to [-1, 1] (0 when either norm is 0), p = 1 - acos(c) / pi,
+ *   w = 1 - (1 - p^K)^L evaluated as -expm1(L * log1p(-p^K)) in double,  neg_logp = fl32(log(w / len + log_eps)).
+ * A query with len == 0: neg_ids = 1 + min(floor(fl32(u * fl32(n_items))), n_items - 1), neg_logp = 0.
+ * Uniforms: element q * num_neg + j of ONE torch.rand(n_queries, num_neg) on the device stream ("Philox state").
+ * Same limits as rsa_lsh_hash_args; n_items < 2^31 - 1. */
+typedef struct rsa_lsh_args {
+  int64_t size;                /* sizeof(rsa_lsh_args) */
+  const float* query;          /* [n_queries, dim] */
+  int64_t n_queries;
+  int32_t dim;
+  int32_t n_bits;              /* K */
+  int32_t n_table;             /* L */
+  int32_t num_neg;
+  const float* weight_vectors; /* [dim, n_bits, n_table] */
+  const int32_t* indptr;       /* [n_table, 2^n_bits + 1] bucket b of table l holds indices[l][indptr[l][b] .. indptr[l][b + 1]) */
+  const int32_t* indices;      /* [n_table, n_items] item ids - 1, grouped by bucket */
+  const float* item_embs;      /* [n_items, dim] the rows the index was built from (the snapshot of update) */
+  int64_t n_items;             /* items WITHOUT the padding id */
+  const float* u_in;           /* rsa_lsh_lookup: the uniforms [n_queries, num_neg] */
+  int64_t* neg_ids;            /* [n_queries, num_neg] out */
+  float* neg_logp;             /* [n_queries, num_neg] out */
+  int32_t* codes_out;          /* nullable [n_queries, n_table] out: the query's codes */
+  float* u_out;                /* nullable out (rsa_lsh_sample: the uniforms drawn) */
+  double log_eps;              /* added inside the log: 1e-12 with pos_items in the reference, 0 without */
+  uint64_t seed, offset;       /* "Philox state" (rsa_lsh_sample) */
+  uint32_t grid_threads;
+  uint32_t _pad;
+  uint64_t elem_base;
+} rsa_lsh_args;
+int rsa_lsh_sample(const rsa_lsh_args* args, rsa_stream_t stream);
+/* The same draw for caller-supplied uniforms (the tests hit every table boundary with it). */
+int rsa_lsh_lookup(const rsa_lsh_args* args, rsa_stream_t stream);
+
 /* PopularSamplerModel.compute_item_p -- recstudio/ann/sampler.py:257-258:
  * logp[i] = log(pop_prob[ids[i]]). */
 int rsa_item_logp(const float* pop_prob, int64_t n_items, const int64_t* ids, int64_t numel,

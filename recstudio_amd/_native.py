@@ -211,6 +211,26 @@ class KmeansArgs(_Sized):
     ]
 
 
+class LshHashArgs(_Sized):
+    """struct rsa_lsh_hash_args."""
+    _fields_ = [
+        ('size', c_int64), ('table', c_void_p), ('n_rows', c_int64), ('row_stride', c_int64), ('row_offset', c_int64),
+        ('dim', c_int32), ('n_bits', c_int32), ('n_table', c_int32), ('_pad', c_int32), ('weight_vectors', c_void_p),
+        ('codes', c_void_p),
+    ]
+
+
+class LshArgs(_Sized):
+    """struct rsa_lsh_args."""
+    _fields_ = [
+        ('size', c_int64), ('query', c_void_p), ('n_queries', c_int64), ('dim', c_int32), ('n_bits', c_int32),
+        ('n_table', c_int32), ('num_neg', c_int32), ('weight_vectors', c_void_p), ('indptr', c_void_p), ('indices', c_void_p),
+        ('item_embs', c_void_p), ('n_items', c_int64), ('u_in', c_void_p), ('neg_ids', c_void_p), ('neg_logp', c_void_p),
+        ('codes_out', c_void_p), ('u_out', c_void_p), ('log_eps', c_double), ('seed', c_uint64), ('offset', c_uint64),
+        ('grid_threads', c_uint32), ('_pad', c_uint32), ('elem_base', c_uint64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -219,7 +239,7 @@ STRUCTS = {
     'rsa_shard_owner_bpr_args': ShardOwnerBprArgs, 'rsa_popular_args': PopularArgs, 'rsa_loss_args': LossArgs,
     'rsa_rows_update_args': RowsUpdateArgs, 'rsa_bpr_sgd_args': BprSgdArgs, 'rsa_seg_gather_args': SegGatherArgs,
     'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
-    'rsa_midx_weights_args': MidxWeightsArgs,
+    'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -238,6 +258,9 @@ SIGNATURES = {
     'rsa_midx_weights': (c_int, [POINTER(MidxWeightsArgs), c_void_p]),
     'rsa_kmeans_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
     'rsa_kmeans_step': (c_int, [POINTER(KmeansArgs), c_void_p]),
+    'rsa_lsh_hash': (c_int, [POINTER(LshHashArgs), c_void_p]),
+    'rsa_lsh_sample': (c_int, [POINTER(LshArgs), c_void_p]),
+    'rsa_lsh_lookup': (c_int, [POINTER(LshArgs), c_void_p]),
     'rsa_item_logp': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     'rsa_embedding_gather': (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     'rsa_fused_sample_gather_score': (c_int, [POINTER(FusedArgs), c_void_p]),

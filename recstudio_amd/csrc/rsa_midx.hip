@@ -31,18 +31,14 @@
 // accumulated by one thread per COLUMN walking the tile's rows in order -- no float atomics, no [N, K] matrix.  Every workgroup
 // leaves its partial sums / counts / loss in the workspace; a second launch adds the partials in workgroup order (in double).
 // The grid is a function of the row count alone, so two runs over the same input are bit-equal.
-#include <atomic>
-
-#include "rsa_common.hpp"
 #include "rsa_internal.hpp"
+#include "rsa_lds.hpp"
 
 namespace rsa {
 
 constexpr int MIDX_MAX_K = 64, MIDX_MAX_DIM = 256;
-constexpr int CPAD = 4;                 // floats of padding per centre row in LDS: one ds_read_b128 width
 constexpr int KM_TILE = 16;             // rows per tile of the Lloyd step (4 per wave)
 constexpr int KM_MAX_GRID = 512;
-constexpr int64_t LDS_STATIC_LIMIT = 64 << 10, LDS_LIMIT = 160 << 10;
 
 extern __shared__ __attribute__((aligned(16))) float midx_smem[];
 
@@ -59,14 +55,6 @@ __device__ __forceinline__ void stage_centres(float* cs, const float* __restrict
     *reinterpret_cast<float4*>(cs + r * stride + c * 4) = reinterpret_cast<const float4*>(centres)[i];
   }
 }
-
-__device__ __forceinline__ void fma4(float4& acc, const float4& a, const float4& b) {
-  acc.x = __fmaf_rn(a.x, b.x, acc.x);
-  acc.y = __fmaf_rn(a.y, b.y, acc.y);
-  acc.z = __fmaf_rn(a.z, b.z, acc.z);
-  acc.w = __fmaf_rn(a.w, b.w, acc.w);
-}
-__device__ __forceinline__ float sum4(const float4& a) { return (a.x + a.y) + (a.z + a.w); }
 
 // x / max(||x||, 1e-12) for a row held one float4 per lane (lanes past the row hold zeros)
 __device__ __forceinline__ float4 normalize_row(float4 v) {
@@ -567,20 +555,6 @@ static int check_codebook(const char* fn, int dim, int parts, int K) {
   RSA_CHECK_ARG(K >= 2 && K <= MIDX_MAX_K, "%s: n_clusters must be in [2, %d], got %d", fn, MIDX_MAX_K, K);
   RSA_CHECK_ARG(dim >= 8 && dim <= MIDX_MAX_DIM && dim % 8 == 0, "%s: dim must be a multiple of 8 in [8, %d], got %d", fn,
                 MIDX_MAX_DIM, dim);
-  return RSA_OK;
-}
-
-// dynamic LDS above 64 KB has to be granted per kernel and device: asked for once, and again only for a larger size
-template <auto kern>
-static int allow_lds(int64_t bytes, const char* who) {
-  constexpr int MAX_DEV = 64;
-  static std::atomic<int64_t> granted[MAX_DEV];            // zero-initialised: nothing granted yet
-  if (bytes <= LDS_STATIC_LIMIT) return RSA_OK;
-  int dev = 0;
-  RSA_CHECK_HIP(hipGetDevice(&dev), who);
-  if (dev >= 0 && dev < MAX_DEV && granted[dev].load(std::memory_order_relaxed) >= bytes) return RSA_OK;
-  RSA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), who);
-  if (dev >= 0 && dev < MAX_DEV) granted[dev].store(bytes, std::memory_order_relaxed);
   return RSA_OK;
 }
 

@@ -407,6 +407,100 @@ def midx_lookup(query, centres, wkk, indptr, indices, cd, u, *, pos_ids=None, co
     return out
 
 
+def _hash_shape(weight_vectors, who):
+    """(dim, n_bits, n_table) of ``LSHSampler.weight_vectors`` [d, K, L], with the limits of rsa_lsh_hash_args checked."""
+    if weight_vectors.dim() != 3:
+        raise ValueError(f'{who}: weight_vectors must be [dim, n_bits, n_table], got {tuple(weight_vectors.shape)}')
+    dim, K, L = (int(v) for v in weight_vectors.shape)
+    if dim % 8 or not 8 <= dim <= 256:
+        raise ValueError(f'{who}: embed_dim must be a multiple of 8 and at most 256, got {dim}')
+    if not 1 <= K <= 16:
+        raise ValueError(f'{who}: n_bits must be in [1, 16], got {K}')
+    if L < 1 or K * L > 64:
+        raise ValueError(f'{who}: n_bits * n_table must be at most 64 (one lane of a wave per projection), got {K} * {L}')
+    return dim, K, L
+
+
+@_on_device
+def lsh_hash(table, weight_vectors):
+    """rsa_lsh_hash: the LSH codes of the rows of ``table`` [N, d] (any row stride: ``weight[1:]`` is read in place) under the
+    projections ``weight_vectors`` [d, K, L] -> int32 [L, N]; bit (k, l) is ``<row, W[:, k, l]> > 0``, the first bit the most
+    significant."""
+    weight_vectors = _need(weight_vectors, torch.float32, 'weight_vectors')
+    table = _need_view(table, torch.float32, 'table')
+    dim, K, L = _hash_shape(weight_vectors, 'lsh_hash')
+    if table.dim() != 2 or table.shape[1] != dim or table.shape[0] < 1:
+        raise ValueError(f'lsh_hash: table must be [N >= 1, {dim}], got {tuple(table.shape)}')
+    base, stride, skip, table = _table_view(table, dim)
+    n = table.shape[0]
+    codes = torch.empty(L, n, dtype=torch.int32, device=table.device)
+    a = nat.LshHashArgs()
+    a.table, a.n_rows, a.row_stride, a.row_offset = base, n, stride, skip
+    a.dim, a.n_bits, a.n_table = dim, K, L
+    a.weight_vectors, a.codes = ptr(weight_vectors), ptr(codes)
+    _launch('rsa_lsh_hash', ctypes.byref(a))
+    return codes
+
+
+def _lsh_args(query, weight_vectors, indptr, indices, item_embs, num_neg, eps, want_codes, who):
+    query = _need(query, torch.float32, 'query')
+    weight_vectors = _need(weight_vectors, torch.float32, 'weight_vectors')
+    dim, K, L = _hash_shape(weight_vectors, who)
+    if query.dim() != 2 or query.shape[1] != dim:
+        raise ValueError(f'{who}: query must be [M, {dim}], got {tuple(query.shape)}')
+    indptr, indices = _need(indptr, torch.int32, 'indptr'), _need(indices, torch.int32, 'indices')
+    item_embs = _need(item_embs, torch.float32, 'item_embs')
+    if item_embs.dim() != 2 or item_embs.shape[1] != dim or item_embs.shape[0] < 1:
+        raise ValueError(f'{who}: item_embs must be [N >= 1, {dim}], got {tuple(item_embs.shape)}')
+    N = item_embs.shape[0]
+    if tuple(indptr.shape) != (L, (1 << K) + 1) or tuple(indices.shape) != (L, N):
+        raise ValueError(f'{who}: indptr must be [{L}, {(1 << K) + 1}] and indices [{L}, {N}], got {tuple(indptr.shape)} and '
+                         f'{tuple(indices.shape)}')
+    if eps < 0:
+        raise ValueError(f'{who}: eps must not be negative')
+    M, n, dev = query.shape[0], int(num_neg), query.device
+    out = dict(neg_ids=torch.empty(M, n, dtype=torch.int64, device=dev), neg_logp=torch.empty(M, n, dtype=torch.float32, device=dev))
+    a = nat.LshArgs()
+    a.query, a.n_queries, a.dim, a.n_bits, a.n_table, a.num_neg = ptr(query), M, dim, K, L, n
+    a.weight_vectors, a.indptr, a.indices, a.item_embs, a.n_items = ptr(weight_vectors), ptr(indptr), ptr(indices), ptr(item_embs), N
+    a.neg_ids, a.neg_logp, a.log_eps = ptr(out['neg_ids']), ptr(out['neg_logp']), float(eps)
+    if want_codes:
+        out['codes'] = torch.empty(M, L, dtype=torch.int32, device=dev)
+        a.codes_out = ptr(out['codes'])
+    return a, out, (query, weight_vectors, indptr, indices, item_embs)
+
+
+@_on_device
+def lsh_sample(query, weight_vectors, indptr, indices, item_embs, num_neg, *, eps=0.0, generator=None, want_u=False,
+               want_codes=False):
+    """rsa_lsh_sample: negatives of LSHSampler for ``query`` [M, d] from the index ``indptr`` int32 [L, 2^K + 1] / ``indices``
+    int32 [L, N] over the snapshot ``item_embs`` [N, d]; the uniforms are those of ``torch.rand(M, num_neg)`` on the device
+    generator (advanced as that call would).  ``eps`` is added inside the log (1e-12 with pos_items in the reference, 0 without).
+    -> dict(neg_ids [M, n] int64, neg_logp [M, n], u [M, n] with ``want_u``, codes int32 [M, L] with ``want_codes``)."""
+    a, out, keep = _lsh_args(query, weight_vectors, indptr, indices, item_embs, num_neg, eps, want_codes, 'lsh_sample')
+    numel = a.n_queries * a.num_neg
+    if numel:
+        pc = rng.reserve(numel, 4, query.device, generator)
+        a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
+    if want_u:
+        out['u'] = torch.empty(a.n_queries, a.num_neg, dtype=torch.float32, device=query.device)
+        a.u_out = ptr(out['u'])
+    _launch('rsa_lsh_sample', ctypes.byref(a))
+    return out
+
+
+@_on_device
+def lsh_lookup(query, weight_vectors, indptr, indices, item_embs, u, *, eps=0.0, want_codes=False):
+    """rsa_lsh_lookup: the draw of ``lsh_sample`` for caller-supplied uniforms ``u`` [M, n]."""
+    u = _need(u, torch.float32, 'u')
+    if u.dim() != 2 or u.shape[0] != query.shape[0]:
+        raise ValueError('lsh_lookup: u must be [M, n]')
+    a, out, keep = _lsh_args(query, weight_vectors, indptr, indices, item_embs, u.shape[1], eps, want_codes, 'lsh_lookup')
+    a.u_in = ptr(u)
+    _launch('rsa_lsh_lookup', ctypes.byref(a))
+    return out
+
+
 # ------------------------------------------------------------------ gathers
 @_on_device
 def embedding_gather(table, ids):

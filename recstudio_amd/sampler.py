@@ -17,7 +17,7 @@ from . import _native as nat
 from . import ops
 
 __all__ = ['Sampler', 'UniformSampler', 'MaskedUniformSampler', 'PopularSamplerModel', 'build_guide_table',
-           'build_cdf_lines', 'MIDXSamplerUniform', 'ClusterSamplerUniform', 'MIDXSamplerPop', 'ClusterSamplerPop']
+           'build_cdf_lines', 'MIDXSamplerUniform', 'ClusterSamplerUniform', 'MIDXSamplerPop', 'ClusterSamplerPop', 'LSHSampler']
 
 
 class Sampler(torch.nn.Module):
@@ -505,6 +505,69 @@ class MIDXSamplerPop(_PopInBucket, MIDXSamplerUniform):
 
 class ClusterSamplerPop(_PopInBucket, ClusterSamplerUniform):
     """recstudio/ann/sampler.py:533-559: ``ClusterSamplerUniform`` with the popularity-weighted item inside the bucket."""
+
+
+class LSHSampler(UniformSampler):
+    """recstudio/ann/sampler.py:562-707: negatives from the union of the query's buckets in ``n_table`` sign-random-projection
+    hash tables of ``n_bits`` bits each, with the collision probability ``1 - (1 - p^K)^L`` in the log-proposal.  ``update`` (once
+    per epoch) hashes the table on ``rsa_lsh_hash`` and builds the reference's ``indices`` [L, N] / ``indptr`` [L, 2^K + 1] (int64,
+    a stable sort per table); ``forward`` is one launch of ``rsa_lsh_sample``.  The uniforms are those of the reference's one
+    ``torch.rand(B, num_neg)`` on the device generator, so a query with a non-empty bucket gets the reference's ids.
+
+    DEVIATIONS:
+    * a query whose buckets are all empty draws uniformly over 1 .. N from its own uniforms of that call (log-probability 0);
+      the reference spends a separate ``torch.randint`` on those rows, which shifts the stream -- distribution-equal;
+    * without ``pos_items`` the reference returns the ids before that patch and ``log(inf)`` for such rows; here both forms
+      return the patched ids and 0;
+    * the cosine is clamped to [-1, 1] (the reference's ``acos`` returns NaN past it), and the position ``floor(u * len)`` to
+      ``len - 1`` also where ``float(len)`` rounds above ``len``;
+    * ``1 - (1 - p^K)^L`` is evaluated as ``-expm1(L * log1p(-p^K))`` in double, without the reference's fp32 cancellation."""
+
+    def __init__(self, num_items: int, n_dims: int, n_bits: int = 4, n_table: int = 16, device='cuda', scorer_fn=None):
+        from .scorer import InnerProductScorer
+        if scorer_fn is not None and type(scorer_fn) is not InnerProductScorer:
+            raise NotImplementedError(f'LSHSampler: scorer must be None or InnerProductScorer, got {type(scorer_fn).__name__}')
+        super().__init__(num_items, scorer_fn)
+        n_dims, n_bits, n_table = int(n_dims), int(n_bits), int(n_table)
+        if n_dims % 8 or not 8 <= n_dims <= 256:
+            raise ValueError(f'LSHSampler: n_dims must be a multiple of 8 and at most 256, got {n_dims}')
+        if not 1 <= n_bits <= 16 or n_table < 1 or n_bits * n_table > 64:
+            raise ValueError(f'LSHSampler: n_bits must be in [1, 16] and n_bits * n_table at most 64, got {n_bits} * {n_table}')
+        self.n_dims, self.n_bits, self.n_table, self.device = n_dims, n_bits, n_table, device
+        w = torch.rand(n_dims, n_bits, n_table)                                 # sampler.py:680-683, the CPU generator
+        self.weight_vectors = torch.nn.Parameter((w / torch.norm(w, dim=0, keepdim=True)).to(device), requires_grad=False)
+        base = torch.from_numpy(1 << np.arange(n_bits - 1, -1, -1)).type(torch.float).to(device)
+        self.K_base_vec = torch.nn.Parameter(base, requires_grad=False)
+        self.indptr, self.indices = None, None
+        self.item_embs = None
+
+    @torch.no_grad()
+    def update(self, item_embs):
+        X = item_embs.detach()
+        if not X.is_cuda or X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] != self.n_dims:
+            raise RuntimeError(f'LSHSampler.update: item_embs must be an fp32 [N, {self.n_dims}] tensor on the GPU')
+        W = self.weight_vectors.detach().to(X.device)
+        codes = ops.lsh_hash(X, W).to(torch.int64)                              # [L, N]
+        self.item_embs = X.clone()
+        # construct_index per table (sampler.py:38-45, :686-707)
+        self.indices = torch.sort(codes, dim=1, stable=True)[1]
+        nb = 1 << self.n_bits
+        rows = torch.arange(self.n_table, device=X.device).unsqueeze(1)
+        count = torch.bincount((codes + rows * nb).flatten(), minlength=self.n_table * nb).view(self.n_table, nb)
+        self.indptr = torch.cat([count.new_zeros(self.n_table, 1), count.cumsum(1)], dim=1)
+        self._indices32, self._indptr32 = self.indices.to(torch.int32), self.indptr.to(torch.int32)
+
+    def forward(self, query, num_neg, pos_items=None):
+        if self.item_embs is None:
+            raise RuntimeError('LSHSampler: call update(item_embs) before sampling (fit does, once per epoch)')
+        if not isinstance(query, Tensor) or query.dim() != 2:
+            raise ValueError('LSHSampler: `query` need to be 2-dimensional.')
+        with torch.no_grad():
+            out = ops.lsh_sample(query.detach(), self.weight_vectors.detach(), self._indptr32, self._indices32, self.item_embs,
+                                 int(num_neg), eps=1e-12 if pos_items is not None else 0.0)
+            if pos_items is not None:
+                return ops.zero_logp_like(pos_items), out['neg_ids'], out['neg_logp']
+            return out['neg_ids'], out['neg_logp']
 
 
 def sampler_kind(sampler):
