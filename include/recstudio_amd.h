@@ -719,6 +719,65 @@ typedef struct rsa_fullscore_args {
 } rsa_fullscore_args;
 int rsa_fullscore(const rsa_fullscore_args* args, rsa_stream_t stream);
 
+/* BaseRetriever.sampling(method='brute') -- baseretriever.py:299-328 -- and RetrieverSampler (recstudio/ann/sampler.py:61-78)
+ * without the [B, N] matrix: num_neg ids per query, with replacement, from softmax(score(q, .) * inv_t) over item rows
+ * [1, n_items), the ids of user_hist [n_query, hist_len] (0-padded, duplicates allowed) removed when it is given.
+ *   lse [n_query]        logsumexp of the scaled scores over the whole catalog (history included, as the reference's softmax).
+ *   neg_logp             s_id * inv_t - lse: the log of the masked, NOT renormalised row, as the reference takes it.
+ *   pos_logp [., n_pos]  the same for pos_ids; -inf for the padding id 0 (log(gather(pad(softmax)))) and for ids >= n_items.
+ * Two-level inverse CDF over blocks of G consecutive items (G = 64, 128 or 256, fixed when the library is built; block g =
+ * items 1 + g * G ...; n_blocks = ceil((n_items - 1) / G)), two uniforms per draw:
+ *   mass[q][g] = sum over the block of exp(s - lse), from one fp32-MFMA pass over the catalog; a block that holds a history
+ *                id is summed again without the history (never by subtraction), a block wholly in the history is exactly 0;
+ *   cum[q][g]  = running sum of mass in fixed point (a power-of-two unit per row: exact, monotone), rounded to fp32 once per entry;
+ *   block      = the first g with cum[g] > fl32(u1 * cum[last]) (when rounding leaves none: the first g with cum[g] == cum[last]);
+ *   item       = the block's rows are scored again with plain fp32 FMAs, w_i = exp(s_i - max of the block) in 2^-40 fixed point
+ *                (history, id 0 and ids >= n_items weigh 0): the first i whose running sum exceeds floor(u2 * total).
+ * An item of weight 0 is never returned.  A row whose every item weighs 0 gets id 0 with log-prob -inf (the checks below run on
+ * the host and cannot see it).  The ids are NOT those of torch.multinomial for the same seed; the distribution and the
+ * log-probabilities are.  Uniforms: elements (q * num_neg + j) * 2 + {0, 1} of ONE torch.rand(n_query, num_neg, 2) on the device
+ * stream ("Philox state"); rsa_softmax_lookup takes them from u_in instead.  dim must be 32, 64 or 128 (RSA_ERR_UNSUPPORTED
+ * otherwise); score_mode / item_aux (64 floats of padding) / query_aux as in rsa_fullscore.  mass / cum: nullable
+ * [n_query, n_blocks] outputs (the tables the draw used).  num_neg = 0 leaves lse (and pos_logp).  All arguments are checked
+ * before the first HIP call; nothing is allocated and nothing synchronises.  Extra memory: 16 bytes per (query, block). */
+int64_t rsa_softmax_sample_workspace_bytes(int64_t n_query, int64_t n_items);
+/* G of this build (callers size mass / cum with it). */
+int32_t rsa_softmax_sample_block(void);
+typedef struct rsa_softmax_sample_args {
+  int64_t size;                /* sizeof(rsa_softmax_sample_args) */
+  const float* item_table;     /* [n_items, dim], row 0 is the padding row */
+  int64_t n_items;
+  int32_t dim;
+  int32_t score_mode;          /* rsa_score_mode */
+  float inv_t;                 /* 1 / temperature, > 0 */
+  int32_t num_neg;
+  const float* query;          /* [n_query, dim] */
+  int64_t n_query;
+  const int64_t* pos_ids;      /* nullable [n_query, n_pos] */
+  int32_t n_pos;
+  int32_t hist_len;            /* 0: nothing is excluded */
+  const int64_t* user_hist;    /* nullable [n_query, hist_len] */
+  const float* item_aux;       /* nullable */
+  const float* query_aux;      /* nullable */
+  uint64_t seed, offset;       /* "Philox state" (rsa_softmax_sample) */
+  uint32_t grid_threads;
+  uint32_t _pad;
+  uint64_t elem_base;
+  const float* u_in;           /* rsa_softmax_lookup: the uniforms [n_query, num_neg, 2] */
+  float* u_out;                /* nullable out (rsa_softmax_sample: the uniforms drawn) */
+  int64_t* neg_ids;            /* [n_query, num_neg] out */
+  float* neg_logp;             /* [n_query, num_neg] out */
+  float* pos_logp;             /* [n_query, n_pos] out */
+  float* lse;                  /* [n_query] out */
+  float* mass;                 /* nullable [n_query, n_blocks] out */
+  float* cum;                  /* nullable [n_query, n_blocks] out */
+  void* workspace;
+  int64_t workspace_bytes;     /* >= rsa_softmax_sample_workspace_bytes(n_query, n_items) */
+} rsa_softmax_sample_args;
+int rsa_softmax_sample(const rsa_softmax_sample_args* args, rsa_stream_t stream);
+/* The same draw for caller-supplied uniforms (the tests hit the table edges with it). */
+int rsa_softmax_lookup(const rsa_softmax_sample_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

@@ -231,6 +231,18 @@ class LshArgs(_Sized):
     ]
 
 
+class SoftmaxSampleArgs(_Sized):
+    """struct rsa_softmax_sample_args."""
+    _fields_ = [
+        ('size', c_int64), ('item_table', c_void_p), ('n_items', c_int64), ('dim', c_int32), ('score_mode', c_int32),
+        ('inv_t', c_float), ('num_neg', c_int32), ('query', c_void_p), ('n_query', c_int64), ('pos_ids', c_void_p),
+        ('n_pos', c_int32), ('hist_len', c_int32), ('user_hist', c_void_p), ('item_aux', c_void_p), ('query_aux', c_void_p),
+        ('seed', c_uint64), ('offset', c_uint64), ('grid_threads', c_uint32), ('_pad', c_uint32), ('elem_base', c_uint64),
+        ('u_in', c_void_p), ('u_out', c_void_p), ('neg_ids', c_void_p), ('neg_logp', c_void_p), ('pos_logp', c_void_p),
+        ('lse', c_void_p), ('mass', c_void_p), ('cum', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -240,6 +252,7 @@ STRUCTS = {
     'rsa_rows_update_args': RowsUpdateArgs, 'rsa_bpr_sgd_args': BprSgdArgs, 'rsa_seg_gather_args': SegGatherArgs,
     'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
+    'rsa_softmax_sample_args': SoftmaxSampleArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -321,6 +334,10 @@ SIGNATURES = {
     'rsa_fullscore_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32]),
     'rsa_fullscore': (c_int, [POINTER(FullscoreArgs), c_void_p]),
     'rsa_row_sqnorm': (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    'rsa_softmax_sample_workspace_bytes': (c_int64, [c_int64, c_int64]),
+    'rsa_softmax_sample_block': (c_int32, []),
+    'rsa_softmax_sample': (c_int, [POINTER(SoftmaxSampleArgs), c_void_p]),
+    'rsa_softmax_lookup': (c_int, [POINTER(SoftmaxSampleArgs), c_void_p]),
 }
 
 _lib = None

@@ -1192,6 +1192,108 @@ def probs_t_query(probs, query, out=None):
     return _unpad(res, d, out)
 
 
+SOFTMAX_SAMPLE_MAX_DIM = 128
+
+
+def softmax_sample_block():
+    """Items per block of the two-level draw (the library's compile-time G): ``mass`` / ``cum`` hold ceil((N - 1) / G) columns."""
+    return int(nat.lib().rsa_softmax_sample_block())
+
+
+def _softmax_sample_args(item_table, query, num_neg, t, score_mode, pos_ids, user_hist, want_tables, items_without_pad, who):
+    item_table = _need(item_table, torch.float32, 'item_table')
+    query = _need(query, torch.float32, 'query')
+    if item_table.dim() != 2 or query.dim() != 2 or query.shape[1] != item_table.shape[1]:
+        raise ValueError(f'{who}: item_table must be [N, d] and query [M, d], got {tuple(item_table.shape)} and {tuple(query.shape)}')
+    d = item_table.shape[1]
+    if d > SOFTMAX_SAMPLE_MAX_DIM or d % 4:
+        raise NotImplementedError(f'{who}: embed_dim must be a multiple of 4 and at most {SOFTMAX_SAMPLE_MAX_DIM} '
+                                  f'(one MFMA pass over k), got {d}')
+    if not float(t) > 0.0:
+        raise ValueError(f'{who}: the temperature t must be positive, got {t}')
+    n = int(num_neg)
+    if n < 0:
+        raise ValueError(f'{who}: num_neg must not be negative')
+    score_mode = _score_mode(score_mode)
+    n_items = item_table.shape[0] + (1 if items_without_pad else 0)
+    if n_items < 2:
+        raise ValueError(f'{who}: the catalog is empty')
+    dev, M = query.device, query.shape[0]
+    ia = qa = None
+    if score_mode != nat.SCORE_IP:       # per-item / per-query operands from the UNPADDED rows
+        ia = row_sqnorm(item_table if items_without_pad else item_table[1:], score_mode, pad=64)
+        qa = row_sqnorm(query, score_mode)
+    item_table, query, dim = _pad_k(item_table, query)
+    # (rows without the padding row: the kernels never touch row 0, so the base pointer is moved one row back)
+    table_ptr = ctypes.c_void_p(item_table.data_ptr() - dim * 4) if items_without_pad else ptr(item_table)
+    out = dict(neg_ids=torch.empty(M, n, dtype=torch.int64, device=dev), neg_logp=torch.empty(M, n, dtype=torch.float32, device=dev),
+               pos_logp=None, lse=torch.empty(M, dtype=torch.float32, device=dev))
+    a = nat.SoftmaxSampleArgs()
+    a.item_table, a.n_items, a.dim, a.score_mode, a.inv_t = table_ptr, n_items, dim, score_mode, 1.0 / float(t)
+    a.query, a.n_query, a.num_neg = ptr(query), M, n
+    a.item_aux, a.query_aux, a.lse = ptr(ia), ptr(qa), ptr(out['lse'])
+    if n:
+        a.neg_ids, a.neg_logp = ptr(out['neg_ids']), ptr(out['neg_logp'])
+    if pos_ids is not None:
+        pos_ids = _need(pos_ids, torch.int64, 'pos_ids')
+        if pos_ids.dim() != 2 or pos_ids.shape[0] != M:
+            raise ValueError(f'{who}: pos_ids must be [M, T]')
+        out['pos_logp'] = torch.empty(pos_ids.shape, dtype=torch.float32, device=dev)
+        a.n_pos, a.pos_ids, a.pos_logp = pos_ids.shape[1], ptr(pos_ids), ptr(out['pos_logp'])
+    if user_hist is not None:
+        user_hist = _need(user_hist, torch.int64, 'user_hist')
+        if user_hist.dim() != 2 or user_hist.shape[0] != M:
+            raise ValueError(f'{who}: user_hist must be [M, L]')
+        if user_hist.shape[1]:
+            a.hist_len, a.user_hist = user_hist.shape[1], ptr(user_hist)
+    if want_tables:
+        G = softmax_sample_block()
+        nb = (n_items - 1 + G - 1) // G
+        out['mass'] = torch.empty(M, nb, dtype=torch.float32, device=dev)
+        out['cum'] = torch.empty(M, nb, dtype=torch.float32, device=dev)
+        a.mass, a.cum = ptr(out['mass']), ptr(out['cum'])
+    ws, a.workspace_bytes = _workspace(dev, 'rsa_softmax_sample_workspace_bytes', M, n_items)
+    a.workspace = ptr(ws)
+    return a, out, (item_table, query, ia, qa, pos_ids, user_hist, ws)
+
+
+@_on_device
+def softmax_sample(item_table, query, num_neg, *, t=1.0, score_mode=0, pos_ids=None, user_hist=None, generator=None, want_u=False,
+                   want_tables=False, items_without_pad=False):
+    """rsa_softmax_sample: ``num_neg`` ids per query, with replacement, from softmax(score(query, .) / t) over rows 1.. of
+    ``item_table`` [N, d] -- the draw of ``sampling(method='brute')`` without the [M, N] matrix (two-level inverse CDF over item
+    blocks, include/recstudio_amd.h).  ``user_hist`` [M, L] (0-padded): those ids are never drawn.  ``pos_ids`` [M, T]: also their
+    log-probabilities (-inf for the padding id).  The uniforms are those of ``torch.rand(M, num_neg, 2)`` on the device generator
+    (advanced as that call would); the ids are NOT torch.multinomial's for the same seed.  ``items_without_pad``: ``item_table`` is
+    weight[1:].  -> dict(neg_ids [M, n] int64, neg_logp [M, n] = score / t - lse (the masked row is not renormalised), pos_logp
+    [M, T] or None, lse [M], u [M, n, 2] with ``want_u``, mass / cum [M, ceil((N - 1) / G)] with ``want_tables``)."""
+    a, out, keep = _softmax_sample_args(item_table, query, num_neg, t, score_mode, pos_ids, user_hist, want_tables,
+                                        items_without_pad, 'softmax_sample')
+    numel = a.n_query * a.num_neg * 2
+    if numel:
+        pc = rng.reserve(numel, 4, query.device, generator)
+        a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
+    if want_u:
+        out['u'] = torch.empty(a.n_query, a.num_neg, 2, dtype=torch.float32, device=query.device)
+        a.u_out = ptr(out['u'])
+    _launch('rsa_softmax_sample', ctypes.byref(a))
+    return out
+
+
+@_on_device
+def softmax_lookup(item_table, query, u, *, t=1.0, score_mode=0, pos_ids=None, user_hist=None, want_tables=False,
+                   items_without_pad=False):
+    """rsa_softmax_lookup: the draw of ``softmax_sample`` for caller-supplied uniforms ``u`` [M, n, 2]."""
+    u = _need(u, torch.float32, 'u')
+    if u.dim() != 3 or u.shape[0] != query.shape[0] or u.shape[2] != 2:
+        raise ValueError('softmax_lookup: u must be [M, n, 2]')
+    a, out, keep = _softmax_sample_args(item_table, query, u.shape[1], t, score_mode, pos_ids, user_hist, want_tables,
+                                        items_without_pad, 'softmax_lookup')
+    a.u_in = ptr(u)
+    _launch('rsa_softmax_lookup', ctypes.byref(a))
+    return out
+
+
 @_on_device
 def topk_mask_history(cand_val, cand_idx, user_hist, k):
     """baseretriever.py:386-392 on sorted candidates: drop history items, keep the k best."""

@@ -49,7 +49,7 @@ def default_config():
                   'tensorboard_path': None, 'sparse_grad': False, 'device_loader': True, 'fused_optimizer': None,
                   'shard_slices': 1, 'shard_layout': 'block', 'shard_owner_loss': True, 'shard_init': 'auto',
                   'shard_lookahead': False, 'shard_deterministic': True, 'shard_rows_share': None,
-                  'fused_prefetch': True},
+                  'fused_prefetch': True, 'brute_stream': False},
         'eval': {'batch_size': 128, 'cutoff': [5, 10, 20], 'val_metrics': ['ndcg', 'recall'], 'val_n_epoch': 1,
                  'test_metrics': ['ndcg', 'recall', 'precision', 'map', 'mrr', 'hit'], 'topk': 100,
                  'save_path': './saved/'},
@@ -488,6 +488,22 @@ class BaseRetriever(torch.nn.Module):
         else:                                                        # 'brute': softmax over the whole catalog
             query = self.query_encoder(self._get_query_feat(batch)) if query is None else query
             pos2 = fiid_val.view(-1, 1) if fiid_val.dim() == 1 else fiid_val
+            if self.config['train'].get('brute_stream', False):
+                # the same distribution and log-probabilities without the [B, N] matrices (ops.softmax_sample); the ids
+                # are not torch.multinomial's for the same seed
+                if not isinstance(self.item_encoder, torch.nn.Embedding):
+                    raise NotImplementedError("train.brute_stream needs an nn.Embedding item tower (the kernel reads the table's rows)")
+                if type(self.score_func) not in (InnerProductScorer, CosineScorer, EuclideanScorer):
+                    raise NotImplementedError('train.brute_stream needs a stock InnerProduct / Cosine / Euclidean scorer, got '
+                                              f'{type(self.score_func).__name__}')
+                if query.dim() != 2:
+                    raise NotImplementedError(f'train.brute_stream needs a 2-D query [B, d], got {tuple(query.shape)}')
+                out = ops.softmax_sample(self.item_vector.detach(), query.detach(), num_neg[1] * pos2.size(-1), t=t,
+                                         score_mode=self.score_func.cosine, pos_ids=pos2,
+                                         user_hist=user_hist if excluding_hist else None, items_without_pad=True)
+                log_pos_prob, neg_id, log_neg_prob = out['pos_logp'], out['neg_ids'], out['neg_logp']
+                result = (log_pos_prob.view_as(fiid_val).detach(), neg_id, log_neg_prob.detach())
+                return (result, query) if return_query else (result, None)
             with torch.no_grad():
                 all_score = self.score_func(query, self.item_vector) / t
                 all_prob = torch.nn.functional.pad(torch.softmax(all_score, dim=-1), pad=(1, 0))
