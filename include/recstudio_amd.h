@@ -539,7 +539,13 @@ int64_t rsa_scatter_rows_sorted_workspace_bytes(int64_t n_queries, int32_t num_n
  * torch.optim.SparseAdam on the coalesced gradient g[id] = upstream * sum_e d_e * query[qrow_e]):
  *     m += (g - m)(1 - beta1);  v += (g^2 - v)(1 - beta2);  weight -= lr * sqrt(1 - beta2^step) / (1 - beta1^step) * m / (sqrt(v) + eps)
  * exp_avg / exp_avg_sq: [n_items, dim] optimizer state, updated in place; rows not in the step are untouched (lazy).
- * The row sums never leave registers: no gradient tensor, no coalesce pass.  step >= 1 is the 1-based step count. */
+ * The row sums never leave registers: no gradient tensor, no coalesce pass.  step >= 1 is the 1-based step count.
+ * With rule = RSA_ROWS_ADAGRAD and state_sum given it is torch.optim.Adagrad's update of every touched row (lr, eps, step as
+ * above; lr_decay; exp_avg / exp_avg_sq must be null):
+ *     state_sum += g^2;  weight -= lr / (1 + (step - 1) * lr_decay) * g / (sqrt(state_sum) + eps)
+ * A row outside the step has g = 0, which changes neither its state_sum nor its weight under the dense rule: leaving it alone
+ * is exact, not lazy.  These fields were appended without a new RSA_ABI_VERSION: a shorter block reads them as 0 = rule 0. */
+#define RSA_ROWS_ADAGRAD 1
 typedef struct rsa_rows_update_args {
   int64_t size;                /* sizeof(rsa_rows_update_args) */
   const float* query;          /* [n_query_rows, dim] */
@@ -565,6 +571,10 @@ typedef struct rsa_rows_update_args {
   uint8_t* solo;               /* rsa_sort_step_elements: nullable [n_queries * (num_neg + has_pos)] out */
   void* workspace;
   int64_t workspace_bytes;     /* >= rsa_scatter_rows_sorted_workspace_bytes(n_queries, num_neg, n_items) */
+  float* state_sum;            /* RSA_ROWS_ADAGRAD: [n_items, dim] sum of squared gradients (then target = the weights), updated in place */
+  double lr_decay;             /* RSA_ROWS_ADAGRAD: clr = lr / (1 + (step - 1) * lr_decay), in double, rounded to fp32 once */
+  int32_t rule;                /* 0: accumulate, or lazy Adam when exp_avg is given (what a block without this field asks for); RSA_ROWS_ADAGRAD */
+  int32_t _pad2;
 } rsa_rows_update_args;
 
 /* sort + apply in one call (the former rsa_scatter_rows_sorted / rsa_adam_rows_sorted) */

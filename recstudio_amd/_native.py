@@ -18,6 +18,7 @@ CSRC = os.path.join(HERE, 'csrc')
 RSA_OK = 0
 SCORE_IP, SCORE_COS, SCORE_EUC = 0, 1, 2
 SAMPLER_GIVEN, SAMPLER_UNIFORM, SAMPLER_POPULAR = 0, 1, 2
+ROWS_ADAGRAD = 1          # RSA_ROWS_ADAGRAD (rsa_rows_update_args.rule)
 LOSS_BPR, LOSS_SSM, LOSS_BCE = 0, 1, 2
 LOSS_WBPR, LOSS_WBCE, LOSS_HINGE, LOSS_NCE, LOSS_CCL = 3, 4, 5, 6, 7
 
@@ -143,7 +144,7 @@ class RowsUpdateArgs(_Sized):
         ('_pad', c_int32), ('dpos', c_void_p), ('dneg', c_void_p), ('upstream', c_void_p), ('n_items', c_int64),
         ('pad_row', c_int64), ('target', c_void_p), ('exp_avg', c_void_p), ('exp_avg_sq', c_void_p), ('lr', c_double),
         ('beta1', c_double), ('beta2', c_double), ('eps', c_double), ('step', c_int64), ('solo', c_void_p), ('workspace', c_void_p),
-        ('workspace_bytes', c_int64),
+        ('workspace_bytes', c_int64), ('state_sum', c_void_p), ('lr_decay', c_double), ('rule', c_int32), ('_pad2', c_int32),
     ]
 
 

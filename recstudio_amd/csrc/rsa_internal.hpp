@@ -10,6 +10,11 @@ struct AdamArgs {            // exp_avg == nullptr: plain accumulate (target[id]
   float one_minus_beta1, one_minus_beta2, eps, step_size;
 };
 
+struct AdagradArgs {         // the Adagrad form of the sorted apply pass (rsa_rows_update_args.rule == RSA_ROWS_ADAGRAD)
+  float* state_sum;          // [n_items, dim]: ONE state table
+  float clr, eps;            // clr = lr / (1 + (step - 1) lr_decay), taken in double and rounded to fp32 once
+};
+
 struct SortedLayout {        // a sorted scatter's workspace (sorted_workspace_bytes)
   uint64_t *pairs_a, *pairs_b;     // packed (key << 32 | element) pairs: the radix sort's ping-pong buffers
   void* temp;                      // its digit counters

@@ -11,7 +11,10 @@
 // backward sums ~1000 item rows per query) is not walked by one wave: each chunk leaves the partial sum of its
 // leading / trailing open segment in the workspace and a second kernel adds a run's partials in chunk order.
 // `target` may be a zeroed dense gradient (== the reference's weight.grad) or the weight table itself with
-// scale = -lr (plain SGD applied in place).
+// scale = -lr (plain SGD applied in place).  With optimizer state the same passes apply a rule to every touched row instead of
+// adding: lazy Adam (exp_avg / exp_avg_sq: torch.optim.SparseAdam, two state rows per row) in the kernels above the line
+// "the Adagrad form", torch.optim.Adagrad (state_sum: one state row per row, `learner: adagrad` of the reference,
+// recommender.py:466-467) in kernels of their own below it.
 #include "rsa_common.hpp"
 #include "rsa_radix.hpp"
 #include "rsa_internal.hpp"
@@ -289,6 +292,191 @@ __global__ __launch_bounds__(256) void sorted_finish_kernel(int64_t n_chunks, co
   apply_run<NDW>(target, adam, cur, scale, lane, acc, trow, mrow_v, vrow_v);
 }
 
+// ---- the Adagrad form (rsa_rows_update_args.rule == RSA_ROWS_ADAGRAD): torch.optim.Adagrad on the touched rows
+//     g = upstream * run sum;   s' = s + g g;   w' = w - clr (g / (sqrt(s') + eps))
+// with ONE state table.  A row without a kept element has g = 0, for which torch's dense pass changes neither s nor w
+// (0 / (sqrt(s) + eps) = 0): leaving such rows alone IS the dense rule, and the sparse branch of torch.optim.Adagrad squares
+// the coalesced row gradient -- the run sum these passes hold in registers.
+// Every rounding is spelled out so that tests/adagrad_referee.py can follow it operation for operation:
+//     g   = fl(scale * acc)
+//     s'  = fl(g * g + s)                 FUSED: one rounding
+//     den = fl(fl(sqrt(s')) + eps)        sqrtf and the division are the correctly rounded ones (hipcc's default)
+//     q   = fl(g / den)
+//     w'  = fl(-clr * q + w)              FUSED: one rounding
+// The kernels below are copies of the frame of sorted_apply_kernel / sorted_finish_kernel under names of their own: a further
+// template parameter on those two would rename every instantiation and a body shared through a function would put the existing
+// kernels' code at the mercy of the inliner, while tools/kernel_fingerprint.py holds every kernel that exists today to its bytes.
+// What differs: one state row (not two) is requested ahead and carried across a run, and DEC is DecStep (exchange segments are
+// only ever accumulated, never stepped).
+template <int NDW, bool NT>
+__device__ __forceinline__ void apply_run_adagrad(float* __restrict__ target, const AdagradArgs& ada, int32_t cur, float scale, int lane,
+                                                  const float (&acc)[NDW], const float (&trow)[NDW], const float (&srow_v)[NDW]) {
+  constexpr int D = 64 * NDW;
+  float* row = target + (size_t)cur * D;
+  float* srow = ada.state_sum + (size_t)cur * D;
+#pragma unroll
+  for (int k = 0; k < NDW; ++k) {
+    const int c = k * 64 + lane;
+    const float g = __fmul_rn(scale, acc[k]);
+    const float s1 = __fmaf_rn(g, g, srow_v[k]);
+    const float den = __fadd_rn(sqrtf(s1), ada.eps);
+    const float q = g / den;
+    st_row<NT>(srow + c, s1);
+    st_row<NT>(row + c, __fmaf_rn(-ada.clr, q, trow[k]));
+  }
+}
+
+template <int NDW, bool NT>
+__global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_adagrad_kernel(
+    const uint64_t* __restrict__ pairs, int64_t total, const float* __restrict__ query, const DecStep dec,
+    const float* __restrict__ upstream, int32_t pad_row, int32_t drop_key, float* __restrict__ target, AdagradArgs ada,
+    float* __restrict__ lead_part, float* __restrict__ trail_part, int32_t* __restrict__ meta, int32_t chunk_elems) {
+  constexpr int D = 64 * NDW;
+  const int lane = lane_id();
+  const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t begin = chunk * chunk_elems;
+  if (begin >= total) return;
+  const float scale = upstream ? upstream[0] : 1.f;
+  const int64_t i = begin + lane;
+  const bool in = lane < chunk_elems && i < total;
+  const uint64_t pr = in ? pairs[i] : 0ull;
+  const int32_t key = in ? (int32_t)rdx_key(pr) : -1;
+  int32_t qrow = 0;
+  float coef = 0.f;
+  bool solo = false;                  // (no forward applies Adagrad rows itself; a flagged element is skipped as in the SGD form)
+  if (in && key != drop_key) {
+    int32_t e = (int32_t)rdx_val(pr);
+    solo = e < 0;
+    e &= 0x7fffffff;
+    if (!solo) dec((int64_t)e, qrow, coef);
+  }
+  const int cnt = (int)(total - begin < chunk_elems ? total - begin : chunk_elems);
+  const int32_t prev = begin > 0 ? (int32_t)rdx_key(pairs[begin - 1]) : -1;
+  const int32_t next = begin + cnt < total ? (int32_t)rdx_key(pairs[begin + cnt]) : -1;
+  float acc[NDW];
+  float trow[NDW], srow_v[NDW];       // the current run's target and state_sum row, requested at its head
+#pragma unroll
+  for (int k = 0; k < NDW; ++k) acc[k] = trow[k] = srow_v[k] = 0.f;
+  int32_t cur = -1;
+  bool leading = false;
+  int32_t lead_key = -1;
+  auto close_segment = [&]() {
+    if (leading) {
+#pragma unroll
+      for (int k = 0; k < NDW; ++k) lead_part[(size_t)chunk * D + k * 64 + lane] = acc[k];
+      leading = false;
+    } else if (cur >= 0) {
+      apply_run_adagrad<NDW, NT>(target, ada, cur, scale, lane, acc, trow, srow_v);
+    }
+#pragma unroll
+    for (int k = 0; k < NDW; ++k) acc[k] = 0.f;
+  };
+  // only the elements with work are visited (see sorted_apply_kernel): rows without a kept element are neither read nor written
+  uint64_t work = __ballot(in && !solo && key != drop_key && key != pad_row);
+  int last_t = -1;
+  constexpr int U = RSA_SORTED_UNROLL;
+  while (work) {
+    int ts[U];
+    int nu = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      ts[u] = 63;
+      if (work) {
+        ts[u] = __ffsll((unsigned long long)work) - 1;
+        work &= work - 1;
+        nu = u + 1;
+      }
+    }
+    // query row, target row and state_sum row of U elements requested together; slots past the last element with work
+    // request row 0, always readable
+    float qv[U][NDW], tv[U][NDW], sv[U][NDW];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int32_t qr = u < nu ? __builtin_amdgcn_readlane(qrow, ts[u]) : 0;
+      const int32_t kr = u < nu ? __builtin_amdgcn_readlane(key, ts[u]) : 0;
+      const float* qp = query + (size_t)qr * D;
+      const float* tp = target + (size_t)kr * D;
+      const float* sp = ada.state_sum + (size_t)kr * D;
+#pragma unroll
+      for (int k = 0; k < NDW; ++k) {
+        qv[u][k] = qp[k * 64 + lane];
+        tv[u][k] = ld_row<NT>(tp + k * 64 + lane);
+        sv[u][k] = ld_row<NT>(sp + k * 64 + lane);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (u >= nu) break;
+      const int t = ts[u];
+      const int32_t kt = __builtin_amdgcn_readlane(key, t);
+      const int32_t before = t == 0 ? prev : __builtin_amdgcn_readlane(key, t - 1);
+      const bool head = kt != before;
+      if (head) {
+        close_segment();
+        cur = kt;
+#pragma unroll
+        for (int k = 0; k < NDW; ++k) {
+          trow[k] = tv[u][k];
+          srow_v[k] = sv[u][k];
+        }
+      } else if (t == 0) {            // the chunk opens inside a run that began in an earlier chunk
+        leading = true;
+        cur = lead_key = kt;
+      }
+      const float cf = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(coef), t));
+#pragma unroll
+      for (int k = 0; k < NDW; ++k) acc[k] = __fmaf_rn(cf, qv[u][k], acc[k]);
+      last_t = t;
+    }
+  }
+  const bool whole = leading;
+  int32_t trail_key = -1;
+  if (leading) {
+    close_segment();                                  // -> lead_part
+  } else if (cur >= 0 && last_t == cnt - 1 && next == cur) {
+    trail_key = cur;                                  // the run goes on: sorted_finish_adagrad_kernel owns its row
+#pragma unroll
+    for (int k = 0; k < NDW; ++k) trail_part[(size_t)chunk * D + k * 64 + lane] = acc[k];
+  } else {
+    close_segment();
+  }
+  if (lane == 0) {
+    meta[chunk * META_STRIDE + META_LEAD_KEY] = lead_key;
+    meta[chunk * META_STRIDE + META_LEAD_FULL] = whole ? 1 : 0;
+    meta[chunk * META_STRIDE + META_TRAIL_KEY] = trail_key;
+  }
+}
+
+// the partials of a run that crosses chunk borders, added in chunk order; plain accesses (a few rows per pass)
+template <int NDW>
+__global__ __launch_bounds__(256) void sorted_finish_adagrad_kernel(int64_t n_chunks, const float* __restrict__ upstream,
+                                                                    int32_t pad_row, float* __restrict__ target, AdagradArgs ada,
+                                                                    const float* __restrict__ lead_part,
+                                                                    const float* __restrict__ trail_part,
+                                                                    const int32_t* __restrict__ meta) {
+  constexpr int D = 64 * NDW;
+  const int lane = lane_id();
+  const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (chunk >= n_chunks) return;
+  const int32_t cur = meta[chunk * META_STRIDE + META_TRAIL_KEY];
+  if (cur < 0 || cur == pad_row) return;
+  const float scale = upstream ? upstream[0] : 1.f;
+  float acc[NDW], trow[NDW], srow_v[NDW];
+#pragma unroll
+  for (int k = 0; k < NDW; ++k) {
+    acc[k] = trail_part[(size_t)chunk * D + k * 64 + lane];
+    trow[k] = target[(size_t)cur * D + k * 64 + lane];
+    srow_v[k] = ada.state_sum[(size_t)cur * D + k * 64 + lane];
+  }
+  for (int64_t c2 = chunk + 1; c2 < n_chunks; ++c2) {
+    if (meta[c2 * META_STRIDE + META_LEAD_KEY] != cur) break;
+#pragma unroll
+    for (int k = 0; k < NDW; ++k) acc[k] = __fadd_rn(acc[k], lead_part[(size_t)c2 * D + k * 64 + lane]);
+    if (!meta[c2 * META_STRIDE + META_LEAD_FULL]) break;
+  }
+  apply_run_adagrad<NDW, false>(target, ada, cur, scale, lane, acc, trow, srow_v);
+}
+
 // After the sort: an element whose key differs from both neighbours is the ONLY element of the step on its row ("solo").
 // solo[e] (element order) <- 1 for such elements unless the row is the padding row / a dropped id, and bit 31 of the
 // element number in `vals` is set so that the apply kernel leaves the row alone: a forward that updates solo rows
@@ -391,6 +579,32 @@ static int apply_sorted_pairs(const uint64_t* pairs, int64_t total, const float*
     return RSA_ERR_UNSUPPORTED;
   }
   RSA_CHECK_LAUNCH("rsa_rows_update_sorted(apply)");
+  return RSA_OK;
+}
+
+// the Adagrad form of the two passes (a step's elements only: DecStep)
+static int apply_sorted_pairs_adagrad(const uint64_t* pairs, int64_t total, const float* query, int32_t dim, const DecStep& dec,
+                                      const float* upstream, int64_t drop_key, int64_t pad_row, float* target, AdagradArgs ada,
+                                      const SortedLayout& L, hipStream_t s) {
+  const int ce = sorted_chunk_elems(total);
+  const unsigned chunks = (unsigned)((total + ce - 1) / ce);
+  dim3 grid((chunks + 3) / 4), block(256);
+  const int32_t pad = (int32_t)(pad_row < 0 || pad_row >= (1ll << 31) ? -2 : pad_row);
+  const bool nt = RSA_SORTED_NT == 1 || (RSA_SORTED_NT == 2 && streams_past_cache(drop_key, dim));      // target AND state_sum
+  const bool built = dispatch_dim<64, 128, 256>(dim, [&](auto D) {
+    constexpr int NDW = D() / 64;
+    dispatch_bool(nt, [&](auto NT) {
+      hipLaunchKernelGGL((sorted_apply_adagrad_kernel<NDW, NT()>), grid, block, 0, s, pairs, total, query, dec, upstream, pad,
+                         (int32_t)drop_key, target, ada, L.lead_part, L.trail_part, L.meta, (int32_t)ce);
+    });
+    hipLaunchKernelGGL(sorted_finish_adagrad_kernel<NDW>, grid, block, 0, s, (int64_t)chunks, upstream, pad, target, ada,
+                       L.lead_part, L.trail_part, L.meta);
+  });
+  if (!built) {
+    rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", dim);
+    return RSA_ERR_UNSUPPORTED;
+  }
+  RSA_CHECK_LAUNCH("rsa_rows_update_sorted(adagrad apply)");
   return RSA_OK;
 }
 
@@ -521,6 +735,24 @@ static int check_adam(const rsa_rows_update_args& a, const char* who) {
   return RSA_OK;
 }
 
+// Adagrad's constants as adam_of takes Adam's: clr = lr / (1 + (step - 1) lr_decay) (torch.optim.Adagrad, step 1-based) in
+// double from the caller's doubles, each rounded to fp32 once.
+static AdagradArgs adagrad_of(const rsa_rows_update_args& a) {
+  return AdagradArgs{a.state_sum, (float)(a.lr / (1.0 + (double)(a.step - 1) * a.lr_decay)), (float)a.eps};
+}
+
+// Which rule the block asks for, and that rule's fields; before any HIP call.  rule 0 is the block as it was before `rule`
+// existed (an older, shorter block reads 0): plain accumulate or lazy Adam, decided by exp_avg (check_adam).
+static int check_rule(const rsa_rows_update_args& a, const char* who) {
+  if (a.rule == 0) return check_adam(a, who);
+  RSA_CHECK_ARG(a.rule == RSA_ROWS_ADAGRAD, "%s: unknown rule %d (0: accumulate / lazy Adam by exp_avg, %d: RSA_ROWS_ADAGRAD)", who,
+                (int)a.rule, (int)RSA_ROWS_ADAGRAD);
+  RSA_CHECK_ARG(a.state_sum != nullptr, "%s: Adagrad needs state_sum", who);
+  RSA_CHECK_ARG(a.exp_avg == nullptr && a.exp_avg_sq == nullptr, "%s: Adagrad takes no exp_avg / exp_avg_sq (state_sum is its only state)", who);
+  RSA_CHECK_ARG(a.step >= 1 && a.eps >= 0.0 && a.lr_decay >= 0.0, "%s: bad Adagrad hyper-parameters (step >= 1, eps >= 0, lr_decay >= 0)", who);
+  return RSA_OK;
+}
+
 // the apply + finish passes over the sorted pairs in the workspace
 static int apply_step_elements(const rsa_rows_update_args& a, int has_pos, hipStream_t s) {
   RSA_CHECK_ARG(a.n_queries >= 0 && a.num_neg >= 1 && a.n_items >= 1 && a.n_items < (1ll << 31), "rsa_rows_update_sorted: bad sizes");
@@ -534,6 +766,9 @@ static int apply_step_elements(const rsa_rows_update_args& a, int has_pos, hipSt
                 (long long)a.workspace_bytes, (long long)need);
   const SortedLayout L = sorted_layout(a.workspace, a.n_queries * (int64_t)(a.num_neg + 1));
   const DecStep dec{a.query_index, a.dpos, a.dneg, (int)a.num_neg, has_pos};
+  if (a.rule == RSA_ROWS_ADAGRAD)
+    return apply_sorted_pairs_adagrad(step_sorted(L, a.n_items), total, a.query, a.dim, dec, a.upstream, a.n_items, a.pad_row, a.target,
+                                      adagrad_of(a), L, s);
   return apply_sorted_pairs(step_sorted(L, a.n_items), total, a.query, a.dim, dec, a.upstream, a.n_items, a.pad_row, a.target,
                             adam_of(a), L, s);
 }
@@ -547,14 +782,14 @@ extern "C" int rsa_sort_step_elements(const rsa_rows_update_args* args, rsa_stre
 extern "C" int rsa_rows_update_presorted(const rsa_rows_update_args* args, rsa_stream_t stream) {
   rsa_rows_update_args a;
   if (int rc = load_args(a, args, "rsa_rows_update_presorted")) return rc;
-  if (int rc = check_adam(a, "rsa_rows_update_presorted")) return rc;
+  if (int rc = check_rule(a, "rsa_rows_update_presorted")) return rc;
   return apply_step_elements(a, a.has_pos != 0, (hipStream_t)stream);
 }
 
 extern "C" int rsa_rows_update_sorted(const rsa_rows_update_args* args, rsa_stream_t stream) {
   rsa_rows_update_args a;
   if (int rc = load_args(a, args, "rsa_rows_update_sorted")) return rc;
-  if (int rc = check_adam(a, "rsa_rows_update_sorted")) return rc;
+  if (int rc = check_rule(a, "rsa_rows_update_sorted")) return rc;
   RSA_CHECK_ARG(a.pos_ids == nullptr || a.dpos != nullptr, "rsa_rows_update_sorted: pos_ids without dpos");
   if (a.dim != 64 && a.dim != 128 && a.dim != 256) {      // before the sort is issued
     rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", a.dim);

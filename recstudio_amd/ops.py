@@ -896,6 +896,12 @@ def _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, who):
     a.lr, a.beta1, a.beta2, a.eps, a.step = float(lr), float(betas[0]), float(betas[1]), float(eps), int(step)
 
 
+def _adagrad_fields(a, state_sum, lr, lr_decay, eps, step, who):
+    a.rule, a.state_sum = nat.ROWS_ADAGRAD, ptr(_need(state_sum, torch.float32, who + ': state_sum'))
+    # (doubles: the library takes clr = lr / (1 + (step - 1) lr_decay) from these and rounds it to fp32 once)
+    a.lr, a.lr_decay, a.eps, a.step = float(lr), float(lr_decay), float(eps), int(step)
+
+
 @_on_device
 def sort_step_elements(pos_ids, neg_ids, n_items, pad_row=0, want_solo=True):
     """rsa_sort_step_elements: the step's (item id, element) pairs sorted by id in a workspace, and the classification
@@ -919,13 +925,13 @@ def sort_step_elements(pos_ids, neg_ids, n_items, pad_row=0, want_solo=True):
 
 
 def _rows_update(who, target, query, dneg, *, neg_ids=None, workspace=None, n_queries=None, num_neg=None, adam=None,
-                 query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
+                 adagrad=None, query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
     """The one body of the rows-update wrappers.  No ``workspace``: sort + apply over ``neg_ids`` / ``pos_ids``
     (rsa_rows_update_sorted; queries and negatives per query derived here, the workspace allocated here).  ``workspace`` given:
     the apply pass over the pairs ``sort_step_elements`` left in it (rsa_rows_update_presorted).  ``adam``: (exp_avg, exp_avg_sq,
-    lr, betas, eps, step) of the lazy-Adam form."""
+    lr, betas, eps, step) of the lazy-Adam form; ``adagrad``: (state_sum, lr, lr_decay, eps, step) of the Adagrad form."""
     presorted = workspace is not None
-    target = _need(target, torch.float32, 'weight' if adam else 'target')
+    target = _need(target, torch.float32, 'weight' if adam or adagrad else 'target')
     query = _need(query, torch.float32, 'query')
     neg_ids = None if presorted else _need(neg_ids, torch.int64, 'neg_ids')
     dneg = _need(dneg, torch.float32, 'dneg')
@@ -943,6 +949,8 @@ def _rows_update(who, target, query, dneg, *, neg_ids=None, workspace=None, n_qu
     a = _rows_update_args(target, query, query_index, M, n, dpos, dneg, upstream, pad_row)
     if adam:
         _adam_fields(a, *adam, who)
+    if adagrad:
+        _adagrad_fields(a, *adagrad, who)
     if presorted:
         a.has_pos, a.workspace_bytes = int(dpos is not None), workspace.numel()
     else:
@@ -987,6 +995,26 @@ def adam_rows_presorted(weight, exp_avg, exp_avg_sq, query, workspace, n_queries
     left in ``workspace``."""
     return _rows_update('adam_rows_presorted', weight, query, dneg, workspace=workspace, n_queries=n_queries, num_neg=num_neg,
                         adam=(exp_avg, exp_avg_sq, lr, betas, eps, step), query_index=query_index, dpos=dpos, upstream=upstream,
+                        pad_row=pad_row)
+
+
+@_on_device
+def adagrad_rows_sorted(weight, state_sum, query, neg_ids, dneg, *, lr, lr_decay=0.0, eps=1e-10, step=1, query_index=None,
+                        pos_ids=None, dpos=None, upstream=None, pad_row=0):
+    """rsa_rows_update_sorted with rule = RSA_ROWS_ADAGRAD: torch.optim.Adagrad's update (state_sum += g^2; weight -= lr / (1 +
+    (step - 1) lr_decay) * g / (sqrt(state_sum) + eps)) on the rows touched by the step, from the factored gradient -- no gradient
+    tensor.  A row outside the step has a zero gradient, which the dense rule leaves as it is: this IS torch.optim.Adagrad."""
+    return _rows_update('adagrad_rows_sorted', weight, query, dneg, neg_ids=neg_ids, adagrad=(state_sum, lr, lr_decay, eps, step),
+                        query_index=query_index, pos_ids=pos_ids, dpos=dpos, upstream=upstream, pad_row=pad_row)
+
+
+@_on_device
+def adagrad_rows_presorted(weight, state_sum, query, workspace, n_queries, num_neg, dneg, *, lr, lr_decay=0.0, eps=1e-10, step=1,
+                           query_index=None, dpos=None, upstream=None, pad_row=0):
+    """rsa_rows_update_presorted with rule = RSA_ROWS_ADAGRAD: the apply pass of adagrad_rows_sorted over the pairs
+    ``sort_step_elements(want_solo=False)`` left in ``workspace``."""
+    return _rows_update('adagrad_rows_presorted', weight, query, dneg, workspace=workspace, n_queries=n_queries, num_neg=num_neg,
+                        adagrad=(state_sum, lr, lr_decay, eps, step), query_index=query_index, dpos=dpos, upstream=upstream,
                         pad_row=pad_row)
 
 

@@ -25,7 +25,7 @@ from . import _native as nat
 from . import eval as rs_eval
 from . import ops
 from .dataset import SeqDataset, TripletDataset
-from .fused import BPRAdamStep, BPRSGDStep, fused_bpr_loss, fused_ssm_loss, retriever_scores
+from .fused import BPRAdagradStep, BPRAdamStep, BPRSGDStep, fused_bpr_loss, fused_ssm_loss, retriever_scores
 from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, PairwiseLoss, PointwiseLoss, SampledSoftmaxLoss,
                         SoftmaxLoss)
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
@@ -1009,29 +1009,39 @@ class BaseRetriever(torch.nn.Module):
                                 on_lr=fused_step.set_lr if fused_step is not None else None, log=self.logger.info)
 
     def _fused_optimizer_step(self, tr):
-        """``train.fused_optimizer: 'sgd' | 'adam'`` (default None = the reference's torch optimizer on autograd
+        """``train.fused_optimizer: 'sgd' | 'adam' | 'learner'`` (default None = the reference's torch optimizer on autograd
         gradients): for the stock BPR two-tower configuration (nn.Embedding towers, InnerProductScorer, BPRLoss,
         Uniform / Popular sampler, negative_count % 64 == 0, embed_dim in {64, 128, 256}) run the whole step --
         sampling, scoring, loss, and the SGD / lazy-Adam update of the touched rows -- in the kernels, with no gradient
         tensors (fused.bpr_sgd_step / fused.FusedBPRAdam).  'adam' follows torch.optim.SparseAdam (rows outside the
-        batch keep their state), which differs from the dense Adam the reference runs by default."""
+        batch keep their state), which differs from the dense Adam the reference runs by default.  'learner' runs the rule
+        ``train.learner`` names: 'sgd' as above, 'adagrad' = torch.optim.Adagrad with its defaults (fused.FusedBPRAdagrad; exact,
+        not lazy: a zero gradient changes neither a row's state_sum nor its weight); any other learner is refused."""
         kind = tr.get('fused_optimizer')
         if not kind:
             return None
+        conf = lambda k: tr[k] if k in tr else self.config['train'][k]      # noqa: E731  (a partial ``tr``: the model's own settings)
         if not (self._fused_train_path() == 'bpr' and isinstance(self.neg_count, int)
                 and isinstance(self.query_encoder, torch.nn.Embedding) and self.item_encoder.weight.shape[1] in (64, 128, 256)
                 and not tr.get('weight_decay') and tr.get('grad_clip_norm') is None):
             raise NotImplementedError("train.fused_optimizer needs the stock BPR two-tower configuration "
                                       "(see BaseRetriever._fused_optimizer_step)")
-        if kind not in ('sgd', 'adam'):
-            raise ValueError(f"train.fused_optimizer must be 'sgd' or 'adam', got {kind!r}")
+        if kind not in ('sgd', 'adam', 'learner'):
+            raise ValueError(f"train.fused_optimizer must be 'sgd' or 'adam', or 'learner' (the rule train.learner names), got {kind!r}")
+        if kind == 'learner':
+            # the reference's own learner inside the kernels: the two whose row-sparse step IS the dense rule (a zero gradient moves
+            # neither the weight nor Adagrad's state_sum).  Dense Adam moves every row in every step: 'adam' above is SparseAdam.
+            kind = str(conf('learner')).lower()
+            if kind not in ('sgd', 'adagrad'):
+                raise NotImplementedError(f"train.fused_optimizer: 'learner' covers train.learner 'sgd' and 'adagrad', got {kind!r}")
         # look-ahead: 'sgd' only on the in-forward step (one 64-negative tile); it does not pay for lazy Adam -- in-process A/B
         # at the headline shape: 2.61 ms plain, 2.68 ms one batch ahead: the draw leaves the forward for the stand-alone sampler
         # and the apply pass is the step -- so there it is opt-in: train.fused_prefetch: 'adam'
         prefetch = tr.get('fused_prefetch', True)
-        ahead = bool(self.neg_count == 64 and prefetch and self.fiid is not None) if kind == 'sgd' else prefetch == 'adam'
-        cls = BPRSGDStep if kind == 'sgd' else BPRAdamStep
-        return cls(self.item_encoder.weight, self.query_encoder.weight, self.neg_count, tr['learning_rate'], self.sampler,
+        # (Adagrad's step has Adam's shape -- stand-alone sampler, two sorts, two apply passes: opt-in too, train.fused_prefetch: 'adagrad')
+        ahead = bool(self.neg_count == 64 and prefetch and self.fiid is not None) if kind == 'sgd' else prefetch == kind
+        cls = {'sgd': BPRSGDStep, 'adam': BPRAdamStep, 'adagrad': BPRAdagradStep}[kind]
+        return cls(self.item_encoder.weight, self.query_encoder.weight, self.neg_count, conf('learning_rate'), self.sampler,
                    self.fuid, self.fiid, ahead)
 
     @torch.no_grad()
