@@ -788,6 +788,57 @@ int rsa_softmax_sample(const rsa_softmax_sample_args* args, rsa_stream_t stream)
 /* The same draw for caller-supplied uniforms (the tests hit the table edges with it). */
 int rsa_softmax_lookup(const rsa_softmax_sample_args* args, rsa_stream_t stream);
 
+/* Sparse (CSR) times dense, the propagation step of the graph retrievers (LightGCN: recstudio/model/graph/lightgcn.py:51-62,
+ * recstudio/model/module/graphmodule.py:168-198 with mess_norm = 'both'):
+ *   y[r, :]       = row_scale[r] * sum_e values[e] * x[indices[e], :]       e in [indptr[r], indptr[r + 1]), r in [0, n_rows)
+ *   acc_out[r, :] = acc_scale * (acc_in[r, :] + y[r, :])                    when acc_out is given
+ * values null: all ones; row_scale null: 1.  y is nullable when acc_out is given; acc_in and acc_out may be the same buffer (x
+ * must not alias y or acc_out).  fp32 throughout, every product and every sum rounded once (no FMA contraction).  dim is a
+ * multiple of 4 and at most 256; x, y, acc_in, acc_out and partials are 16-byte aligned.  Row and byte offsets are 64-bit.
+ * No atomics: a row is summed by one wave in an order fixed by the matrix, dim and the plan, so two runs are bit-equal.
+ *
+ * THE PLAN (built once per matrix; ops.spmm_plan builds it with torch ops, any caller can from indptr alone).  Rows with more
+ * than `chunk` edges ("split rows") are cut into pieces of `chunk` consecutive edges (the last one shorter); a piece is summed by
+ * a wave of its own into partials[p, :] and a second launch adds a split row's partials in ascending p and applies row_scale and
+ * the accumulation.  Rows of at most `chunk` edges take no part in the plan.  `plan` is ONE int64 device array of
+ * plan_len >= 2 * n_split + 1 + 2 * n_parts entries:
+ *   [0, n_split)                         split_row[s]   the split rows, ascending
+ *   [n_split, 2 n_split + 1)             split_part[s]  first piece of split row s; split_part[n_split] = n_parts
+ *   [2 n_split + 1, .. + n_parts)        part_row[p]    the row of piece p (= split_row[s] for split_part[s] <= p < split_part[s + 1])
+ *   [2 n_split + 1 + n_parts, .. + n_parts)  part_edge[p]  its first edge: indptr[row] + (p - split_part[s]) * chunk
+ * chunk, n_split and n_parts travel in the argument block (the checks below run on the host and do not read device memory).
+ * partials: caller-owned fp32 [n_parts, dim] (partials_bytes >= n_parts * dim * 4), overwritten by every call.
+ * A null pointer among indptr / indices / x, neither y nor acc_out, acc_out without acc_in, a bad dim, a negative size, chunk < 1,
+ * a plan_len or partials_bytes that is too small: RSA_ERR_ARG before the first HIP call.  Out-of-range entries of indptr /
+ * indices / plan are clamped into the arrays, never followed.  Two launches (one when n_split == 0); nothing is allocated and
+ * nothing synchronises. */
+typedef struct rsa_spmm_args {
+  int64_t size;                /* sizeof(rsa_spmm_args) */
+  const int64_t* indptr;       /* [n_rows + 1] */
+  const int32_t* indices;      /* [nnz] column of every edge */
+  const float* values;         /* nullable [nnz] */
+  int64_t n_rows;
+  int64_t n_cols;              /* rows of x */
+  int64_t nnz;
+  int32_t dim;
+  int32_t _pad;
+  const float* x;              /* [n_cols, dim] */
+  const float* row_scale;      /* nullable [n_rows] */
+  float* y;                    /* nullable [n_rows, dim] out */
+  const float* acc_in;         /* nullable [n_rows, dim] */
+  float* acc_out;              /* nullable [n_rows, dim] out (may be acc_in) */
+  float acc_scale;
+  float _pad2;
+  int64_t chunk;               /* the plan's chunk size (>= 1) */
+  int64_t n_split;             /* rows longer than chunk */
+  int64_t n_parts;             /* their pieces = rows of partials */
+  const int64_t* plan;         /* nullable when n_split == 0 */
+  int64_t plan_len;
+  float* partials;             /* nullable when n_parts == 0 */
+  int64_t partials_bytes;
+} rsa_spmm_args;
+int rsa_spmm_csr(const rsa_spmm_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

@@ -244,6 +244,17 @@ class SoftmaxSampleArgs(_Sized):
     ]
 
 
+class SpmmArgs(_Sized):
+    """struct rsa_spmm_args."""
+    _fields_ = [
+        ('size', c_int64), ('indptr', c_void_p), ('indices', c_void_p), ('values', c_void_p), ('n_rows', c_int64),
+        ('n_cols', c_int64), ('nnz', c_int64), ('dim', c_int32), ('_pad', c_int32), ('x', c_void_p), ('row_scale', c_void_p),
+        ('y', c_void_p), ('acc_in', c_void_p), ('acc_out', c_void_p), ('acc_scale', c_float), ('_pad2', c_float),
+        ('chunk', c_int64), ('n_split', c_int64), ('n_parts', c_int64), ('plan', c_void_p), ('plan_len', c_int64),
+        ('partials', c_void_p), ('partials_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -253,7 +264,7 @@ STRUCTS = {
     'rsa_rows_update_args': RowsUpdateArgs, 'rsa_bpr_sgd_args': BprSgdArgs, 'rsa_seg_gather_args': SegGatherArgs,
     'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
-    'rsa_softmax_sample_args': SoftmaxSampleArgs,
+    'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -339,6 +350,7 @@ SIGNATURES = {
     'rsa_softmax_sample_block': (c_int32, []),
     'rsa_softmax_sample': (c_int, [POINTER(SoftmaxSampleArgs), c_void_p]),
     'rsa_softmax_lookup': (c_int, [POINTER(SoftmaxSampleArgs), c_void_p]),
+    'rsa_spmm_csr': (c_int, [POINTER(SpmmArgs), c_void_p]),
 }
 
 _lib = None

@@ -479,6 +479,37 @@ class TripletDataset:
             hist[sk, col] = val[order]
         return hist, count
 
+    def get_graph(self, idx, form='coo', value_fields=None, row_offset=0, col_offset=0, bidirectional=False, shape=None):
+        """recstudio/data/dataset.py:575-726 for the interaction graph (``idx = [0]``) of this split: every interaction (u, i) is
+        the edge ``u + row_offset -> i + col_offset`` (duplicates kept), ``bidirectional`` appends the reversed edges behind them.
+        -> ((rows, cols, vals, shape), num_relations): torch COO tensors (int64, int64, and the reference's edge values: 1 / 2 for the
+        forward / reversed edges with ``value_fields='inter'``, float ones without) instead of the reference's scipy / dgl
+        objects, which cannot be assumed where this package runs.  Networks other than the interactions are not covered."""
+        unlist = lambda v: v[0] if isinstance(v, (list, tuple)) and len(v) == 1 else v      # noqa: E731
+        idx, value_field, bidirectional = unlist(idx), unlist(value_fields), bool(unlist(bidirectional))
+        row_offset, col_offset = unlist(row_offset) or 0, unlist(col_offset) or 0
+        if idx != 0:
+            raise NotImplementedError(f'get_graph: only the interaction graph (idx = [0]) is covered, got idx = {idx!r}')
+        if form not in ('coo', 'torch'):
+            raise NotImplementedError(f"get_graph: form {form!r} is not covered (torch COO tensors are returned as form 'coo')")
+        if not isinstance(row_offset, int) or not isinstance(col_offset, int):
+            raise NotImplementedError('get_graph: one row_offset / col_offset per graph')
+        sub = self.inter_feat_subset
+        source = self.inter_feat[self.fuid][sub] + row_offset
+        target = self.inter_feat[self.fiid][sub] + col_offset
+        rows, cols = (torch.cat([source, target]), torch.cat([target, source])) if bidirectional else (source, target)
+        if value_field is None:
+            vals, n_rel = torch.ones(len(rows)), 0
+        elif value_field == 'inter':
+            vals = torch.cat([torch.full((len(source),), 1), torch.full((len(source),), 2)]) if bidirectional \
+                else torch.full((len(source),), 1)
+            n_rel = 3 if bidirectional else 2
+        else:
+            raise NotImplementedError(f"get_graph: value_fields must be None or 'inter', got {value_field!r}")
+        if shape is None:
+            shape = (self.num_users, self.num_items)
+        return (rows, cols, vals, tuple(shape)), n_rel
+
     # ------------------------------------------------------------------ build / split
     def build(self, binarized_rating_thres=None, fmeval=False, neg_count=None, sampler=None, shuffle=True,
               split_mode='user_entry', split_ratio=(0.8, 0.1, 0.1), **kwargs):

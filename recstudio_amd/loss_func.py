@@ -12,7 +12,15 @@ from . import _native as nat
 from . import ops
 
 __all__ = ['FullScoreLoss', 'PairwiseLoss', 'PointwiseLoss', 'BPRLoss', 'SampledSoftmaxLoss', 'SoftmaxLoss',
-           'BinaryCrossEntropyLoss']
+           'BinaryCrossEntropyLoss', 'l2_reg_loss_fn']
+
+
+def l2_reg_loss_fn(*args):
+    """recstudio/model/loss_func.py:189-193: sum over the given [B, D] embeddings of mean_b ||emb_b||^2."""
+    loss = 0.
+    for emb in args:
+        loss = loss + torch.mean(torch.sum(emb * emb, dim=-1))
+    return loss
 
 
 class FullScoreLoss(torch.nn.Module):

@@ -1352,3 +1352,116 @@ def row_topk(values, k):
 def rng_advance(offset_dev, increment):
     """*offset_dev += increment on the stream (rsa_rng_advance): the device copy of the generator offset."""
     _launch('rsa_rng_advance', ptr(offset_dev), int(increment))
+
+
+# ------------------------------------------------------------------ sparse x dense (graph propagation)
+SPMM_MAX_DIM = 256
+# Rows longer than this are cut into pieces summed by separate waves (include/recstudio_amd.h, "THE PLAN").  Measured on the
+# Zipf graph of tools/bench_lightgcn.py (DESIGN 4.9): 128 / 256 / 512 / 1024 / 2048 edges -> 8.5 / 6.1 / 4.9 / 4.3 / 4.0 ms per layer.
+SPMM_CHUNK = 2048
+
+
+class SpmmPlan:
+    """The chunk list of one CSR matrix for ``spmm_csr`` (``spmm_plan`` builds it, once per matrix): ``table`` is the int64 array
+    rsa_spmm_args.plan describes -- split_row [n_split], split_part [n_split + 1], part_row [n_parts], part_edge [n_parts] --, and
+    the partials workspace [n_parts, d] is kept here between calls."""
+
+    def __init__(self, chunk, n_rows, nnz, n_split, n_parts, table):
+        self.chunk, self.n_rows, self.nnz, self.n_split, self.n_parts, self.table = chunk, n_rows, nnz, n_split, n_parts, table
+        self._partials = None
+
+    def to(self, device):
+        if self.table.device != torch.device(device):
+            self.table, self._partials = self.table.to(device), None
+        return self
+
+    def split_row(self):
+        return self.table[:self.n_split]
+
+    def split_part(self):
+        return self.table[self.n_split:2 * self.n_split + 1]
+
+    def part_row(self):
+        return self.table[2 * self.n_split + 1:2 * self.n_split + 1 + self.n_parts]
+
+    def part_edge(self):
+        return self.table[2 * self.n_split + 1 + self.n_parts:]
+
+    def partials(self, dim, device):
+        need = self.n_parts * dim
+        if self._partials is None or self._partials.numel() < need or self._partials.device != device:
+            self._partials = torch.empty(max(need, 4), dtype=torch.float32, device=device)
+        return self._partials
+
+
+def spmm_plan(indptr, chunk=SPMM_CHUNK):
+    """The plan of ``spmm_csr`` for the matrix whose row pointer is ``indptr`` int64 [R + 1] (host or device; the plan lives where
+    ``indptr`` does): rows of more than ``chunk`` edges are cut into pieces of ``chunk`` consecutive edges."""
+    if not isinstance(indptr, torch.Tensor) or indptr.dtype != torch.int64 or indptr.dim() != 1 or indptr.numel() < 1:
+        raise TypeError('spmm_plan: indptr must be an int64 tensor [R + 1]')
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f'spmm_plan: chunk must be at least 1, got {chunk}')
+    deg = indptr[1:] - indptr[:-1]
+    if deg.numel() and int(deg.min()) < 0:
+        raise ValueError('spmm_plan: indptr must not decrease')
+    split = (deg > chunk).nonzero().view(-1)
+    pieces = (deg[split] + chunk - 1) // chunk
+    split_part = torch.cat([pieces.new_zeros(1), torch.cumsum(pieces, 0)])
+    n_split, n_parts = int(split.numel()), int(split_part[-1])
+    owner = torch.repeat_interleave(torch.arange(n_split, device=indptr.device), pieces)
+    part_row = split[owner]
+    part_edge = indptr[part_row] + (torch.arange(n_parts, device=indptr.device) - split_part[owner]) * chunk
+    table = torch.cat([split, split_part, part_row, part_edge]).contiguous()
+    return SpmmPlan(chunk, int(deg.numel()), int(indptr[-1]) if indptr.numel() else 0, n_split, n_parts, table)
+
+
+@_on_device
+def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=None, acc_scale=1.0):
+    """rsa_spmm_csr: ``y[r] = row_scale[r] * sum_e values[e] * x[indices[e]]`` over the edges ``[indptr[r], indptr[r + 1])`` of
+    row r -- ``indptr`` int64 [R + 1], ``indices`` int32 [nnz], ``values`` fp32 [nnz] or None (all ones), ``x`` fp32 [C, d] with d
+    a multiple of 4 and at most 256, ``row_scale`` fp32 [R] or None, ``plan`` = ``spmm_plan(indptr)``.  No atomics; bit-equal
+    from run to run.
+    ``acc`` fp32 [R, d]: also ``acc <- acc_scale * (acc + y)`` IN PLACE, in the same pass (the running layer sum of LightGCN; the
+    last layer's ``acc_scale = 1 / (L + 1)`` makes it the mean).  With ``acc`` and without ``y`` the product itself is not written.
+    Without ``acc``, ``y`` None allocates the result.  Returns ``y`` when it was written, else ``acc``."""
+    indptr = _need(indptr, torch.int64, 'indptr')
+    indices = _need(indices, torch.int32, 'indices')
+    values = _need_opt(values, torch.float32, 'values')
+    x = _need(x, torch.float32, 'x')
+    row_scale = _need_opt(row_scale, torch.float32, 'row_scale')
+    if not isinstance(plan, SpmmPlan):
+        raise TypeError('spmm_csr: plan must come from spmm_plan(indptr)')
+    R, nnz = indptr.numel() - 1, indices.numel()
+    if x.dim() != 2 or x.shape[1] % 4 or not 4 <= x.shape[1] <= SPMM_MAX_DIM:
+        raise ValueError(f'spmm_csr: x must be [C, d] with d a multiple of 4 and at most {SPMM_MAX_DIM}, got {tuple(x.shape)}')
+    C, d = x.shape
+    if plan.n_rows != R or plan.nnz != nnz:
+        raise ValueError(f'spmm_csr: the plan was built for {plan.n_rows} rows / {plan.nnz} edges, the matrix has {R} / {nnz}')
+    if values is not None and values.numel() != nnz:
+        raise ValueError('spmm_csr: values must hold one weight per edge')
+    if row_scale is not None and row_scale.numel() != R:
+        raise ValueError('spmm_csr: row_scale must hold one factor per row')
+    dev = x.device
+    plan.to(dev)
+    for name, t in (('y', y), ('acc', acc)):
+        if t is not None:
+            _need_view(t, torch.float32, name)
+            if tuple(t.shape) != (R, d) or not t.is_contiguous():
+                raise ValueError(f'spmm_csr: {name} must be a contiguous [{R}, {d}] tensor')
+            if t.data_ptr() == x.data_ptr() and t.numel():
+                raise ValueError(f'spmm_csr: {name} must not alias x')
+    if y is None and acc is None:
+        y = torch.empty(R, d, dtype=torch.float32, device=dev)
+    partials = plan.partials(d, dev) if plan.n_parts else None
+    a = nat.SpmmArgs()
+    a.indptr, a.indices, a.values = ptr(indptr), ptr(indices), ptr(values)
+    a.n_rows, a.n_cols, a.nnz, a.dim = R, C, nnz, d
+    a.x, a.row_scale, a.y = ptr(x), ptr(row_scale), ptr(y)
+    a.acc_in, a.acc_out, a.acc_scale = ptr(acc), ptr(acc), float(acc_scale)
+    a.chunk, a.n_split, a.n_parts = plan.chunk, plan.n_split, plan.n_parts
+    if plan.n_split:
+        a.plan, a.plan_len = ptr(plan.table), plan.table.numel()
+        a.partials, a.partials_bytes = ptr(partials), partials.numel() * 4
+    _launch('rsa_spmm_csr', ctypes.byref(a))
+    return y if y is not None else acc

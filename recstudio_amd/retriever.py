@@ -31,7 +31,7 @@ from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, Pairwise
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
 
-__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'default_config',
+__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'LightGCN', 'default_config',
            'seed_everything']
 
 
@@ -517,18 +517,25 @@ class BaseRetriever(torch.nn.Module):
         result = (log_pos_prob.detach(), neg_id, log_neg_prob.detach())
         return (result, query) if return_query else (result, None)
 
+    def _fullscore_catalog(self):
+        """The catalog size (padding row included) when ``topk`` can run the MFMA kernel over ``item_vector`` -- a stock scorer
+        over an nn.Embedding item tower --, else None: scores are materialised and ``torch.topk`` selects."""
+        if type(self.score_func) in (InnerProductScorer, CosineScorer, EuclideanScorer) \
+                and isinstance(self.item_encoder, torch.nn.Embedding):
+            return self.item_encoder.weight.shape[0]
+        return None
+
     def topk(self, batch, k, user_h=None, return_query=False):
         """baseretriever.py:374-397: full-catalog scores -> top (k + |hist|) -> drop history -> top k."""
         query = self.query_encoder(self._get_query_feat(batch))
         if getattr(self, '_shard', None) is not None:
             return self._topk_sharded(query, k, user_h, return_query)
         more = user_h.size(1) if user_h is not None else 0
-        if type(self.score_func) in (InnerProductScorer, CosineScorer, EuclideanScorer) \
-                and isinstance(self.item_encoder, torch.nn.Embedding):
+        n_items = self._fullscore_catalog()
+        if n_items is not None:
             # the MFMA kernel: scores + exact top-(k + more) without the [B, N] matrix (cosine / Euclidean: the tile
             # epilogue applies the norms, scorer.py:19-34); embed_dim > 128 or k + more > 1024 (a user whose history
             # is longer than that, e.g. ml-1m) are composed from the same kernel on materialised scores (ops.fullscore)
-            n_items = self.item_encoder.weight.shape[0]
             kc = min(k + more, n_items - 1)
             table = self.item_vector if hasattr(self, 'item_vector') else self._get_item_vector()
             q = query.detach().contiguous()
@@ -1144,6 +1151,114 @@ class BPR(BaseRetriever):
 
     def _get_sampler(self, train_data):
         return UniformSampler(train_data.num_items)
+
+
+class LightGCN(BaseRetriever):
+    """recstudio/model/graph/lightgcn.py:14-84, recstudio/model/graph/config/{all,lightgcn}.yaml (n_layers 3, l2_reg_weight 1e-4,
+    negative_count 1).  The base tables ``user_emb`` / ``item_emb`` are propagated over the normalised interaction graph
+    (``graphmodule.NormAdj``, ``rsa_spmm_csr``); everything behind the propagation is the fused path: the propagated item table is
+    the ``item_weight`` of ``fused.retriever_scores``, the propagated user table its ``query_src`` with the batch's user ids as
+    ``query_index`` -- the negatives are drawn in the kernel (the ids ``UniformSampler`` gives for the seed), no [B, n, d] tensor
+    exists, and the dense table gradients flow back into the propagation's backward.  The towers are not nn.Embedding modules,
+    so ``train.fused_optimizer``, multi-GPU ``fit`` and ``train.ann`` refuse this model as they refuse any such tower."""
+
+    def __init__(self, config=None, **kwargs):
+        super().__init__(config, **kwargs)
+        self.config['model'].setdefault('n_layers', 3)
+        self.config['model'].setdefault('l2_reg_weight', 1e-4)
+        given = config or {}
+        for group, key, value in (('train', 'negative_count', 1), ('train', 'early_stop_patience', 100), ('eval', 'cutoff', [20, 10, 5])):
+            if key not in given.get(group, {}):
+                self.config[group][key] = value
+
+    def _init_model(self, train_data, drop_unused_field=True):
+        from . import graphmodule
+        super()._init_model(train_data, drop_unused_field)
+        self.num_users, self.num_items = train_data.num_users, train_data.num_items
+        self.user_emb = torch.nn.Embedding(self.num_users, self.embed_dim, padding_idx=0)
+        self.item_emb = torch.nn.Embedding(self.num_items, self.embed_dim, padding_idx=0)
+        self.LightGCNNet = graphmodule.LightGCNNet(self.config['model']['n_layers'])
+        self.adj_mat = self._get_graph(train_data)
+
+    def _get_graph(self, train_data):
+        """The normalised adjacency of the training interactions (``model.spmm_chunk``: the chunk size of its plan, default
+        ``ops.SPMM_CHUNK``)."""
+        from . import graphmodule
+        return graphmodule.NormAdj.from_dataset(train_data, chunk=self.config['model'].get('spmm_chunk'))
+
+    def _get_dataset_class():
+        return TripletDataset
+
+    def _get_loss_func(self):
+        return BPRLoss()
+
+    def _get_score_func(self):
+        return InnerProductScorer()
+
+    def _get_sampler(self, train_data):
+        return UniformSampler(train_data.num_items)
+
+    def _get_query_encoder(self, train_data):
+        from . import graphmodule
+        return graphmodule.GraphUserEncoder()
+
+    def _get_item_encoder(self, train_data):
+        from . import graphmodule
+        return graphmodule.GraphItemEncoder()
+
+    def _propagate(self, embeddings):
+        return self.LightGCNNet.propagate(self.adj_mat, embeddings)
+
+    def update_encoders(self):
+        embeddings = torch.cat([self.user_emb.weight, self.item_emb.weight], dim=0)
+        all_embeddings = self._propagate(embeddings)
+        self.query_encoder.user_embeddings, self.item_encoder.item_embeddings = \
+            all_embeddings[:self.num_users], all_embeddings[self.num_users:]
+
+    def forward(self, batch, full_score=False, return_query=True, return_item=True, return_neg_item=False, return_neg_id=True):
+        self.update_encoders()
+        users, items = self.query_encoder.user_embeddings, self.item_encoder.item_embeddings
+        pos_items, uid = self._get_item_feat(batch), batch[self.fuid]
+        if self.neg_count is None or isinstance(self.neg_count, (list, tuple)) or type(self.score_func) is not InnerProductScorer \
+                or self.config['train'].get('sampling_method', 'none') != 'none' or pos_items.dim() != 1:
+            return self._forward_plugins(batch, full_score, return_query, return_item, return_neg_item, return_neg_id)
+        n = self.neg_count
+        score, neg_ids = retriever_scores(items, users, n, query_index=uid, pos_ids=pos_items, sampler=self.sampler)
+        output = {'score': {'pos_score': score['pos_score'], 'log_pos_prob': score['log_pos_prob'].detach(),
+                            'neg_score': score['neg_score'].view(-1, n), 'log_neg_prob': score['log_neg_prob'].view(-1, n).detach()}}
+        if return_neg_id:
+            output['neg_id'] = neg_ids.view(-1, n)
+        if return_neg_item:
+            output['neg_item'] = self.item_encoder(neg_ids.view(-1, n))
+        if return_query:
+            output['query'] = self.query_encoder(uid)
+        if return_item:
+            output['item'] = self.item_encoder(pos_items)
+        return output
+
+    def training_step(self, batch):
+        from .loss_func import l2_reg_loss_fn
+        output = self.forward(batch, isinstance(self.loss_fn, FullScoreLoss), return_query=False, return_item=False, return_neg_id=True)
+        score = dict(output['score'], label=batch[self.frating])
+        # the regulariser sees the BASE rows of the batch (lightgcn.py:72-73), through the gather / sorted-scatter autograd node
+        reg = l2_reg_loss_fn(_EmbedFn.apply(self.user_emb.weight, batch[self.fuid]),
+                             _EmbedFn.apply(self.item_emb.weight, batch[self.fiid]),
+                             _EmbedFn.apply(self.item_emb.weight, output['neg_id'].reshape(-1)))
+        return self.loss_fn(**score) + self.config['model']['l2_reg_weight'] * reg
+
+    def _get_item_vector(self):
+        if self.item_encoder.item_embeddings is None:
+            return self.item_emb.weight[1:].detach().clone()
+        return self.item_encoder.item_embeddings[1:].detach().clone()
+
+    @torch.no_grad()
+    def _update_item_vector(self):
+        self.update_encoders()
+        super()._update_item_vector()
+
+    def _fullscore_catalog(self):
+        # ``item_vector`` is a plain fp32 table (the propagated item rows): the MFMA top-k reads it as it reads an nn.Embedding's
+        return self.num_items if type(self.score_func) in (InnerProductScorer, CosineScorer, EuclideanScorer) else None
 
 
 class _EmbedFn(torch.autograd.Function):

@@ -1,0 +1,185 @@
+"""Times the LightGCN propagation kernel (ops.spmm_csr / rsa_spmm_csr) next to torch.sparse.mm on the same matrix, on a graph of the
+same size with evenly spread degrees, and inside a whole LightGCN training step; one process, one device, the arms alternating (a, b,
+c, a, b, c, ...), device events around every call, warm-up calls first.  Prints one JSON object and writes it to
+profiles/lightgcn_bench.json.
+
+    python tools/bench_lightgcn.py [--users 1048576 --items 1048576 --inter 67108864 --dims 64 128 --reps 10 --warmup 3]
+
+Graph: dataset.synthetic_interactions(users, items, inter, alpha=1.0) -- users uniform, items Zipf(1) -- as the bidirectional
+normalised adjacency (graphmodule.NormAdj): 2 * inter non-zeros over users + items + 2 rows.
+Arms, per width d:
+  (a) spmm        ops.spmm_csr, one middle layer of LightGCN: the layer output written, the running sum read and written
+  (b) torch       torch.sparse.mm(torch.sparse_csr_tensor(same arrays), x): what a user would write without the kernel
+  (c) even        (a) on a matrix with the same shape and non-zero count whose rows all have the same length
+  (d) step        LightGCN.training_step + backward at --batch, --layers layers, next to the same step with (b) as its propagation
+Recorded: median / min / max in ms; for (a) and (c) the fraction of the 8 TB/s peak on the byte model
+    bytes = nnz (8 + 4 d) + R 4 d (1 write + 2 accumulation) + n_parts 4 d (1 write + 1 read)
+(an edge costs its index, its value and one d-float source row; the plan's partials are written once and read once); the ratios a / b
+and a / c; the degree median and maximum; (a) at d = dims[0] for the chunk sizes of --chunks.
+The script exits non-zero if the median of (a) exceeds the median of (b) in the same run for any width: a hand-written kernel that
+loses to the library call has no reason to be in the tree."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_BYTES_PER_S = 8e12
+
+
+def timed(fns, reps, warmup):
+    """[ms per call] per function, the functions called in turn."""
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    ms = [[] for _ in fns]
+    for _ in range(reps):
+        for i, f in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            f()
+            b.record()
+            b.synchronize()
+            ms[i].append(a.elapsed_time(b))
+    return ms
+
+
+def row(t):
+    return dict(ms=statistics.median(t), ms_min_max=(min(t), max(t)))
+
+
+def model_bytes(nnz, n_rows, d, n_parts):
+    return nnz * (8 + 4 * d) + n_rows * 4 * d * 3 + n_parts * 4 * d * 2
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--users', type=int, default=1 << 20)
+    ap.add_argument('--items', type=int, default=1 << 20)
+    ap.add_argument('--inter', type=int, default=1 << 26)
+    ap.add_argument('--dims', type=int, nargs='+', default=[64, 128])
+    ap.add_argument('--chunks', type=int, nargs='*', default=[128, 256, 512, 1024, 2048, 4096, 8192])
+    ap.add_argument('--batch', type=int, default=4096)
+    ap.add_argument('--layers', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lightgcn_bench.json'))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_lightgcn.py measures on the GPU: none found')
+    import recstudio_amd as ra
+    from recstudio_amd import dataset, graphmodule, ops
+    dev = torch.device('cuda')
+    nu, ni = a.users + 1, a.items + 1                       # the padding ids
+    n = nu + ni
+    users, items = dataset.synthetic_interactions(a.users, a.items, a.inter, alpha=1.0)
+    users, items = torch.from_numpy(users), torch.from_numpy(items)
+    u_dev, i_dev = users.to(dev), items.to(dev) + nu
+    adj = graphmodule.NormAdj(torch.cat([u_dev, i_dev]), torch.cat([i_dev, u_dev]), n, symmetric=True)      # built on the device
+    del u_dev, i_dev
+    nnz = adj.nnz
+    deg = adj.indptr[1:] - adj.indptr[:-1]
+    res = dict(device=torch.cuda.get_device_name(0), users=a.users, items=a.items, interactions=a.inter, rows=n, nnz=nnz,
+               degree_median=float(deg.float().median()), degree_max=int(deg.max()), degree_user_median=float(deg[:nu].float().median()),
+               degree_item_median=float(deg[nu:].float().median()), chunk=adj.plan.chunk, split_rows=adj.plan.n_split,
+               partial_rows=adj.plan.n_parts, reps=a.reps, warmup=a.warmup, peak_bytes_per_s=PEAK_BYTES_PER_S, widths={})
+    print(f'graph built: {n} rows, {nnz} non-zeros, {adj.plan.n_split} split rows', file=sys.stderr, flush=True)
+    # (c): the same shape and non-zero count, every row the same length, random columns
+    per_row = nnz // n
+    even_ptr = torch.arange(n + 1, device=dev, dtype=torch.int64) * per_row
+    even_ptr[-1] = nnz                                      # (the remainder goes to the last row)
+    g = torch.Generator(device=dev).manual_seed(3)
+    even_idx = torch.randint(0, n, (nnz,), device=dev, generator=g, dtype=torch.int32)
+    even_plan = ops.spmm_plan(even_ptr)
+    csr = torch.sparse_csr_tensor(adj.indptr, adj.indices.long(), adj.values, (n, n))
+    ok = True
+    for d in a.dims:
+        x = torch.empty(n, d, device=dev).normal_(0, 0.1, generator=g)
+        y, acc = torch.empty_like(x), torch.zeros_like(x)
+        arm_a = lambda: ops.spmm_csr(adj.indptr, adj.indices, adj.values, x, plan=adj.plan, y=y, acc=acc)                # noqa: E731
+        arm_b = lambda: torch.sparse.mm(csr, x)                                                                          # noqa: E731
+        arm_c = lambda: ops.spmm_csr(even_ptr, even_idx, adj.values, x, plan=even_plan, y=y, acc=acc)                    # noqa: E731
+        ms = timed([arm_a, arm_b, arm_c], a.reps, a.warmup)
+        w = dict(spmm=row(ms[0]), torch_sparse_mm=row(ms[1]), even=row(ms[2]), table_bytes=n * d * 4)
+        for key, parts in (('spmm', adj.plan.n_parts), ('even', even_plan.n_parts)):
+            w[key]['model_bytes'] = model_bytes(nnz, n, d, parts)
+            w[key]['fraction_of_peak'] = w[key]['model_bytes'] / (w[key]['ms'] * 1e-3) / PEAK_BYTES_PER_S
+        w['spmm_over_torch'] = w['spmm']['ms'] / w['torch_sparse_mm']['ms']
+        w['spmm_over_even'] = w['spmm']['ms'] / w['even']['ms']
+        err = (torch.sparse.mm(csr, x) - ops.spmm_csr(adj.indptr, adj.indices, adj.values, x, plan=adj.plan)).abs().max()
+        w['max_abs_difference_to_torch'] = float(err)
+        ok = ok and w['spmm']['ms'] <= w['torch_sparse_mm']['ms']
+        res['widths'][str(d)] = w
+        print(f'd = {d}: {json.dumps(w)}', file=sys.stderr, flush=True)
+        if d == a.dims[0] and a.chunks:
+            plans = [ops.spmm_plan(adj.indptr, c) for c in a.chunks]
+            fns = [lambda p=p: ops.spmm_csr(adj.indptr, adj.indices, adj.values, x, plan=p, y=y, acc=acc) for p in plans]
+            res['chunk_sweep'] = {str(c): dict(row(t), partial_rows=p.n_parts, split_rows=p.n_split)
+                                  for c, p, t in zip(a.chunks, plans, timed(fns, a.reps, a.warmup))}
+            del plans, fns
+        del x, y, acc
+    del even_ptr, even_idx, even_plan
+
+    # (d): the whole training step
+    class OnDevice(ra.LightGCN):
+        def _get_graph(self, train_data):
+            return adj
+
+    class TorchSparse(OnDevice):
+        class _Fn(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, e, layers):
+                ctx.layers = layers
+                x = s = e
+                for _ in range(layers):
+                    x = torch.sparse.mm(csr, x)
+                    s = s + x
+                return s / (layers + 1)
+
+            @staticmethod
+            def backward(ctx, grad):          # the matrix is symmetric
+                return TorchSparse._Fn.forward(ctx, grad.contiguous(), ctx.layers), None
+
+        def _propagate(self, e):
+            return TorchSparse._Fn.apply(e, self.config['model']['n_layers'])
+
+    data = ra.TripletDataset.from_mapped_ids(users, items, n_users=nu, n_items=ni)
+    cfg = {'model': {'embed_dim': a.dims[0], 'n_layers': a.layers}, 'train': {'negative_count': 1}}
+    steps = []
+    for cls in (OnDevice, TorchSparse):
+        m = cls(cfg)
+        m._init_model(data)
+        m._init_parameter()
+        m.to(dev)
+        gb = torch.Generator(device=dev).manual_seed(5)
+        pick = [torch.randint(0, a.inter, (a.batch,), device=dev, generator=gb).cpu() for _ in range(4)]
+        batches = [{data.fuid: users[p].to(dev), data.fiid: items[p].to(dev), data.frating: torch.ones(a.batch, device=dev)} for p in pick]
+        turn = {'k': 0}
+
+        def step(m=m, batches=batches, turn=turn):
+            turn['k'] += 1
+            for p in m.parameters():
+                p.grad = None
+            m.training_step(batches[turn['k'] % len(batches)]).backward()
+        steps.append(step)
+    ms = timed(steps, a.reps, a.warmup)
+    res['training_step'] = dict(batch=a.batch, layers=a.layers, dim=a.dims[0], spmm=row(ms[0]), torch_sparse_mm=row(ms[1]),
+                                spmm_over_torch=statistics.median(ms[0]) / statistics.median(ms[1]))
+    res['spmm_not_slower_than_torch'] = ok
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    print(json.dumps(res))
+    if not ok:
+        raise SystemExit('ops.spmm_csr is slower than torch.sparse.mm on the same matrix in this run')
+
+
+if __name__ == '__main__':
+    main()
