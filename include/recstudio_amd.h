@@ -839,6 +839,45 @@ typedef struct rsa_spmm_args {
 } rsa_spmm_args;
 int rsa_spmm_csr(const rsa_spmm_args* args, rsa_stream_t stream);
 
+/* Graph augmentation of the self-supervised graph retrievers (SGL: recstudio/model/graph/sgl.py,
+ * recstudio/model/module/data_augmentation.py:229-304, the dgl branch): thin the SYMMETRIC base graph held as the CSR of
+ * rsa_spmm_csr (rows = destinations, indices = sources) and renormalise it by the degrees that survive.  rev[e] is the position
+ * of edge e's reverse edge (a bijection: rev[rev[e]] = e, indices[rev[e]] = row(e), row(rev[e]) = indices[e]).
+ *   keep[e]     = floor(u_e + keep_prob) != 0, u_e = element e of torch.rand(nnz) for the given Philox state (one fp32 add, the
+ *                 rule of data_augmentation.py:250-251); and, with node_drop, neither end of e flagged.  keep_prob >= 1 consumes
+ *                 no uniforms.  The two directions of an interaction are separate edges with separate draws (dgl.DropEdge on the
+ *                 bidirectional graph): the thinned matrix is NOT symmetric.
+ *   in_deg[r]   = kept edges of row r;  out_deg[c] = kept edges with source c (= the count over row c of keep[rev[e]])
+ *   values[e]   = keep[e] ? (float)(f(out_deg[indices[e]]) * f(in_deg[r])) : +0,  f(k) = 1.0 / sqrt((double)k); the product is
+ *                 taken in double and rounded once (GraphConv norm = 'both' on the thinned graph; no 1 / keep_prob factor)
+ *   t_values[e] = values[rev[e]]: the TRANSPOSED thinned matrix in the same indptr / indices (and the same rsa_spmm_csr plan)
+ * No float atomics; the degrees of rows longer than long_row (0: 2048; at least 128) are integer atomic sums of per-wave counts, at
+ * most ceil(K / 64) per counter for a row of K edges; two runs are bit-equal.  Entries of indptr / indices / rev are clamped into
+ * their arrays, never followed out of them.  A null indptr / indices / rev / values / in_deg / out_deg, a negative size, keep_prob
+ * outside [0, 1], a long_row in [1, 128): RSA_ERR_ARG before the first HIP call.  One memset and two launches on the stream;
+ * nothing is allocated and nothing synchronises. */
+typedef struct rsa_graph_dropout_args {
+  int64_t size;                /* sizeof(rsa_graph_dropout_args) */
+  const int64_t* indptr;       /* [n_rows + 1] */
+  const int32_t* indices;      /* [nnz] */
+  const int64_t* rev;          /* [nnz] */
+  int64_t n_rows;
+  int64_t nnz;
+  uint64_t seed;               /* Philox state of the torch.rand(nnz) call this stands for */
+  uint64_t offset;
+  uint32_t grid_threads;
+  float keep_prob;
+  uint64_t elem_base;
+  const uint8_t* node_drop;    /* nullable [n_rows]: non-zero = every edge at this node falls */
+  uint8_t* keep;               /* nullable [nnz] out */
+  int32_t* in_deg;             /* [n_rows] out */
+  int32_t* out_deg;            /* [n_rows] out */
+  float* values;               /* [nnz] out */
+  float* t_values;             /* nullable [nnz] out */
+  int64_t long_row;            /* 0: the default */
+} rsa_graph_dropout_args;
+int rsa_graph_dropout(const rsa_graph_dropout_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

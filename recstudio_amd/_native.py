@@ -255,6 +255,16 @@ class SpmmArgs(_Sized):
     ]
 
 
+class GraphDropoutArgs(_Sized):
+    """struct rsa_graph_dropout_args."""
+    _fields_ = [
+        ('size', c_int64), ('indptr', c_void_p), ('indices', c_void_p), ('rev', c_void_p), ('n_rows', c_int64), ('nnz', c_int64),
+        ('seed', c_uint64), ('offset', c_uint64), ('grid_threads', c_uint32), ('keep_prob', c_float), ('elem_base', c_uint64),
+        ('node_drop', c_void_p), ('keep', c_void_p), ('in_deg', c_void_p), ('out_deg', c_void_p), ('values', c_void_p),
+        ('t_values', c_void_p), ('long_row', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -265,6 +275,7 @@ STRUCTS = {
     'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
+    'rsa_graph_dropout_args': GraphDropoutArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -351,6 +362,7 @@ SIGNATURES = {
     'rsa_softmax_sample': (c_int, [POINTER(SoftmaxSampleArgs), c_void_p]),
     'rsa_softmax_lookup': (c_int, [POINTER(SoftmaxSampleArgs), c_void_p]),
     'rsa_spmm_csr': (c_int, [POINTER(SpmmArgs), c_void_p]),
+    'rsa_graph_dropout': (c_int, [POINTER(GraphDropoutArgs), c_void_p]),
 }
 
 _lib = None

@@ -10,7 +10,7 @@ import torch
 
 from . import ops
 
-__all__ = ['NormAdj', 'LightGCNNet', 'GraphUserEncoder', 'GraphItemEncoder']
+__all__ = ['NormAdj', 'AugmentedAdj', 'LightGCNNet', 'GraphUserEncoder', 'GraphItemEncoder']
 
 
 def _csr_by(key, other, weights, n):
@@ -28,7 +28,9 @@ class NormAdj:
     degree of 0 giving the factor 0.  Stored as the CSR over destination rows -- ``indptr`` int64 [n + 1], ``indices`` int32 [nnz]
     (the sources), ``values`` fp32 [nnz] = the product of the two factors taken in float64 and rounded once -- with the chunk
     ``plan`` of ``ops.spmm_csr``.  The transposed CSR is built as well: the backward of the product multiplies by it.  For the
-    bidirectional interaction graph the matrix is symmetric and the two are the SAME arrays, which ``from_dataset`` asserts."""
+    bidirectional interaction graph the matrix is symmetric and the two are the SAME arrays, which ``from_dataset`` asserts.
+    A symmetric graph also has ``rev`` (int64 [nnz], built on first use): the position of every edge's reverse edge, which
+    ``augmented`` hands to ``ops.graph_dropout``."""
 
     def __init__(self, rows, cols, n_nodes, chunk=None, symmetric=False):
         rows, cols = torch.as_tensor(rows, dtype=torch.int64), torch.as_tensor(cols, dtype=torch.int64)
@@ -56,6 +58,7 @@ class NormAdj:
         else:
             self.t_indptr, self.t_indices, self.t_values = t
             self.t_plan = ops.spmm_plan(self.t_indptr, chunk)
+        self._rev = None
 
     @classmethod
     def from_dataset(cls, train_data, chunk=None):
@@ -75,11 +78,63 @@ class NormAdj:
                 self.t_indptr, self.t_indices, self.t_values = self.indptr, self.indices, self.values
             self.plan.to(device)
             self.t_plan.to(device)
+            if self._rev is not None:
+                self._rev = self._rev.to(device)
         return self
+
+    @property
+    def rev(self):
+        """``rev[e]`` = the position of the edge dst(e) -> src(e): a bijection with ``rev[rev[e]] == e``,
+        ``indices[rev[e]] == row(e)`` and ``row(rev[e]) == indices[e]``; the k-th of the duplicates src -> dst (in edge order, which
+        is the stable order of the input) is paired with the k-th of the duplicates dst -> src.  Symmetric graphs only."""
+        if self._rev is None:
+            if not self.symmetric:
+                raise ValueError('NormAdj.rev: only a symmetric graph has a reverse edge for every edge')
+            deg = self.indptr[1:] - self.indptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.n_nodes, device=deg.device), deg)
+            cols = self.indices.long()
+            # the edges ordered by (row, col) and by (col, row): equal ranks hold an edge and its reverse
+            by_key = torch.sort(rows * self.n_nodes + cols, stable=True).indices
+            by_rkey = torch.sort(cols * self.n_nodes + rows, stable=True).indices
+            rev = torch.empty_like(by_key)
+            rev[by_rkey] = by_key
+            self._rev = rev
+        return self._rev
+
+    def augmented(self, keep_prob, node_drop=None, generator=None):
+        """One randomly thinned, renormalised copy of this graph (``ops.graph_dropout`` on the device the graph lives on) as a
+        view that ``LightGCNNet.propagate`` takes in place of the graph."""
+        if not self.indptr.is_cuda:
+            raise RuntimeError('NormAdj.augmented: move the graph to the GPU first (to(device)); there is no CPU fallback')
+        if node_drop is not None:
+            node_drop = torch.as_tensor(node_drop).to(self.indptr.device)
+        long_row = min(max(self.chunk, 128), ops.GRAPH_DROPOUT_LONG_ROW)      # (a small test chunk also shortens the rows that are shared)
+        values, t_values, in_deg, out_deg, keep = ops.graph_dropout(self.indptr, self.indices, self.rev, keep_prob, node_drop=node_drop,
+                                                                    generator=generator, want_keep=True, long_row=long_row)
+        return AugmentedAdj(self, values, t_values, in_deg, out_deg, keep)
 
     def csr(self, transposed=False):
         return (self.t_indptr, self.t_indices, self.t_values, self.t_plan) if transposed else \
             (self.indptr, self.indices, self.values, self.plan)
+
+
+class AugmentedAdj:
+    """A thinned copy of ``base`` (``NormAdj.augmented``): the base's ``indptr`` / ``indices`` / plan with the weights of the
+    thinned, renormalised matrix (``values``; 0 on a dropped edge) and of its transpose (``t_values``).  ``keep`` uint8 [nnz],
+    ``in_deg`` / ``out_deg`` int32 [n] are kept for inspection."""
+
+    def __init__(self, base, values, t_values, in_deg, out_deg, keep):
+        self.base, self.n_nodes, self.nnz = base, base.n_nodes, base.nnz
+        self.values, self.t_values, self.in_deg, self.out_deg, self.keep = values, t_values, in_deg, out_deg, keep
+
+    def to(self, device):
+        device, mine = torch.device(device), self.values.device
+        if device.type != mine.type or (device.index is not None and device.index != mine.index):
+            raise RuntimeError('AugmentedAdj: a view lives on the device it was drawn on')
+        return self
+
+    def csr(self, transposed=False):
+        return (self.base.indptr, self.base.indices, self.t_values if transposed else self.values, self.base.plan)
 
 
 def _layer_mean(csr, e0, n_layers):
@@ -97,6 +152,49 @@ def _layer_mean(csr, e0, n_layers):
         ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=acc, acc_scale=1.0 / (L + 1) if last else 1.0)
         x = y
     return acc
+
+
+def _layer_mean_each(csrs, e0):
+    """(E_0 + E_1 + ... + E_L) / (L + 1) with E_k = A_k E_{k-1}, one matrix per layer: the launches of ``_layer_mean``."""
+    L = len(csrs)
+    acc = e0.detach().clone(memory_format=torch.contiguous_format)
+    x, spare = e0.detach().contiguous(), [None, None]
+    for k, (indptr, indices, values, plan) in enumerate(csrs):
+        last = k == L - 1
+        y = None
+        if not last:
+            y = spare[k % 2] = torch.empty_like(acc) if spare[k % 2] is None else spare[k % 2]
+        ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=acc, acc_scale=1.0 / (L + 1) if last else 1.0)
+        x = y
+    return acc
+
+
+def _horner_mean(csrs, g):
+    """(g + B_1 (g + B_2 (g + ... B_L g))) / (L + 1) for the matrices ``csrs`` = B_1 .. B_L: h <- g + B_k h from k = L down to
+    1, each step ONE launch (``acc`` = g is read, ``acc_out`` = the new h written), the last one scaling."""
+    L = len(csrs)
+    g = g.detach().contiguous()
+    h, spare = g, [torch.empty_like(g), torch.empty_like(g) if L > 1 else None]
+    for j, k in enumerate(range(L - 1, -1, -1)):
+        indptr, indices, values, plan = csrs[k]
+        out = spare[j % 2]
+        ops.spmm_csr(indptr, indices, values, h, plan=plan, acc=g, acc_out=out, acc_scale=1.0 / (L + 1) if k == 0 else 1.0)
+        h = out
+    return h
+
+
+class _PropagateEachFn(torch.autograd.Function):
+    """One matrix per layer (RandomWalkLightGCN, sgl.py:9-24): with E_k = A_k E_{k-1} the mean's gradient is
+    (g + A_1^T (g + A_2^T (g + ... A_L^T g))) / (L + 1) -- the matrices do not commute, so the recurrence runs from layer L down."""
+
+    @staticmethod
+    def forward(ctx, e0, adjs):
+        ctx.adjs = adjs
+        return _layer_mean_each([a.csr() for a in adjs], e0)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _horner_mean([a.csr(transposed=True) for a in ctx.adjs], g), None
 
 
 class _PropagateFn(torch.autograd.Function):
@@ -121,13 +219,20 @@ class LightGCNNet(torch.nn.Module):
         self.n_layers = int(n_layers)
 
     def propagate(self, adj, embeddings):
-        """``embeddings`` fp32 [n_nodes, d] (d a multiple of 4, at most 256) -> the mean over the layers E_0 .. E_L."""
-        if embeddings.shape[0] != adj.n_nodes:
-            raise ValueError(f'LightGCNNet: {embeddings.shape[0]} embedding rows for a graph of {adj.n_nodes} nodes')
-        adj.to(embeddings.device)
+        """``embeddings`` fp32 [n_nodes, d] (d a multiple of 4, at most 256) -> the mean over the layers E_0 .. E_L.  ``adj``: a
+        ``NormAdj``, an ``AugmentedAdj``, or a list of ``n_layers`` of them, layer k propagating over ``adj[k - 1]``."""
+        each = isinstance(adj, (list, tuple))
+        if each and len(adj) != self.n_layers:
+            raise ValueError(f'LightGCNNet: {len(adj)} graphs for {self.n_layers} layers')
+        for a in adj if each else (adj,):
+            if embeddings.shape[0] != a.n_nodes:
+                raise ValueError(f'LightGCNNet: {embeddings.shape[0]} embedding rows for a graph of {a.n_nodes} nodes')
+            a.to(embeddings.device)
         if self.n_layers == 0:
             return embeddings
-        return _PropagateFn.apply(embeddings, adj, self.n_layers)
+        if each and any(a is not adj[0] for a in adj):
+            return _PropagateEachFn.apply(embeddings, tuple(adj))
+        return _PropagateFn.apply(embeddings, adj[0] if each else adj, self.n_layers)
 
     forward = propagate
 

@@ -1417,14 +1417,16 @@ def spmm_plan(indptr, chunk=SPMM_CHUNK):
 
 
 @_on_device
-def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=None, acc_scale=1.0):
+def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=None, acc_scale=1.0, acc_out=None):
     """rsa_spmm_csr: ``y[r] = row_scale[r] * sum_e values[e] * x[indices[e]]`` over the edges ``[indptr[r], indptr[r + 1])`` of
     row r -- ``indptr`` int64 [R + 1], ``indices`` int32 [nnz], ``values`` fp32 [nnz] or None (all ones), ``x`` fp32 [C, d] with d
     a multiple of 4 and at most 256, ``row_scale`` fp32 [R] or None, ``plan`` = ``spmm_plan(indptr)``.  No atomics; bit-equal
     from run to run.
     ``acc`` fp32 [R, d]: also ``acc <- acc_scale * (acc + y)`` IN PLACE, in the same pass (the running layer sum of LightGCN; the
     last layer's ``acc_scale = 1 / (L + 1)`` makes it the mean).  With ``acc`` and without ``y`` the product itself is not written.
-    Without ``acc``, ``y`` None allocates the result.  Returns ``y`` when it was written, else ``acc``."""
+    ``acc_out`` fp32 [R, d] (with ``acc``): the accumulation is written THERE and ``acc`` is only read -- one step of a Horner
+    recurrence ``h' = acc_scale * (g + A h)`` with g = ``acc``, h = ``x``, h' = ``acc_out``.
+    Without ``acc``, ``y`` None allocates the result.  Returns ``y`` when it was written, else ``acc_out`` / ``acc``."""
     indptr = _need(indptr, torch.int64, 'indptr')
     indices = _need(indices, torch.int32, 'indices')
     values = _need_opt(values, torch.float32, 'values')
@@ -1444,12 +1446,15 @@ def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=No
         raise ValueError('spmm_csr: row_scale must hold one factor per row')
     dev = x.device
     plan.to(dev)
-    for name, t in (('y', y), ('acc', acc)):
+    if acc_out is not None and acc is None:
+        raise ValueError('spmm_csr: acc_out without acc')
+    for name, t in (('y', y), ('acc', acc), ('acc_out', acc_out)):
         if t is not None:
             _need_view(t, torch.float32, name)
             if tuple(t.shape) != (R, d) or not t.is_contiguous():
                 raise ValueError(f'spmm_csr: {name} must be a contiguous [{R}, {d}] tensor')
-            if t.data_ptr() == x.data_ptr() and t.numel():
+            # (acc may be x when the sum goes to acc_out: it is then only read)
+            if t.data_ptr() == x.data_ptr() and t.numel() and not (name == 'acc' and acc_out is not None):
                 raise ValueError(f'spmm_csr: {name} must not alias x')
     if y is None and acc is None:
         y = torch.empty(R, d, dtype=torch.float32, device=dev)
@@ -1458,10 +1463,57 @@ def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=No
     a.indptr, a.indices, a.values = ptr(indptr), ptr(indices), ptr(values)
     a.n_rows, a.n_cols, a.nnz, a.dim = R, C, nnz, d
     a.x, a.row_scale, a.y = ptr(x), ptr(row_scale), ptr(y)
-    a.acc_in, a.acc_out, a.acc_scale = ptr(acc), ptr(acc), float(acc_scale)
+    a.acc_in, a.acc_out, a.acc_scale = ptr(acc), ptr(acc if acc_out is None else acc_out), float(acc_scale)
     a.chunk, a.n_split, a.n_parts = plan.chunk, plan.n_split, plan.n_parts
     if plan.n_split:
         a.plan, a.plan_len = ptr(plan.table), plan.table.numel()
         a.partials, a.partials_bytes = ptr(partials), partials.numel() * 4
     _launch('rsa_spmm_csr', ctypes.byref(a))
-    return y if y is not None else acc
+    return y if y is not None else (acc if acc_out is None else acc_out)
+
+
+GRAPH_DROPOUT_LONG_ROW = 2048      # rows longer than this are counted by several waves (rsa_graphaug.hip, "WORK ITEMS")
+
+
+@_on_device
+def graph_dropout(indptr, indices, rev, keep_prob, *, node_drop=None, generator=None, want_keep=False, long_row=None):
+    """rsa_graph_dropout: thin the symmetric CSR graph (``indptr`` int64 [n + 1], ``indices`` int32 [nnz], ``rev`` int64 [nnz] =
+    the position of every edge's reverse edge) and renormalise it by the surviving degrees.  Edge e is kept iff
+    ``floor(u_e + keep_prob) != 0`` for ``u = torch.rand(nnz, device=...)`` on the device generator (advanced as that call would;
+    not touched when ``keep_prob >= 1``) and, with ``node_drop`` (bool / uint8 [n]), neither of its ends is flagged.
+    -> ``(values, t_values, in_deg, out_deg[, keep])``: fp32 [nnz] weights ``in_deg(dst)^-1/2 out_deg(src)^-1/2`` of the kept
+    edges (0 on the dropped ones) and the same for the transposed thinned matrix (``t_values == values[rev]``), both in the layout
+    -- and for the ``spmm_plan`` -- of the base graph; int32 [n] degrees; ``keep`` uint8 [nnz] with ``want_keep``.  ``long_row``
+    (default 2048, at least 128): rows longer than this are counted by the waves of the edge windows they reach into.  No float
+    atomics; bit-equal from run to run."""
+    indptr = _need(indptr, torch.int64, 'indptr')
+    indices = _need(indices, torch.int32, 'indices')
+    rev = _need(rev, torch.int64, 'rev')
+    n, nnz = indptr.numel() - 1, indices.numel()
+    if indptr.dim() != 1 or n < 0 or rev.numel() != nnz:
+        raise ValueError('graph_dropout: indptr must be [n + 1] and rev must hold one position per edge')
+    keep_prob = float(keep_prob)
+    if not 0.0 <= keep_prob <= 1.0:
+        raise ValueError(f'graph_dropout: keep_prob must lie in [0, 1], got {keep_prob}')
+    if node_drop is not None:
+        if node_drop.dtype == torch.bool:
+            node_drop = node_drop.view(torch.uint8)
+        node_drop = _need(node_drop, torch.uint8, 'node_drop')
+        if node_drop.numel() != n:
+            raise ValueError('graph_dropout: node_drop must hold one flag per node')
+    dev = indptr.device
+    values = torch.empty(nnz, dtype=torch.float32, device=dev)
+    t_values = torch.empty(nnz, dtype=torch.float32, device=dev)
+    in_deg = torch.empty(n, dtype=torch.int32, device=dev)
+    out_deg = torch.empty(n, dtype=torch.int32, device=dev)
+    keep = torch.empty(nnz, dtype=torch.uint8, device=dev) if want_keep else None
+    a = nat.GraphDropoutArgs()
+    a.indptr, a.indices, a.rev, a.n_rows, a.nnz = ptr(indptr), ptr(indices), ptr(rev), n, nnz
+    a.keep_prob, a.node_drop, a.keep = keep_prob, ptr(node_drop), ptr(keep)
+    a.in_deg, a.out_deg, a.values, a.t_values = ptr(in_deg), ptr(out_deg), ptr(values), ptr(t_values)
+    a.long_row = GRAPH_DROPOUT_LONG_ROW if long_row is None else int(long_row)
+    if keep_prob < 1.0 and nnz:
+        pc = rng.reserve(nnz, 4, dev, generator)
+        a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
+    _launch('rsa_graph_dropout', ctypes.byref(a))
+    return (values, t_values, in_deg, out_deg) + ((keep,) if want_keep else ())

@@ -1261,6 +1261,43 @@ class LightGCN(BaseRetriever):
         return self.num_items if type(self.score_func) in (InnerProductScorer, CosineScorer, EuclideanScorer) else None
 
 
+class SGL(LightGCN):
+    """recstudio/model/graph/sgl.py:34-114, recstudio/model/graph/config/sgl.yaml (aug_type 'ED', n_layers 3, l2_reg_weight 1e-4,
+    ssl_ratio 0.1, ssl_reg 0.1, temperature 0.2, negative_count 1, batch_size 2048): LightGCN's step plus ``ssl_reg`` times the
+    InfoNCE contrast (users and items) between two randomly thinned views of the graph, drawn afresh every step
+    (``data_augmentation.SGLAugmentation`` on ``rsa_graph_dropout``).  ``last_views`` holds the last step's two views (their
+    masks and degrees; ``ssl_reg: 0`` draws none and is LightGCN's step).  Evaluation propagates over the full graph and is
+    LightGCN's.
+
+    Two deliberate deviations from the reference.  (1) sgl.py:101-103 ends a line with a stray comma, so ``training_step``
+    returns a tuple and ``Recommender.training_epoch`` (recommender.py:615-639) runs no backward at all; here the loss is the sum
+    those three lines plainly intend.  (2) Which edges fall is defined by the device ``torch.rand`` stream in CSR edge order, not
+    by ``dgl.DropEdge``'s stream, which cannot be reproduced without dgl; the distribution is the same."""
+
+    def __init__(self, config=None, **kwargs):
+        super().__init__(config, **kwargs)
+        for key, value in (('aug_type', 'ED'), ('ssl_ratio', 0.1), ('ssl_reg', 0.1), ('temperature', 0.2)):
+            self.config['model'].setdefault(key, value)
+        if 'batch_size' not in (config or {}).get('train', {}):
+            self.config['train']['batch_size'] = 2048
+
+    def _init_model(self, train_data, drop_unused_field=True):
+        from . import data_augmentation
+        super()._init_model(train_data, drop_unused_field)
+        self.augmentaion_model = data_augmentation.SGLAugmentation(self.config['model'], train_data)
+
+    @property
+    def last_views(self):
+        return self.augmentaion_model.last_views
+
+    def training_step(self, batch):
+        loss = super().training_step(batch)
+        if not self.config['model']['ssl_reg']:
+            return loss
+        cl_output = self.augmentaion_model(batch, self.user_emb, self.item_emb, self.adj_mat, self.LightGCNNet)
+        return loss + self.config['model']['ssl_reg'] * cl_output['cl_loss']
+
+
 class _EmbedFn(torch.autograd.Function):
     """item_encoder(ids) with the HIP gather forward and the HIP row scatter-add backward."""
 
