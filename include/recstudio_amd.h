@@ -811,7 +811,19 @@ int rsa_softmax_lookup(const rsa_softmax_sample_args* args, rsa_stream_t stream)
  * A null pointer among indptr / indices / x, neither y nor acc_out, acc_out without acc_in, a bad dim, a negative size, chunk < 1,
  * a plan_len or partials_bytes that is too small: RSA_ERR_ARG before the first HIP call.  Out-of-range entries of indptr /
  * indices / plan are clamped into the arrays, never followed.  Two launches (one when n_split == 0); nothing is allocated and
- * nothing synchronises. */
+ * nothing synchronises.
+ *
+ * THE PERTURBED FORM (SimGCL: recstudio/model/graph/simgcl.py:14-26, feat + sign(feat) * normalize(rand_like(feat)) * eps).  With
+ * noise_eps != 0 the row's sum AFTER row_scale, s, is replaced by s' before y and the accumulation see it:
+ *   u_c  = element noise_elem_base + r * dim + c of ONE torch.rand call over n_rows * dim outputs ("Philox state")
+ *   q    = max(sqrt(sum_c u_c * u_c), 1e-12)         the sum in fp32 in the fixed order rsa_spmm.hip states
+ *   s'_c = s_c + sgn(s_c) * (u_c / q) * noise_eps    sgn = +1 / -1 / 0 for s_c > 0 / < 0 / +-0 (torch.sign, not copysign)
+ * so a row without edges stays exactly 0.  A split row is perturbed once, on its total; its uniforms and q do not depend on
+ * the plan.  noise_u (nullable fp32 [n_rows, dim]) receives the raw uniforms.  The uniforms are bit-equal to torch.rand_like
+ * of an [n_rows, dim] tensor while n_rows * dim < 2^31 (torch splits larger calls; here the element index is 64-bit).
+ * A noise_eps that is not finite, noise_eps != 0 with noise_grid_threads 0 or no multiple of 256 or a noise_offset that is
+ * no multiple of 4, noise_u with noise_eps == 0, a noise_u that is not 16-byte aligned: RSA_ERR_ARG before the first HIP call.
+ * The noise fields were appended without a new RSA_ABI_VERSION: a shorter or zeroed block reads noise_eps = 0 = no noise. */
 typedef struct rsa_spmm_args {
   int64_t size;                /* sizeof(rsa_spmm_args) */
   const int64_t* indptr;       /* [n_rows + 1] */
@@ -836,6 +848,12 @@ typedef struct rsa_spmm_args {
   int64_t plan_len;
   float* partials;             /* nullable when n_parts == 0 */
   int64_t partials_bytes;
+  float noise_eps;             /* 0: no noise */
+  uint32_t noise_grid_threads; /* "Philox state" of the torch.rand(n_rows, dim) call the noise stands for */
+  uint64_t noise_seed;
+  uint64_t noise_offset;
+  uint64_t noise_elem_base;
+  float* noise_u;              /* nullable [n_rows, dim] out: the uniforms */
 } rsa_spmm_args;
 int rsa_spmm_csr(const rsa_spmm_args* args, rsa_stream_t stream);
 

@@ -251,7 +251,8 @@ class SpmmArgs(_Sized):
         ('n_cols', c_int64), ('nnz', c_int64), ('dim', c_int32), ('_pad', c_int32), ('x', c_void_p), ('row_scale', c_void_p),
         ('y', c_void_p), ('acc_in', c_void_p), ('acc_out', c_void_p), ('acc_scale', c_float), ('_pad2', c_float),
         ('chunk', c_int64), ('n_split', c_int64), ('n_parts', c_int64), ('plan', c_void_p), ('plan_len', c_int64),
-        ('partials', c_void_p), ('partials_bytes', c_int64),
+        ('partials', c_void_p), ('partials_bytes', c_int64), ('noise_eps', c_float), ('noise_grid_threads', c_uint32),
+        ('noise_seed', c_uint64), ('noise_offset', c_uint64), ('noise_elem_base', c_uint64), ('noise_u', c_void_p),
     ]
 
 

@@ -1,6 +1,7 @@
 // CSR sparse x dense product with a fused layer-mean epilogue: the propagation of the graph retrievers (gfx950).
 //
 // rsa_spmm_csr : LightGCNNet.forward, one layer      recstudio/model/module/graphmodule.py:168-198 (mess_norm 'both')
+//                SimGCLNet.forward, one layer        recstudio/model/graph/simgcl.py:14-26 (the same with noise: NOISE below)
 //
 //   y[r, :] = row_scale[r] * sum_e values[e] * x[indices[e], :],   acc_out[r, :] = acc_scale * (acc_in[r, :] + y[r, :])
 //
@@ -24,6 +25,27 @@
 //
 // Every index read from memory is clamped into its array before it is followed (indptr into [0, nnz], indices into [0, n_cols),
 // plan rows into [0, n_rows), plan pieces into [0, n_parts]).
+//
+// NOISE (SimGCLNet.forward, recstudio/model/graph/simgcl.py:14-26; include/recstudio_amd.h, "THE PERTURBED FORM").  With
+// noise_eps != 0 the launches are OTHER kernels (spmm_gather_noise_kernel<LG>, spmm_finish_noise_kernel) around the same
+// wave_gather_sum; the plain path runs the kernels it ran before, with the kernel arguments it had.  The row's sum after
+// row_scale sits in the float4 of the d / 4 writer lanes; before store_row writes it, finish_row_noise adds sgn(s_c) * (u_c / q) * eps (the moves: row_moves),
+// q = max(||u||_2, 1e-12):
+//   * DRAWS.  u_c is element r * d + c of one torch.rand call (torch_rand_element): a ten-round Philox evaluation per element,
+//     three of its four words unused.  The d draws of a row are spread over the wave's 64 lanes -- lane l draws the columns
+//     l, l + 64, l + 128, l + 192 below d, so d <= 64 costs ONE evaluation of wave time, d = 256 four -- and handed to the
+//     writer lanes by shuffles (writer w takes columns 4 w .. 4 w + 3).  The other form, every writer lane drawing its own four
+//     columns (4 evaluations of wave time at any d, on d / 4 lanes), was not built.  The same lanes write noise_u, coalesced.
+//     The moves of a row need no sum, so the gather launch computes them BEFORE its gather loop, where the Philox rounds run
+//     under the loads of the other waves instead of after the wave's last load: 4.31 ms against 4.39 ms per layer at d = 64,
+//     7.89 against 7.91 at d = 128, alternating processes on one device.
+//   * ORDER OF sum u^2.  Lane l adds the squares of its columns in ascending order onto +0 (each square rounded once, each
+//     addition rounded once; a lane without a column keeps +0); the 64 lane sums are added by the xor butterfly 1, 2, 4, 8,
+//     16, 32, which gives every lane the same bits.  sqrt and the division are the correctly rounded ones.
+//   * SPLIT ROWS get the perturbation once, on the row's total: spmm_finish_noise_kernel gives a split row a WAVE, not d / 4
+//     threads -- lane w < d / 4 adds column w of the row's partials in ascending piece order exactly as spmm_finish_kernel
+//     does, then the wave runs the same row_moves: the row norm is reduced across the wave's lanes, not recomputed per
+//     thread, and a row's uniforms, q and perturbation are by construction those it would get unsplit.
 #include "rsa_internal.hpp"
 
 namespace rsa {
@@ -110,12 +132,16 @@ __device__ __forceinline__ float4 wave_gather_sum(const SpmmParams& p, int64_t s
   return acc;
 }
 
-// row r, columns 4 col .. 4 col + 3: row_scale, y and the accumulation from the row's unscaled sum
-__device__ __forceinline__ void finish_row(const SpmmParams& p, int64_t r, int col, float4 sum) {
+__device__ __forceinline__ float4 scale_row(const SpmmParams& p, int64_t r, float4 sum) {
   if (p.row_scale) {
     const float sc = p.row_scale[r];
     sum = make_float4(sc * sum.x, sc * sum.y, sc * sum.z, sc * sum.w);
   }
+  return sum;
+}
+
+// row r, columns 4 col .. 4 col + 3: y and the accumulation from the row's scaled sum
+__device__ __forceinline__ void store_row(const SpmmParams& p, int64_t r, int col, float4 sum) {
   const int64_t at = r * p.dim + col * 4;
   if (p.y) *reinterpret_cast<float4*>(p.y + at) = sum;
   if (p.acc_out) {
@@ -123,6 +149,61 @@ __device__ __forceinline__ void finish_row(const SpmmParams& p, int64_t r, int c
     const float k = p.acc_scale;
     *reinterpret_cast<float4*>(p.acc_out + at) = make_float4(k * (a.x + sum.x), k * (a.y + sum.y), k * (a.z + sum.z), k * (a.w + sum.w));
   }
+}
+
+// row r, columns 4 col .. 4 col + 3: row_scale, y and the accumulation from the row's unscaled sum
+__device__ __forceinline__ void finish_row(const SpmmParams& p, int64_t r, int col, float4 sum) {
+  store_row(p, r, col, scale_row(p, r, sum));
+}
+
+struct SpmmNoise {
+  float eps;
+  PhiloxCall pc;
+  float* u;                             // nullable [n_rows, dim]
+};
+
+// The whole wave: the moves of row r, (u_c / q) * eps for the columns 4 lane .. 4 lane + 3 (file header, NOISE).  Needs no sum.
+__device__ __forceinline__ float4 row_moves(const SpmmParams& p, const SpmmNoise& nz, int64_t r, int lane) {
+  const uint64_t base = (uint64_t)r * (uint64_t)p.dim;
+  float u[4], sq = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane + 64 * k;
+    u[k] = 0.f;
+    if (k * 64 < p.dim) {                                         // (uniform over the wave)
+      if (c < p.dim) {
+        u[k] = torch_rand_element(nz.pc, base + (uint64_t)c);
+        if (nz.u) nz.u[base + c] = u[k];
+      }
+      sq += u[k] * u[k];
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) sq += __shfl_xor(sq, m, 64);
+  const float q = fmaxf(sqrtf(sq), 1e-12f);
+  float un[4];                                                    // the uniforms of columns 4 lane .. 4 lane + 3
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = (4 * lane + j) & (SPMM_MAX_DIM - 1);            // (lanes >= d4 fetch something and drop it)
+    un[j] = __shfl(u[0], c & 63, 64);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+      if (k * 64 < p.dim) {
+        const float v = __shfl(u[k], c & 63, 64);
+        if ((c >> 6) == k) un[j] = v;
+      }
+    }
+  }
+  return make_float4((un[0] / q) * nz.eps, (un[1] / q) * nz.eps, (un[2] / q) * nz.eps, (un[3] / q) * nz.eps);
+}
+
+// s + sgn(s) * t, sgn = torch.sign: a zero stays where it is
+__device__ __forceinline__ float moved(float s, float t) { return s + (s > 0.f ? t : (s < 0.f ? -t : 0.f)); }
+
+// finish_row on the perturbed row: row_scale, the move by `mv` (row_moves), y and the accumulation
+__device__ __forceinline__ void finish_row_noise(const SpmmParams& p, int64_t r, int col, float4 sum, const float4& mv) {
+  sum = scale_row(p, r, sum);
+  store_row(p, r, col, make_float4(moved(sum.x, mv.x), moved(sum.y, mv.y), moved(sum.z, mv.z), moved(sum.w, mv.w)));
 }
 
 // One wave per work item; items [0, n_parts) are the pieces of the split rows, items n_parts + r the rows.
@@ -172,6 +253,57 @@ __global__ __launch_bounds__(256) void spmm_finish_kernel(const SpmmParams p) {
   finish_row(p, clamp64(p.split_row[s], 0, p.n_rows - 1), col, acc);
 }
 
+// The perturbed form of the gather kernel: the same work items, the same sums, row_moves and finish_row_noise in place of finish_row.
+template <int LG>
+__global__ __launch_bounds__(256) void spmm_gather_noise_kernel(const SpmmParams p, const SpmmNoise nz) {
+  const int lane = lane_id();
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= p.n_parts + p.n_rows) return;
+  const bool writer = lane < (1 << LG) && lane < p.d4;
+  if (item < p.n_parts) {
+    const int64_t r = clamp64(p.part_row[item], 0, p.n_rows - 1);
+    const int64_t row_end = clamp64(p.indptr[r + 1], 0, p.nnz);
+    const int64_t s = clamp64(p.part_edge[item], 0, row_end);
+    const int64_t e = row_end - s < p.chunk ? row_end : s + p.chunk;
+    const float4 sum = wave_gather_sum<LG>(p, s, e, lane);
+    if (writer) *reinterpret_cast<float4*>(p.partials + item * p.dim + lane * 4) = sum;
+    return;
+  }
+  const int64_t r = item - p.n_parts;
+  const int64_t s = clamp64(p.indptr[r], 0, p.nnz);
+  const int64_t e = clamp64(p.indptr[r + 1], s, p.nnz);
+  if (e - s > p.chunk) return;
+  const float4 mv = row_moves(p, nz, r, lane);                    // (before the gather: measured against after it, file header)
+  const float4 sum = wave_gather_sum<LG>(p, s, e, lane);
+  if (writer) finish_row_noise(p, r, lane, sum, mv);
+}
+
+// One WAVE per split row: lane w < d4 adds column w of the row's partials in ascending piece order (the additions of
+// spmm_finish_kernel), then the wave perturbs the total.
+__global__ __launch_bounds__(256) void spmm_finish_noise_kernel(const SpmmParams p, const SpmmNoise nz) {
+  const int lane = lane_id();
+  const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= p.n_split) return;
+  const bool writer = lane < p.d4;
+  const int64_t p0 = clamp64(p.split_part[s], 0, p.n_parts);
+  const int64_t p1 = clamp64(p.split_part[s + 1], p0, p.n_parts);
+  const float* part = p.partials + (writer ? lane : 0) * 4;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int64_t q = p0; q < p1; q += SPMM_UNROLL) {
+    float4 v[SPMM_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SPMM_UNROLL; ++u) v[u] = *reinterpret_cast<const float4*>(part + (q + u < p1 ? q + u : p1 - 1) * p.dim);
+#pragma unroll
+    for (int u = 0; u < SPMM_UNROLL; ++u) {
+      if (q + u >= p1) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      add_scaled(acc, 1.f, v[u]);
+    }
+  }
+  const int64_t r = clamp64(p.split_row[s], 0, p.n_rows - 1);
+  const float4 mv = row_moves(p, nz, r, lane);
+  if (writer) finish_row_noise(p, r, lane, acc, mv);
+}
+
 }  // namespace rsa
 
 using namespace rsa;
@@ -197,6 +329,13 @@ extern "C" int rsa_spmm_csr(const rsa_spmm_args* args, rsa_stream_t stream) {
   RSA_CHECK_ARG(a.n_parts == 0 || a.partials != nullptr, "%s: partials is null", fn);
   RSA_CHECK_ARG(a.partials_bytes >= a.n_parts * a.dim * 4, "%s: the partials workspace is too small: %lld bytes, %lld pieces need %lld",
                 fn, (long long)a.partials_bytes, (long long)a.n_parts, (long long)(a.n_parts * a.dim * 4));
+  RSA_CHECK_ARG(std::isfinite(a.noise_eps), "%s: noise_eps must be finite", fn);
+  const bool noise = a.noise_eps != 0.f;
+  RSA_CHECK_ARG(!noise || (a.noise_grid_threads > 0 && a.noise_grid_threads % 256 == 0 && (a.noise_offset & 3) == 0),
+                "%s: bad philox state for the noise (grid_threads %u must be a positive multiple of 256, offset a multiple of 4)", fn,
+                a.noise_grid_threads);
+  RSA_CHECK_ARG(noise || a.noise_u == nullptr, "%s: noise_u without noise_eps", fn);
+  RSA_CHECK_ARG(((uintptr_t)a.noise_u & 15) == 0, "%s: noise_u must be 16-byte aligned", fn);
   RSA_CHECK_ARG(a.y != nullptr || a.acc_out != nullptr, "%s: y and acc_out are both null", fn);
   RSA_CHECK_ARG(a.acc_out == nullptr || a.acc_in != nullptr, "%s: acc_out without acc_in", fn);
   if (a.n_rows == 0) return RSA_OK;
@@ -221,6 +360,18 @@ extern "C" int rsa_spmm_csr(const rsa_spmm_args* args, rsa_stream_t stream) {
   int lg = 0;                                                    // lanes per neighbour row: the power of two >= dim / 4
   while ((1 << lg) < p.d4) ++lg;
   const unsigned blocks = (unsigned)((p.n_parts + p.n_rows + 3) / 4);
+  if (noise) {
+    const SpmmNoise nz{a.noise_eps, PhiloxCall{a.noise_seed, a.noise_offset >> 2, a.noise_grid_threads, a.noise_elem_base}, a.noise_u};
+    dispatch_int<0, 1, 2, 3, 4, 5, 6>(lg, [&](auto LG) {
+      hipLaunchKernelGGL((spmm_gather_noise_kernel<LG()>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, nz);
+    });
+    RSA_CHECK_LAUNCH(fn);
+    if (p.n_split) {
+      hipLaunchKernelGGL(spmm_finish_noise_kernel, dim3((unsigned)((p.n_split + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, nz);
+      RSA_CHECK_LAUNCH(fn);
+    }
+    return RSA_OK;
+  }
   dispatch_int<0, 1, 2, 3, 4, 5, 6>(lg, [&](auto LG) {
     hipLaunchKernelGGL((spmm_gather_kernel<LG()>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p);
   });

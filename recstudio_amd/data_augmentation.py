@@ -1,4 +1,5 @@
-"""Graph augmentation -- host-side mirror of the graph half of ``recstudio.model.module.data_augmentation`` (:229-450) for SGL.
+"""Graph augmentation -- host-side mirror of the graph half of ``recstudio.model.module.data_augmentation`` (:229-450 for SGL,
+:524-570 for SimGCL, whose views are not thinned graphs but noise in the propagation: ``graphmodule.SimGCLNet``).
 
 The reference copies its ``dgl`` graph and thins the copy once per view per step (``copy.deepcopy`` + ``dgl.DropEdge`` /
 ``remove_edges``); here a view is ``NormAdj.augmented``: one ``rsa_graph_dropout`` call that draws the mask, counts the
@@ -14,7 +15,7 @@ import torch.nn.functional as F
 
 from .scorer import full_lse
 
-__all__ = ['EdgeDropout', 'NodeDropout', 'InfoNCELoss', 'SGLAugmentation']
+__all__ = ['EdgeDropout', 'NodeDropout', 'InfoNCELoss', 'SGLAugmentation', 'SimGCLAugmentation']
 
 
 class EdgeDropout(torch.nn.Module):
@@ -123,4 +124,41 @@ class SGLAugmentation(torch.nn.Module):
         # the batch rows through the gather / sorted-scatter node, not index_add
         user_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(user_all_vec1, uid), _EmbedFn.apply(user_all_vec2, uid), all_reps=user_all_vec2)
         item_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(item_all_vec1, iid), _EmbedFn.apply(item_all_vec2, iid), all_reps=item_all_vec2)
+        return {'cl_loss': user_cl_loss + item_cl_loss}
+
+
+class SimGCLAugmentation(torch.nn.Module):
+    """data_augmentation.py:524-570: two PERTURBED propagations of the base tables over the full graph
+    (``graphmodule.SimGCLNet.propagate(perturbed=True)``: every layer output moved by ``eps`` along a random direction of its own
+    sign pattern), and InfoNCE (cosine, all nodes as negatives) between the two views of the batch's unique users and of its
+    unique items.  The device stream takes L ``rand_like`` calls for view 1, then L for view 2.  Only ``cl_neg_type: 'all'``
+    exists here; the in-batch forms of ``InfoNCELoss`` are not implemented and are refused at construction.  ``torch.unique`` is
+    the reference's semantics (its host sync is accepted)."""
+
+    def __init__(self, config, train_data):
+        super().__init__()
+        self.config = config
+        self.fiid, self.fuid = train_data.fiid, train_data.fuid
+        self.num_users, self.num_items = train_data.num_users, train_data.num_items
+        if self.config['cl_neg_type'] != 'all':
+            raise NotImplementedError(f"SimGCLAugmentation: cl_neg_type {self.config['cl_neg_type']!r} contrasts inside the batch; only "
+                                      "'all' (every node as a negative) is implemented")
+        self.InfoNCELoss_fn = InfoNCELoss(temperature=self.config['temperature'], sim_method='cosine', neg_type='all')
+
+    def get_gnn_embeddings(self, user_emb, item_emb, adj_mat, gnn_net):
+        adj_mat.to(user_emb.weight.device)
+        embeddings = torch.cat([user_emb.weight, item_emb.weight], dim=0)
+        all_embeddings = gnn_net.propagate(adj_mat, embeddings, perturbed=True)
+        return all_embeddings[:self.num_users], all_embeddings[self.num_users:]
+
+    def forward(self, batch, user_emb, item_emb, adj_mat, gnn_net):
+        from .retriever import _EmbedFn
+        device = user_emb.weight.device
+        u_idx = torch.unique(batch[self.fuid]).to(device)
+        i_idx = torch.unique(batch[self.fiid]).to(device)
+        user_all_vec1, item_all_vec1 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
+        user_all_vec2, item_all_vec2 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
+        # the batch rows through the gather / sorted-scatter node, not index_add; all_reps is the whole table (row 0 is skipped)
+        user_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(user_all_vec1, u_idx), _EmbedFn.apply(user_all_vec2, u_idx), all_reps=user_all_vec2)
+        item_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(item_all_vec1, i_idx), _EmbedFn.apply(item_all_vec2, i_idx), all_reps=item_all_vec2)
         return {'cl_loss': user_cl_loss + item_cl_loss}

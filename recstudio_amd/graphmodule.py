@@ -4,13 +4,15 @@
 ``NormAdj`` is what the reference holds as a ``dgl.graph`` plus the two degree-norm vectors of ``LightGCNNet.forward``
 (graphmodule.py:176-188, mess_norm 'both'): the normalised adjacency ``D^-1/2 A D^-1/2`` in CSR with the norms folded into the edge
 values.  ``LightGCNNet`` is graphmodule.py:190-198 with ``LightGCNCombiner`` (:89-94, the identity on the neighbour message) and
-the layer mean of lightgcn.py:56-60 in one autograd node.  ``GraphUserEncoder`` / ``GraphItemEncoder``: graphmodule.py:97-111.
+the layer mean of lightgcn.py:56-60 in one autograd node.  ``SimGCLNet`` is recstudio/model/graph/simgcl.py:8-26: the same
+propagation with every layer output perturbed inside the kernel and a layer mean that skips the input.  ``GraphUserEncoder`` /
+``GraphItemEncoder``: graphmodule.py:97-111.
 """
 import torch
 
-from . import ops
+from . import ops, rng
 
-__all__ = ['NormAdj', 'AugmentedAdj', 'LightGCNNet', 'GraphUserEncoder', 'GraphItemEncoder']
+__all__ = ['NormAdj', 'AugmentedAdj', 'LightGCNNet', 'SimGCLNet', 'GraphUserEncoder', 'GraphItemEncoder']
 
 
 def _csr_by(key, other, weights, n):
@@ -233,6 +235,99 @@ class LightGCNNet(torch.nn.Module):
         if each and any(a is not adj[0] for a in adj):
             return _PropagateEachFn.apply(embeddings, tuple(adj))
         return _PropagateFn.apply(embeddings, adj[0] if each else adj, self.n_layers)
+
+    forward = propagate
+
+
+def _skip_input_mean(csr, e0, n_layers, eps=0.0, calls=None, noise_out=None):
+    """(E'_1 + ... + E'_L) / L with E_k = A E'_{k-1}, E'_0 = E_0 and E'_k = E_k perturbed by call ``calls[k - 1]`` (or E_k without
+    ``calls``): L launches of ``ops.spmm_csr`` and no memset -- layer 1 writes its output only, layer 2 starts the running sum from
+    layer 1's output (``acc`` = y_1 is read, ``acc_out`` written), the later ones add in place, the last one scales by 1 / L and
+    writes no layer output.  ``noise_out``: a list that receives the L tables of uniforms (tests)."""
+    indptr, indices, values, plan = csr
+    L = int(n_layers)
+    x, spare, acc = e0.detach().contiguous(), [None, None], None
+    for k in range(L):
+        last = k == L - 1
+        noise = {}
+        if calls is not None:
+            noise = {'noise': calls[k], 'noise_eps': eps}
+            if noise_out is not None:
+                noise_out.append(torch.empty_like(x))
+                noise['noise_out'] = noise_out[-1]
+        y = None
+        if not last or k == 0:
+            y = spare[k % 2] = torch.empty_like(x) if spare[k % 2] is None else spare[k % 2]
+        if k == 0:
+            ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, **noise)
+        elif k == 1:
+            acc = torch.empty_like(x)
+            ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=x, acc_out=acc, acc_scale=1.0 / L if last else 1.0, **noise)
+        else:
+            ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=acc, acc_scale=1.0 / L if last else 1.0, **noise)
+        x = y
+    return x if L == 1 else acc
+
+
+def _skip_input_mean_grad(csr_t, g, n_layers):
+    """(A^T g + ... + (A^T)^L g) / L for the transposed matrix ``csr_t``: h <- g + A^T h, L - 1 times from h = g (one launch each,
+    ``acc`` = g read, ``acc_out`` = the new h written, the last one scaling by 1 / L), then one launch A^T h."""
+    indptr, indices, values, plan = csr_t
+    L = int(n_layers)
+    g = g.detach().contiguous()
+    h, spare = g, [None, None]
+    for j in range(L - 1):
+        out = spare[j % 2] = torch.empty_like(g) if spare[j % 2] is None else spare[j % 2]
+        ops.spmm_csr(indptr, indices, values, h, plan=plan, acc=g, acc_out=out, acc_scale=1.0 / L if j == L - 2 else 1.0)
+        h = out
+    return ops.spmm_csr(indptr, indices, values, h, plan=plan)
+
+
+class _SimGCLPropagateFn(torch.autograd.Function):
+    """sign has derivative zero and the uniforms do not depend on the input, so a perturbed layer is E'_k = A E'_{k-1} + const:
+    perturbed or not, dE_0 = 1 / L * sum_{k = 1 .. L} (A^T)^k g, and nothing but the graph is kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, e0, adj, n_layers, eps, calls, noise_out):
+        ctx.adj, ctx.n_layers = adj, n_layers
+        return _skip_input_mean(adj.csr(), e0, n_layers, eps, calls, noise_out)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _skip_input_mean_grad(ctx.adj.csr(transposed=True), g, ctx.n_layers), None, None, None, None, None
+
+
+class SimGCLNet(torch.nn.Module):
+    """recstudio/model/graph/simgcl.py:8-26 with the layer mean of :77-81 in one autograd node: E_k = A E'_{k-1} and, when
+    ``perturbed``, E'_k = E_k + sign(E_k) * normalize(rand_like(E_k), dim=-1) * eps; the result is mean(E'_1 .. E'_L) -- the
+    input E_0 is NOT part of the mean, unlike LightGCN's.  The noise is added in the epilogue of the propagation kernel
+    (``ops.spmm_csr(noise=...)``) from the device generator's stream: layer k draws what the k-th of L consecutive
+    ``torch.rand_like(E)`` calls would (bit-equal while ``n_nodes * d < 2**31``), and the generator is advanced by those L calls."""
+
+    def __init__(self, n_layers, eps):
+        super().__init__()
+        if int(n_layers) < 1:
+            raise ValueError('SimGCLNet: n_layers must be at least 1 (the mean over the layer outputs skips the input; '
+                             'without a layer it is the mean of nothing)')
+        self.n_layers, self.eps = int(n_layers), float(eps)
+
+    def propagate(self, adj, embeddings, perturbed=False, generator=None, noise_out=None):
+        """``embeddings`` fp32 [n_nodes, d] (d a multiple of 4, at most 256) -> mean(E'_1 .. E'_L) over ``adj`` (a ``NormAdj`` or
+        an ``AugmentedAdj``).  ``noise_out``: a list; the L tables of uniforms are appended to it (tests)."""
+        if embeddings.shape[0] != adj.n_nodes:
+            raise ValueError(f'SimGCLNet: {embeddings.shape[0]} embedding rows for a graph of {adj.n_nodes} nodes')
+        adj.to(embeddings.device)
+        calls = None
+        if perturbed:
+            if not embeddings.is_cuda:
+                raise RuntimeError('SimGCLNet: recstudio_amd runs on the GPU only; there is no CPU fallback')
+            numel = embeddings.numel()
+            first = rng.reserve(numel, 4, embeddings.device, generator, repeat=self.n_layers)
+            step = rng.counter_offset(numel, first.grid_threads, 4)
+            if self.eps != 0.0:          # (eps 0 still consumes the stream of the L rand_like calls, as the reference does)
+                calls = [rng.PhiloxCall(first.seed, first.offset + k * step, first.grid_threads, first.elem_base)
+                         for k in range(self.n_layers)]
+        return _SimGCLPropagateFn.apply(embeddings, adj, self.n_layers, self.eps, calls, noise_out)
 
     forward = propagate
 

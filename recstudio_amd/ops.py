@@ -6,6 +6,7 @@ tensors must live on a ROCm device -- there is no CPU path.
 """
 import ctypes
 import functools
+import math
 
 import torch
 
@@ -1417,7 +1418,8 @@ def spmm_plan(indptr, chunk=SPMM_CHUNK):
 
 
 @_on_device
-def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=None, acc_scale=1.0, acc_out=None):
+def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=None, acc_scale=1.0, acc_out=None,
+             noise=None, noise_eps=0.0, noise_out=None):
     """rsa_spmm_csr: ``y[r] = row_scale[r] * sum_e values[e] * x[indices[e]]`` over the edges ``[indptr[r], indptr[r + 1])`` of
     row r -- ``indptr`` int64 [R + 1], ``indices`` int32 [nnz], ``values`` fp32 [nnz] or None (all ones), ``x`` fp32 [C, d] with d
     a multiple of 4 and at most 256, ``row_scale`` fp32 [R] or None, ``plan`` = ``spmm_plan(indptr)``.  No atomics; bit-equal
@@ -1426,7 +1428,14 @@ def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=No
     last layer's ``acc_scale = 1 / (L + 1)`` makes it the mean).  With ``acc`` and without ``y`` the product itself is not written.
     ``acc_out`` fp32 [R, d] (with ``acc``): the accumulation is written THERE and ``acc`` is only read -- one step of a Horner
     recurrence ``h' = acc_scale * (g + A h)`` with g = ``acc``, h = ``x``, h' = ``acc_out``.
-    Without ``acc``, ``y`` None allocates the result.  Returns ``y`` when it was written, else ``acc_out`` / ``acc``."""
+    Without ``acc``, ``y`` None allocates the result.  Returns ``y`` when it was written, else ``acc_out`` / ``acc``.
+    ``noise`` (a ``rng.PhiloxCall`` reserved for ONE ``torch.rand`` call over ``R * d`` outputs) with ``noise_eps != 0``: SimGCL's
+    perturbed layer.  Row r's sum after ``row_scale``, s, becomes ``s + sign(s) * u / max(||u||_2, 1e-12) * noise_eps`` before
+    ``y`` and the accumulation see it, ``u`` = elements ``[r d, (r + 1) d)`` of that call (``torch.sign``: a zero stays zero, so
+    rows without edges stay 0).  ``noise_out`` fp32 [R, d]: receives the uniforms.  They are bit-equal to ``torch.rand_like`` of
+    an [R, d] tensor in the generator state ``noise`` was reserved in while ``R * d < 2**31``; torch splits larger calls in two,
+    here a larger table still draws the elements of one call indexed with 64 bits.  ``noise_eps == 0`` is the plain product and
+    takes neither ``noise`` nor ``noise_out``."""
     indptr = _need(indptr, torch.int64, 'indptr')
     indices = _need(indices, torch.int32, 'indices')
     values = _need_opt(values, torch.float32, 'values')
@@ -1456,6 +1465,20 @@ def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=No
             # (acc may be x when the sum goes to acc_out: it is then only read)
             if t.data_ptr() == x.data_ptr() and t.numel() and not (name == 'acc' and acc_out is not None):
                 raise ValueError(f'spmm_csr: {name} must not alias x')
+    noise_eps = float(noise_eps)
+    if not math.isfinite(noise_eps):
+        raise ValueError(f'spmm_csr: noise_eps must be finite, got {noise_eps}')
+    if noise_eps != 0.0:
+        if not isinstance(noise, rng.PhiloxCall):
+            raise TypeError('spmm_csr: noise_eps needs noise, a rng.PhiloxCall (rng.reserve(R * d, 4, device))')
+        if noise.grid_threads <= 0 or noise.grid_threads % rng.BLOCK or noise.offset % 4:
+            raise ValueError(f'spmm_csr: bad philox state for the noise: {noise}')
+    elif noise is not None or noise_out is not None:
+        raise ValueError('spmm_csr: noise / noise_out without noise_eps')
+    if noise_out is not None:
+        _need_view(noise_out, torch.float32, 'noise_out')
+        if tuple(noise_out.shape) != (R, d) or not noise_out.is_contiguous() or noise_out.data_ptr() % 16:
+            raise ValueError(f'spmm_csr: noise_out must be a contiguous, 16-byte aligned [{R}, {d}] tensor')
     if y is None and acc is None:
         y = torch.empty(R, d, dtype=torch.float32, device=dev)
     partials = plan.partials(d, dev) if plan.n_parts else None
@@ -1468,6 +1491,9 @@ def spmm_csr(indptr, indices, values, x, *, plan, row_scale=None, y=None, acc=No
     if plan.n_split:
         a.plan, a.plan_len = ptr(plan.table), plan.table.numel()
         a.partials, a.partials_bytes = ptr(partials), partials.numel() * 4
+    if noise_eps != 0.0:
+        a.noise_eps, a.noise_u = noise_eps, ptr(noise_out)
+        a.noise_seed, a.noise_offset, a.noise_grid_threads, a.noise_elem_base = noise.seed, noise.offset, noise.grid_threads, noise.elem_base
     _launch('rsa_spmm_csr', ctypes.byref(a))
     return y if y is not None else (acc if acc_out is None else acc_out)
 

@@ -31,7 +31,7 @@ from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, Pairwise
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
 
-__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'LightGCN', 'default_config',
+__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'LightGCN', 'SGL', 'SimGCL', 'default_config',
            'seed_everything']
 
 
@@ -1296,6 +1296,42 @@ class SGL(LightGCN):
             return loss
         cl_output = self.augmentaion_model(batch, self.user_emb, self.item_emb, self.adj_mat, self.LightGCNNet)
         return loss + self.config['model']['ssl_reg'] * cl_output['cl_loss']
+
+
+class SimGCL(LightGCN):
+    """recstudio/model/graph/simgcl.py:35-110, recstudio/model/graph/config/simgcl.yaml (eps 0.1, n_layers 3, l2_reg_weight 1e-4,
+    cl_neg_type 'all', temperature 0.2, batch_size 2048, learning_rate 0.001, negative_count 1): LightGCN's step -- BPR on
+    uniform negatives plus the l2 regulariser of the base rows -- over ``graphmodule.SimGCLNet``, whose layer mean SKIPS the
+    input (mean(E_1 .. E_L), which ``evaluate`` / ``topk`` use as well), plus the InfoNCE contrast between two noise-perturbed
+    propagations of the same graph (``data_augmentation.SimGCLAugmentation``; the noise is added inside ``rsa_spmm_csr``).  The
+    device stream of a step: the negatives first, then the L ``rand_like`` calls of view 1, then those of view 2.
+
+    ``model.cl_weight`` (0.5 in simgcl.yaml) is accepted and NOT applied: nothing in the reference reads it, simgcl.py:98 adds
+    ``cl_loss`` with weight 1, and so does this class."""
+
+    def __init__(self, config=None, **kwargs):
+        super().__init__(config, **kwargs)
+        for key, value in (('eps', 0.1), ('cl_weight', 0.5), ('cl_neg_type', 'all'), ('temperature', 0.2)):
+            self.config['model'].setdefault(key, value)
+        given = (config or {}).get('train', {})
+        for key, value in (('batch_size', 2048), ('learning_rate', 0.001)):
+            if key not in given:
+                self.config['train'][key] = value
+
+    def _init_model(self, train_data, drop_unused_field=True):
+        from . import data_augmentation, graphmodule
+        super()._init_model(train_data, drop_unused_field)
+        del self.LightGCNNet
+        self.SimGCLNet = graphmodule.SimGCLNet(self.config['model']['n_layers'], self.config['model']['eps'])
+        self.augmentation_model = data_augmentation.SimGCLAugmentation(self.config['model'], train_data)
+
+    def _propagate(self, embeddings):
+        return self.SimGCLNet.propagate(self.adj_mat, embeddings)
+
+    def training_step(self, batch):
+        loss = super().training_step(batch)                    # the negatives are drawn here, before the noise
+        cl_output = self.augmentation_model(batch, self.user_emb, self.item_emb, self.adj_mat, self.SimGCLNet)
+        return loss + cl_output['cl_loss']
 
 
 class _EmbedFn(torch.autograd.Function):
