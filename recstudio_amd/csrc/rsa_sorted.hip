@@ -12,13 +12,14 @@
 // leading / trailing open segment in the workspace and a second kernel adds a run's partials in chunk order.
 // `target` may be a zeroed dense gradient (== the reference's weight.grad) or the weight table itself with
 // scale = -lr (plain SGD applied in place).  With optimizer state the same passes apply a rule to every touched row instead of
-// adding: lazy Adam (exp_avg / exp_avg_sq: torch.optim.SparseAdam, two state rows per row) in the kernels above the line
-// "the Adagrad form", torch.optim.Adagrad (state_sum: one state row per row, `learner: adagrad` of the reference,
-// recommender.py:466-467) in kernels of their own below it.
+// adding: lazy Adam (exp_avg / exp_avg_sq: torch.optim.SparseAdam, two state rows per row: AdamRule) or torch.optim.Adagrad
+// (state_sum: one state row per row, `learner: adagrad` of the reference, recommender.py:466-467: AdagradRule).  The passes
+// are written once (sorted_apply_frame, sorted_finish_frame); the kernels are those frames under a rule.
 #include "rsa_common.hpp"
 #include "rsa_radix.hpp"
 #include "rsa_internal.hpp"
 #include <cstring>
+#include <type_traits>
 
 // rows requested ahead by the apply pass.  4: 78 VGPRs at d = 128 = 6 waves/SIMD; 8: 110 = 4 waves.  In-process A/B
 // (tools/exp_sorted_ab.py, us per launch, 4 vs 8): headline shape all elements 836.2 / 837.7, solo rows skipped 343.7 / 350.4;
@@ -36,8 +37,6 @@
 
 namespace rsa {
 
-// target[cur] (+ lazy Adam state) <- one read-modify-write of the row with the run's sum `acc`; trow / mrow_v / vrow_v
-// are the row's current values (requested earlier, at the head of the run).
 template <bool NT>
 __device__ __forceinline__ float ld_row(const float* p) {
   if constexpr (NT) return __builtin_nontemporal_load(p);
@@ -49,44 +48,88 @@ __device__ __forceinline__ void st_row(float* p, float v) {
   else *p = v;
 }
 
-template <int NDW, bool NT = false>
-__device__ __forceinline__ void apply_run(float* __restrict__ target, const AdamArgs& adam, int32_t cur, float scale, int lane,
-                                          const float (&acc)[NDW], const float (&trow)[NDW], const float (&mrow_v)[NDW],
-                                          const float (&vrow_v)[NDW]) {
-  constexpr int D = 64 * NDW;
-  float* row = target + (size_t)cur * D;
-  if (adam.exp_avg == nullptr) {
+// ---- the rules: what a touched row becomes, given the run's sum.  The two passes below (sorted_apply_frame,
+// sorted_finish_frame) are written once over a rule: NS state rows travel with a target row, state(s) is the table of the
+// s-th, and apply_run read-modify-writes target[cur] and its state rows ONCE from `acc`; trow / srow are the rows' current
+// values (requested earlier, at the head of the run).
+
+// Plain accumulate (exp_avg == nullptr, decided at run time: SGD and Adam share their instantiations) or lazy Adam.
+struct AdamRule {
+  static constexpr int NS = 2;
+  static constexpr const char* who = "rsa_rows_update_sorted(apply)";
+  AdamArgs a;
+  __device__ __forceinline__ bool has_state() const { return a.exp_avg != nullptr; }
+  __device__ __forceinline__ float* state(int s) const { return s == 0 ? a.exp_avg : a.exp_avg_sq; }
+  template <int NDW, bool NT>
+  __device__ __forceinline__ void apply_run(float* __restrict__ target, int32_t cur, float scale, int lane, const float (&acc)[NDW],
+                                            const float (&trow)[NDW], const float (&srow)[NS][NDW]) const {
+    constexpr int D = 64 * NDW;
+    float* row = target + (size_t)cur * D;
+    if (a.exp_avg == nullptr) {
 #pragma unroll
-    for (int k = 0; k < NDW; ++k) st_row<NT>(row + k * 64 + lane, trow[k] + scale * acc[k]);
-    return;
-  }
-  // lazy Adam on the touched row (torch.optim.SparseAdam's update, torch/optim/_functional.py sparse_adam):
-  // m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); w -= step_size * m / (sqrt(v) + eps)
-  float* mrow = adam.exp_avg + (size_t)cur * D;
-  float* vrow = adam.exp_avg_sq + (size_t)cur * D;
+      for (int k = 0; k < NDW; ++k) st_row<NT>(row + k * 64 + lane, trow[k] + scale * acc[k]);
+      return;
+    }
+    // lazy Adam on the touched row (torch.optim.SparseAdam's update, torch/optim/_functional.py sparse_adam):
+    // m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); w -= step_size * m / (sqrt(v) + eps)
+    float* mrow = a.exp_avg + (size_t)cur * D;
+    float* vrow = a.exp_avg_sq + (size_t)cur * D;
 #pragma unroll
-  for (int k = 0; k < NDW; ++k) {
-    const int c = k * 64 + lane;
-    const float g = scale * acc[k];
-    const float m0 = mrow_v[k], v0 = vrow_v[k];
-    const float m1 = m0 + (g - m0) * adam.one_minus_beta1;
-    const float v1 = v0 + (g * g - v0) * adam.one_minus_beta2;
-    st_row<NT>(mrow + c, m1);
-    st_row<NT>(vrow + c, v1);
-    st_row<NT>(row + c, trow[k] - adam.step_size * (m1 / (sqrtf(v1) + adam.eps)));
+    for (int k = 0; k < NDW; ++k) {
+      const int c = k * 64 + lane;
+      const float g = scale * acc[k];
+      const float m0 = srow[0][k], v0 = srow[1][k];
+      const float m1 = m0 + (g - m0) * a.one_minus_beta1;
+      const float v1 = v0 + (g * g - v0) * a.one_minus_beta2;
+      st_row<NT>(mrow + c, m1);
+      st_row<NT>(vrow + c, v1);
+      st_row<NT>(row + c, trow[k] - a.step_size * (m1 / (sqrtf(v1) + a.eps)));
+    }
   }
-}
+};
+
+// rsa_rows_update_args.rule == RSA_ROWS_ADAGRAD: torch.optim.Adagrad on the touched rows
+//     g = upstream * run sum;   s' = s + g g;   w' = w - clr (g / (sqrt(s') + eps))
+// with ONE state table.  A row without a kept element has g = 0, for which torch's dense pass changes neither s nor w
+// (0 / (sqrt(s) + eps) = 0): leaving such rows alone IS the dense rule, and the sparse branch of torch.optim.Adagrad squares
+// the coalesced row gradient -- the run sum these passes hold in registers.
+// Every rounding is spelled out so that tests/adagrad_referee.py can follow it operation for operation:
+//     g   = fl(scale * acc)
+//     s'  = fl(g * g + s)                 FUSED: one rounding
+//     den = fl(fl(sqrt(s')) + eps)        sqrtf and the division are the correctly rounded ones (hipcc's default)
+//     q   = fl(g / den)
+//     w'  = fl(-clr * q + w)              FUSED: one rounding
+// Only a step's elements are ever stepped (DecStep): exchange segments are accumulated, never stepped.
+struct AdagradRule {
+  static constexpr int NS = 1;
+  static constexpr const char* who = "rsa_rows_update_sorted(adagrad apply)";
+  AdagradArgs a;
+  __device__ __forceinline__ bool has_state() const { return true; }
+  __device__ __forceinline__ float* state(int) const { return a.state_sum; }
+  template <int NDW, bool NT>
+  __device__ __forceinline__ void apply_run(float* __restrict__ target, int32_t cur, float scale, int lane, const float (&acc)[NDW],
+                                            const float (&trow)[NDW], const float (&srow)[NS][NDW]) const {
+    constexpr int D = 64 * NDW;
+    float* row = target + (size_t)cur * D;
+    float* srow_p = a.state_sum + (size_t)cur * D;
+#pragma unroll
+    for (int k = 0; k < NDW; ++k) {
+      const int c = k * 64 + lane;
+      const float g = __fmul_rn(scale, acc[k]);
+      const float s1 = __fmaf_rn(g, g, srow[0][k]);
+      const float den = __fadd_rn(sqrtf(s1), a.eps);
+      const float q = g / den;
+      st_row<NT>(srow_p + c, s1);
+      st_row<NT>(row + c, __fmaf_rn(-a.clr, q, trow[k]));
+    }
+  }
+};
 
 // Per-chunk record of the open segments: meta[4 c + 0] = key of the LEADING segment if it continues the previous chunk's
 // run (else -1), [1] = 1 if that segment is the whole chunk, [2] = key of the TRAILING segment if its run goes on into
 // the next chunk and started in this one (else -1).
 enum { META_LEAD_KEY = 0, META_LEAD_FULL = 1, META_TRAIL_KEY = 2, META_STRIDE = 4 };
 
-// One wave per chunk of 64 sorted elements.  Runs that begin and end inside the chunk are applied here; the open
-// leading / trailing segments leave their partial sums in lead_part / trail_part [chunk, D] for sorted_finish_kernel.
-#ifndef RSA_SORTED_MIN_WAVES
-#define RSA_SORTED_MIN_WAVES 1
-#endif
 // What element e of the sorted pairs stands for: its query row and its coefficient d loss/d score.
 struct DecStep {             // a step's [M, (1 +) n] element order: e = m * w + c
   const int64_t* query_index;
@@ -111,15 +154,16 @@ struct DecSegments {         // received exchange segments: e = slot, key = (que
   }
 };
 
-template <int NDW, class DEC, bool NT>   // dwords per lane per row: D = 64 * NDW; NT: streaming accesses to the target (and state) rows
-__global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel(const uint64_t* __restrict__ pairs,
-                                                           int64_t total, const float* __restrict__ query, const DEC dec,
-                                                           const float* __restrict__ upstream, int32_t pad_row,
-                                                           int32_t drop_key, float* __restrict__ target, AdamArgs adam,
-                                                           float* __restrict__ lead_part, float* __restrict__ trail_part,
-                                                           int32_t* __restrict__ meta, int32_t key_base, int32_t elem_base,
-                                                           int32_t chunk_elems) {
-  constexpr int D = 64 * NDW;
+// The apply pass, one wave per chunk: NDW dwords per lane per row (D = 64 * NDW); NT: streaming accesses to the target (and
+// state) rows.
+template <int NDW, bool NT, class RULE, class DEC>
+__device__ __forceinline__ void sorted_apply_frame(const uint64_t* __restrict__ pairs, int64_t total, const float* __restrict__ query,
+                                                   const DEC& dec, const float* __restrict__ upstream, int32_t pad_row,
+                                                   int32_t drop_key, float* __restrict__ target, const RULE& rule,
+                                                   float* __restrict__ lead_part, float* __restrict__ trail_part,
+                                                   int32_t* __restrict__ meta, int32_t key_base, int32_t elem_base,
+                                                   int32_t chunk_elems) {
+  constexpr int D = 64 * NDW, NS = RULE::NS;
   const int lane = lane_id();
   const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   // chunk_elems = 64, or 16 for a small pass (sorted_chunk_elems): a wave walks its elements a few at a time, one round trip
@@ -147,9 +191,13 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
   const int32_t prev = begin > 0 ? (int32_t)(rdx_key(pairs[begin - 1]) - (uint32_t)key_base) : -1;                     // key in front of the chunk
   const int32_t next = begin + cnt < total ? (int32_t)(rdx_key(pairs[begin + cnt]) - (uint32_t)key_base) : -1;         // key behind it
   float acc[NDW];
-  float trow[NDW], mrow_v[NDW], vrow_v[NDW];     // the current run's target (and Adam state) row, requested at its head
+  float trow[NDW], srow[NS][NDW];     // the current run's target (and state) rows, requested at its head
 #pragma unroll
-  for (int k = 0; k < NDW; ++k) acc[k] = trow[k] = mrow_v[k] = vrow_v[k] = 0.f;
+  for (int k = 0; k < NDW; ++k) {
+    acc[k] = trow[k] = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) srow[s][k] = 0.f;
+  }
   int32_t cur = -1;           // id of the run being accumulated (-1: none)
   bool leading = false;       // accumulating the segment that continues the previous chunk's run
   int32_t lead_key = -1;
@@ -159,7 +207,7 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
       for (int k = 0; k < NDW; ++k) lead_part[(size_t)chunk * D + k * 64 + lane] = acc[k];
       leading = false;
     } else if (cur >= 0) {
-      apply_run<NDW, NT>(target, adam, cur, scale, lane, acc, trow, mrow_v, vrow_v);
+      rule.template apply_run<NDW, NT>(target, cur, scale, lane, acc, trow, srow);
     }
 #pragma unroll
     for (int k = 0; k < NDW; ++k) acc[k] = 0.f;
@@ -167,11 +215,12 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
   // Only the elements with work are visited: not the dropped ones (empty slots), not the padding row's, not the ones a
   // forward has applied itself (solo) -- in a step whose solo rows are applied in the forward half of a chunk is such,
   // and a pass that walked them anyway (redirected to row 0) ran no faster than the full one.  None of them can sit
-  // INSIDE a run that has work (a run is one key), so skipping them leaves every run's element order untouched.
+  // INSIDE a run that has work (a run is one key), so skipping them leaves every run's element order untouched, and rows
+  // without a kept element are neither read nor written.
   uint64_t work = __ballot(in && !solo && key != drop_key && key != pad_row);
   int last_t = -1;
-  // The query rows AND the target rows of U elements are requested together before the (serial) run logic consumes
-  // them.  Round 1 loaded one query row per iteration and read-modified-wrote the target row inside flush(): every
+  // The query rows AND the target (and state) rows of U elements are requested together before the (serial) run logic
+  // consumes them.  Round 1 loaded one query row per iteration and read-modified-wrote the target row inside flush(): every
   // element waited for its own round trip and every run for an HBM read in the middle of the serial chain (VERDICT r1:
   // 0.9 ms of the 1.7 ms SGD step).  A target row belongs to exactly one run and a closed run to exactly one wave, so
   // reading it at the head of the run instead of at its end sees the same value.  Slots past the last element with
@@ -189,7 +238,7 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
         nu = u + 1;
       }
     }
-    float qv[U][NDW], tv[U][NDW], mv[U][NDW], vv[U][NDW];
+    float qv[U][NDW], tv[U][NDW], sv[U][NS][NDW];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int32_t qr = u < nu ? __builtin_amdgcn_readlane(qrow, ts[u]) : 0;
@@ -201,17 +250,18 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
         qv[u][k] = qp[k * 64 + lane];
         tv[u][k] = ld_row<NT>(tp + k * 64 + lane);
       }
-      if (adam.exp_avg != nullptr) {
-        const float* mp = adam.exp_avg + (size_t)kr * D;
-        const float* vp = adam.exp_avg_sq + (size_t)kr * D;
+      if (rule.has_state()) {
 #pragma unroll
         for (int k = 0; k < NDW; ++k) {
-          mv[u][k] = ld_row<NT>(mp + k * 64 + lane);
-          vv[u][k] = ld_row<NT>(vp + k * 64 + lane);
+#pragma unroll
+          for (int s = 0; s < NS; ++s) sv[u][s][k] = ld_row<NT>(rule.state(s) + (size_t)kr * D + k * 64 + lane);
         }
       } else {
 #pragma unroll
-        for (int k = 0; k < NDW; ++k) mv[u][k] = vv[u][k] = 0.f;
+        for (int k = 0; k < NDW; ++k) {
+#pragma unroll
+          for (int s = 0; s < NS; ++s) sv[u][s][k] = 0.f;
+        }
       }
     }
 #pragma unroll
@@ -227,8 +277,8 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
 #pragma unroll
         for (int k = 0; k < NDW; ++k) {
           trow[k] = tv[u][k];
-          mrow_v[k] = mv[u][k];
-          vrow_v[k] = vv[u][k];
+#pragma unroll
+          for (int s = 0; s < NS; ++s) srow[s][k] = sv[u][s][k];
         }
       } else if (t == 0) {            // the chunk opens inside a run that began in an earlier chunk
         leading = true;
@@ -239,6 +289,9 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
       for (int k = 0; k < NDW; ++k) acc[k] = __fmaf_rn(cf, qv[u][k], acc[k]);
       last_t = t;
     }
+    // vmcnt(0): the rows requested above that nothing read (an element that is not its run's head, a slot past the last
+    // element) have landed.  Left outstanding, they make the compiler wait for them in the middle of the next requests.
+    __builtin_amdgcn_s_waitcnt(0x0f70);
   }
   // the chunk's last segment: still the leading one (the whole chunk lies inside one run), open towards the next chunk,
   // or closed
@@ -247,7 +300,7 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
   if (leading) {
     close_segment();                                  // -> lead_part
   } else if (cur >= 0 && last_t == cnt - 1 && next == cur) {
-    trail_key = cur;                                  // the run goes on: sorted_finish_kernel owns its row
+    trail_key = cur;                                  // the run goes on: the finish pass owns its row
 #pragma unroll
     for (int k = 0; k < NDW; ++k) trail_part[(size_t)chunk * D + k * 64 + lane] = acc[k];
   } else {
@@ -260,28 +313,28 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel
   }
 }
 
-// One wave per chunk whose trailing segment opened a run: adds the leading partials of the following chunks in chunk
-// order (a chunk that lies wholly inside the run passes the walk on) and applies the row once.
-template <int NDW>
-__global__ __launch_bounds__(256) void sorted_finish_kernel(int64_t n_chunks, const float* __restrict__ upstream,
-                                                            int32_t pad_row, float* __restrict__ target, AdamArgs adam,
-                                                            const float* __restrict__ lead_part,
-                                                            const float* __restrict__ trail_part,
-                                                            const int32_t* __restrict__ meta) {
-  constexpr int D = 64 * NDW;
+// The finish pass, one wave per chunk whose trailing segment opened a run: adds the leading partials of the following chunks
+// in chunk order (a chunk that lies wholly inside the run passes the walk on) and applies the row once.  Plain accesses (a
+// few rows per pass).
+template <int NDW, class RULE>
+__device__ __forceinline__ void sorted_finish_frame(int64_t n_chunks, const float* __restrict__ upstream, int32_t pad_row,
+                                                    float* __restrict__ target, const RULE& rule,
+                                                    const float* __restrict__ lead_part, const float* __restrict__ trail_part,
+                                                    const int32_t* __restrict__ meta) {
+  constexpr int D = 64 * NDW, NS = RULE::NS;
   const int lane = lane_id();
   const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (chunk >= n_chunks) return;
   const int32_t cur = meta[chunk * META_STRIDE + META_TRAIL_KEY];
   if (cur < 0 || cur == pad_row) return;
   const float scale = upstream ? upstream[0] : 1.f;
-  float acc[NDW], trow[NDW], mrow_v[NDW], vrow_v[NDW];
+  float acc[NDW], trow[NDW], srow[NS][NDW];
 #pragma unroll
   for (int k = 0; k < NDW; ++k) {
     acc[k] = trail_part[(size_t)chunk * D + k * 64 + lane];
     trow[k] = target[(size_t)cur * D + k * 64 + lane];
-    mrow_v[k] = adam.exp_avg ? adam.exp_avg[(size_t)cur * D + k * 64 + lane] : 0.f;
-    vrow_v[k] = adam.exp_avg ? adam.exp_avg_sq[(size_t)cur * D + k * 64 + lane] : 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) srow[s][k] = rule.has_state() ? rule.state(s)[(size_t)cur * D + k * 64 + lane] : 0.f;
   }
   for (int64_t c2 = chunk + 1; c2 < n_chunks; ++c2) {
     if (meta[c2 * META_STRIDE + META_LEAD_KEY] != cur) break;
@@ -289,41 +342,34 @@ __global__ __launch_bounds__(256) void sorted_finish_kernel(int64_t n_chunks, co
     for (int k = 0; k < NDW; ++k) acc[k] += lead_part[(size_t)c2 * D + k * 64 + lane];
     if (!meta[c2 * META_STRIDE + META_LEAD_FULL]) break;
   }
-  apply_run<NDW>(target, adam, cur, scale, lane, acc, trow, mrow_v, vrow_v);
+  rule.template apply_run<NDW, false>(target, cur, scale, lane, acc, trow, srow);
 }
 
-// ---- the Adagrad form (rsa_rows_update_args.rule == RSA_ROWS_ADAGRAD): torch.optim.Adagrad on the touched rows
-//     g = upstream * run sum;   s' = s + g g;   w' = w - clr (g / (sqrt(s') + eps))
-// with ONE state table.  A row without a kept element has g = 0, for which torch's dense pass changes neither s nor w
-// (0 / (sqrt(s) + eps) = 0): leaving such rows alone IS the dense rule, and the sparse branch of torch.optim.Adagrad squares
-// the coalesced row gradient -- the run sum these passes hold in registers.
-// Every rounding is spelled out so that tests/adagrad_referee.py can follow it operation for operation:
-//     g   = fl(scale * acc)
-//     s'  = fl(g * g + s)                 FUSED: one rounding
-//     den = fl(fl(sqrt(s')) + eps)        sqrtf and the division are the correctly rounded ones (hipcc's default)
-//     q   = fl(g / den)
-//     w'  = fl(-clr * q + w)              FUSED: one rounding
-// The kernels below are copies of the frame of sorted_apply_kernel / sorted_finish_kernel under names of their own: a further
-// template parameter on those two would rename every instantiation and a body shared through a function would put the existing
-// kernels' code at the mercy of the inliner, while tools/kernel_fingerprint.py holds every kernel that exists today to its bytes.
-// What differs: one state row (not two) is requested ahead and carried across a run, and DEC is DecStep (exchange segments are
-// only ever accumulated, never stepped).
-template <int NDW, bool NT>
-__device__ __forceinline__ void apply_run_adagrad(float* __restrict__ target, const AdagradArgs& ada, int32_t cur, float scale, int lane,
-                                                  const float (&acc)[NDW], const float (&trow)[NDW], const float (&srow_v)[NDW]) {
-  constexpr int D = 64 * NDW;
-  float* row = target + (size_t)cur * D;
-  float* srow = ada.state_sum + (size_t)cur * D;
-#pragma unroll
-  for (int k = 0; k < NDW; ++k) {
-    const int c = k * 64 + lane;
-    const float g = __fmul_rn(scale, acc[k]);
-    const float s1 = __fmaf_rn(g, g, srow_v[k]);
-    const float den = __fadd_rn(sqrtf(s1), ada.eps);
-    const float q = g / den;
-    st_row<NT>(srow + c, s1);
-    st_row<NT>(row + c, __fmaf_rn(-ada.clr, q, trow[k]));
-  }
+// The kernels: the two frames under a rule.  One wave per chunk of 64 sorted elements; runs that begin and end inside the
+// chunk are applied by the apply kernel, the open leading / trailing segments leave their partial sums in lead_part /
+// trail_part [chunk, D] for the finish kernel.
+#ifndef RSA_SORTED_MIN_WAVES
+#define RSA_SORTED_MIN_WAVES 1
+#endif
+template <int NDW, class DEC, bool NT>
+__global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_kernel(const uint64_t* __restrict__ pairs,
+                                                           int64_t total, const float* __restrict__ query, const DEC dec,
+                                                           const float* __restrict__ upstream, int32_t pad_row,
+                                                           int32_t drop_key, float* __restrict__ target, AdamArgs adam,
+                                                           float* __restrict__ lead_part, float* __restrict__ trail_part,
+                                                           int32_t* __restrict__ meta, int32_t key_base, int32_t elem_base,
+                                                           int32_t chunk_elems) {
+  sorted_apply_frame<NDW, NT>(pairs, total, query, dec, upstream, pad_row, drop_key, target, AdamRule{adam}, lead_part, trail_part,
+                              meta, key_base, elem_base, chunk_elems);
+}
+
+template <int NDW>
+__global__ __launch_bounds__(256) void sorted_finish_kernel(int64_t n_chunks, const float* __restrict__ upstream,
+                                                            int32_t pad_row, float* __restrict__ target, AdamArgs adam,
+                                                            const float* __restrict__ lead_part,
+                                                            const float* __restrict__ trail_part,
+                                                            const int32_t* __restrict__ meta) {
+  sorted_finish_frame<NDW>(n_chunks, upstream, pad_row, target, AdamRule{adam}, lead_part, trail_part, meta);
 }
 
 template <int NDW, bool NT>
@@ -331,150 +377,17 @@ __global__ __launch_bounds__(256, RSA_SORTED_MIN_WAVES) void sorted_apply_adagra
     const uint64_t* __restrict__ pairs, int64_t total, const float* __restrict__ query, const DecStep dec,
     const float* __restrict__ upstream, int32_t pad_row, int32_t drop_key, float* __restrict__ target, AdagradArgs ada,
     float* __restrict__ lead_part, float* __restrict__ trail_part, int32_t* __restrict__ meta, int32_t chunk_elems) {
-  constexpr int D = 64 * NDW;
-  const int lane = lane_id();
-  const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t begin = chunk * chunk_elems;
-  if (begin >= total) return;
-  const float scale = upstream ? upstream[0] : 1.f;
-  const int64_t i = begin + lane;
-  const bool in = lane < chunk_elems && i < total;
-  const uint64_t pr = in ? pairs[i] : 0ull;
-  const int32_t key = in ? (int32_t)rdx_key(pr) : -1;
-  int32_t qrow = 0;
-  float coef = 0.f;
-  bool solo = false;                  // (no forward applies Adagrad rows itself; a flagged element is skipped as in the SGD form)
-  if (in && key != drop_key) {
-    int32_t e = (int32_t)rdx_val(pr);
-    solo = e < 0;
-    e &= 0x7fffffff;
-    if (!solo) dec((int64_t)e, qrow, coef);
-  }
-  const int cnt = (int)(total - begin < chunk_elems ? total - begin : chunk_elems);
-  const int32_t prev = begin > 0 ? (int32_t)rdx_key(pairs[begin - 1]) : -1;
-  const int32_t next = begin + cnt < total ? (int32_t)rdx_key(pairs[begin + cnt]) : -1;
-  float acc[NDW];
-  float trow[NDW], srow_v[NDW];       // the current run's target and state_sum row, requested at its head
-#pragma unroll
-  for (int k = 0; k < NDW; ++k) acc[k] = trow[k] = srow_v[k] = 0.f;
-  int32_t cur = -1;
-  bool leading = false;
-  int32_t lead_key = -1;
-  auto close_segment = [&]() {
-    if (leading) {
-#pragma unroll
-      for (int k = 0; k < NDW; ++k) lead_part[(size_t)chunk * D + k * 64 + lane] = acc[k];
-      leading = false;
-    } else if (cur >= 0) {
-      apply_run_adagrad<NDW, NT>(target, ada, cur, scale, lane, acc, trow, srow_v);
-    }
-#pragma unroll
-    for (int k = 0; k < NDW; ++k) acc[k] = 0.f;
-  };
-  // only the elements with work are visited (see sorted_apply_kernel): rows without a kept element are neither read nor written
-  uint64_t work = __ballot(in && !solo && key != drop_key && key != pad_row);
-  int last_t = -1;
-  constexpr int U = RSA_SORTED_UNROLL;
-  while (work) {
-    int ts[U];
-    int nu = 0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      ts[u] = 63;
-      if (work) {
-        ts[u] = __ffsll((unsigned long long)work) - 1;
-        work &= work - 1;
-        nu = u + 1;
-      }
-    }
-    // query row, target row and state_sum row of U elements requested together; slots past the last element with work
-    // request row 0, always readable
-    float qv[U][NDW], tv[U][NDW], sv[U][NDW];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int32_t qr = u < nu ? __builtin_amdgcn_readlane(qrow, ts[u]) : 0;
-      const int32_t kr = u < nu ? __builtin_amdgcn_readlane(key, ts[u]) : 0;
-      const float* qp = query + (size_t)qr * D;
-      const float* tp = target + (size_t)kr * D;
-      const float* sp = ada.state_sum + (size_t)kr * D;
-#pragma unroll
-      for (int k = 0; k < NDW; ++k) {
-        qv[u][k] = qp[k * 64 + lane];
-        tv[u][k] = ld_row<NT>(tp + k * 64 + lane);
-        sv[u][k] = ld_row<NT>(sp + k * 64 + lane);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (u >= nu) break;
-      const int t = ts[u];
-      const int32_t kt = __builtin_amdgcn_readlane(key, t);
-      const int32_t before = t == 0 ? prev : __builtin_amdgcn_readlane(key, t - 1);
-      const bool head = kt != before;
-      if (head) {
-        close_segment();
-        cur = kt;
-#pragma unroll
-        for (int k = 0; k < NDW; ++k) {
-          trow[k] = tv[u][k];
-          srow_v[k] = sv[u][k];
-        }
-      } else if (t == 0) {            // the chunk opens inside a run that began in an earlier chunk
-        leading = true;
-        cur = lead_key = kt;
-      }
-      const float cf = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(coef), t));
-#pragma unroll
-      for (int k = 0; k < NDW; ++k) acc[k] = __fmaf_rn(cf, qv[u][k], acc[k]);
-      last_t = t;
-    }
-  }
-  const bool whole = leading;
-  int32_t trail_key = -1;
-  if (leading) {
-    close_segment();                                  // -> lead_part
-  } else if (cur >= 0 && last_t == cnt - 1 && next == cur) {
-    trail_key = cur;                                  // the run goes on: sorted_finish_adagrad_kernel owns its row
-#pragma unroll
-    for (int k = 0; k < NDW; ++k) trail_part[(size_t)chunk * D + k * 64 + lane] = acc[k];
-  } else {
-    close_segment();
-  }
-  if (lane == 0) {
-    meta[chunk * META_STRIDE + META_LEAD_KEY] = lead_key;
-    meta[chunk * META_STRIDE + META_LEAD_FULL] = whole ? 1 : 0;
-    meta[chunk * META_STRIDE + META_TRAIL_KEY] = trail_key;
-  }
+  sorted_apply_frame<NDW, NT>(pairs, total, query, dec, upstream, pad_row, drop_key, target, AdagradRule{ada}, lead_part,
+                              trail_part, meta, 0, 0, chunk_elems);
 }
 
-// the partials of a run that crosses chunk borders, added in chunk order; plain accesses (a few rows per pass)
 template <int NDW>
 __global__ __launch_bounds__(256) void sorted_finish_adagrad_kernel(int64_t n_chunks, const float* __restrict__ upstream,
                                                                     int32_t pad_row, float* __restrict__ target, AdagradArgs ada,
                                                                     const float* __restrict__ lead_part,
                                                                     const float* __restrict__ trail_part,
                                                                     const int32_t* __restrict__ meta) {
-  constexpr int D = 64 * NDW;
-  const int lane = lane_id();
-  const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (chunk >= n_chunks) return;
-  const int32_t cur = meta[chunk * META_STRIDE + META_TRAIL_KEY];
-  if (cur < 0 || cur == pad_row) return;
-  const float scale = upstream ? upstream[0] : 1.f;
-  float acc[NDW], trow[NDW], srow_v[NDW];
-#pragma unroll
-  for (int k = 0; k < NDW; ++k) {
-    acc[k] = trail_part[(size_t)chunk * D + k * 64 + lane];
-    trow[k] = target[(size_t)cur * D + k * 64 + lane];
-    srow_v[k] = ada.state_sum[(size_t)cur * D + k * 64 + lane];
-  }
-  for (int64_t c2 = chunk + 1; c2 < n_chunks; ++c2) {
-    if (meta[c2 * META_STRIDE + META_LEAD_KEY] != cur) break;
-#pragma unroll
-    for (int k = 0; k < NDW; ++k) acc[k] = __fadd_rn(acc[k], lead_part[(size_t)c2 * D + k * 64 + lane]);
-    if (!meta[c2 * META_STRIDE + META_LEAD_FULL]) break;
-  }
-  apply_run_adagrad<NDW, false>(target, ada, cur, scale, lane, acc, trow, srow_v);
+  sorted_finish_frame<NDW>(n_chunks, upstream, pad_row, target, AdagradRule{ada}, lead_part, trail_part, meta);
 }
 
 // After the sort: an element whose key differs from both neighbours is the ONLY element of the step on its row ("solo").
@@ -554,64 +467,49 @@ int classify_solo(uint64_t* pairs, int64_t total, int64_t pad_row, int64_t drop_
   return RSA_OK;
 }
 
-// the apply + finish passes over sorted pairs
-template <class DEC>
+// the apply + finish passes over sorted pairs.  The Adagrad kernels exist for a step's elements only (DEC = DecStep, no
+// key_base / elem_base).
+template <class RULE, class DEC>
 static int apply_sorted_pairs(const uint64_t* pairs, int64_t total, const float* query, int32_t dim, const DEC& dec,
-                              const float* upstream, int64_t drop_key, int64_t pad_row, float* target, AdamArgs adam,
+                              const float* upstream, int64_t drop_key, int64_t pad_row, float* target, const RULE& rule,
                               const SortedLayout& L, hipStream_t s, int64_t key_base = 0, int64_t elem_base = 0) {
+  constexpr bool ADAGRAD = std::is_same_v<RULE, AdagradRule>;
   const int ce = sorted_chunk_elems(total);
   const unsigned chunks = (unsigned)((total + ce - 1) / ce);
   dim3 grid((chunks + 3) / 4), block(256);
   const int32_t pad = (int32_t)(pad_row < 0 || pad_row >= (1ll << 31) ? -2 : pad_row);
-  const bool nt = RSA_SORTED_NT == 1 || (RSA_SORTED_NT == 2 && streams_past_cache(drop_key, dim));      // (drop_key = the table's row count)
+  // (drop_key = the table's row count; the state tables stream with the target)
+  const bool nt = RSA_SORTED_NT == 1 || (RSA_SORTED_NT == 2 && streams_past_cache(drop_key, dim));
   const bool built = dispatch_dim<64, 128, 256>(dim, [&](auto D) {
     constexpr int NDW = D() / 64;
     dispatch_bool(nt, [&](auto NT) {
-      hipLaunchKernelGGL((sorted_apply_kernel<NDW, DEC, NT()>), grid, block, 0, s, pairs, total, query, dec, upstream, pad,
-                         (int32_t)drop_key, target, adam, L.lead_part, L.trail_part, L.meta, (int32_t)key_base, (int32_t)elem_base,
-                         (int32_t)ce);
+      if constexpr (ADAGRAD)
+        hipLaunchKernelGGL((sorted_apply_adagrad_kernel<NDW, NT()>), grid, block, 0, s, pairs, total, query, dec, upstream, pad,
+                           (int32_t)drop_key, target, rule.a, L.lead_part, L.trail_part, L.meta, (int32_t)ce);
+      else
+        hipLaunchKernelGGL((sorted_apply_kernel<NDW, DEC, NT()>), grid, block, 0, s, pairs, total, query, dec, upstream, pad,
+                           (int32_t)drop_key, target, rule.a, L.lead_part, L.trail_part, L.meta, (int32_t)key_base,
+                           (int32_t)elem_base, (int32_t)ce);
     });
-    hipLaunchKernelGGL(sorted_finish_kernel<NDW>, grid, block, 0, s, (int64_t)chunks, upstream, pad, target, adam, L.lead_part,
-                       L.trail_part, L.meta);
+    if constexpr (ADAGRAD)
+      hipLaunchKernelGGL(sorted_finish_adagrad_kernel<NDW>, grid, block, 0, s, (int64_t)chunks, upstream, pad, target, rule.a,
+                         L.lead_part, L.trail_part, L.meta);
+    else
+      hipLaunchKernelGGL(sorted_finish_kernel<NDW>, grid, block, 0, s, (int64_t)chunks, upstream, pad, target, rule.a, L.lead_part,
+                         L.trail_part, L.meta);
   });
   if (!built) {
     rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", dim);
     return RSA_ERR_UNSUPPORTED;
   }
-  RSA_CHECK_LAUNCH("rsa_rows_update_sorted(apply)");
-  return RSA_OK;
-}
-
-// the Adagrad form of the two passes (a step's elements only: DecStep)
-static int apply_sorted_pairs_adagrad(const uint64_t* pairs, int64_t total, const float* query, int32_t dim, const DecStep& dec,
-                                      const float* upstream, int64_t drop_key, int64_t pad_row, float* target, AdagradArgs ada,
-                                      const SortedLayout& L, hipStream_t s) {
-  const int ce = sorted_chunk_elems(total);
-  const unsigned chunks = (unsigned)((total + ce - 1) / ce);
-  dim3 grid((chunks + 3) / 4), block(256);
-  const int32_t pad = (int32_t)(pad_row < 0 || pad_row >= (1ll << 31) ? -2 : pad_row);
-  const bool nt = RSA_SORTED_NT == 1 || (RSA_SORTED_NT == 2 && streams_past_cache(drop_key, dim));      // target AND state_sum
-  const bool built = dispatch_dim<64, 128, 256>(dim, [&](auto D) {
-    constexpr int NDW = D() / 64;
-    dispatch_bool(nt, [&](auto NT) {
-      hipLaunchKernelGGL((sorted_apply_adagrad_kernel<NDW, NT()>), grid, block, 0, s, pairs, total, query, dec, upstream, pad,
-                         (int32_t)drop_key, target, ada, L.lead_part, L.trail_part, L.meta, (int32_t)ce);
-    });
-    hipLaunchKernelGGL(sorted_finish_adagrad_kernel<NDW>, grid, block, 0, s, (int64_t)chunks, upstream, pad, target, ada,
-                       L.lead_part, L.trail_part, L.meta);
-  });
-  if (!built) {
-    rsa::set_error("rsa_rows_update_sorted: dim=%d: built for dim in {64, 128, 256}", dim);
-    return RSA_ERR_UNSUPPORTED;
-  }
-  RSA_CHECK_LAUNCH("rsa_rows_update_sorted(adagrad apply)");
+  RSA_CHECK_LAUNCH(RULE::who);
   return RSA_OK;
 }
 
 int apply_sorted_segments(const uint64_t* pairs, int64_t total, int64_t slots, const float* query, int32_t dim,
                           const int64_t* keys, const float* d, const float* upstream, int64_t n_rows, int64_t pad_row,
                           float* target, const SortedLayout& L, hipStream_t s) {
-  const AdamArgs none{nullptr, nullptr, 0.f, 0.f, 0.f, 0.f};
+  const AdamRule none{{nullptr, nullptr, 0.f, 0.f, 0.f, 0.f}};
   const DecSegments dec{keys, d, slots};
   return apply_sorted_pairs(pairs, total, query, dim, dec, upstream, n_rows, pad_row, target, none, L, s);
 }
@@ -657,7 +555,7 @@ int apply_step_all(bool users, const float* query, const int64_t* query_index, i
   const int64_t t_items = n_queries * (int64_t)(num_neg + 1), total = t_items + n_queries;
   const SortedLayout L = sorted_layout(workspace, total);
   const uint64_t* sorted = radix_result(L.pairs_a, L.pairs_b, step_all_bits(n_items, n_users));
-  const AdamArgs none{nullptr, nullptr, 0.f, 0.f, 0.f, 0.f};
+  const AdamRule none{{nullptr, nullptr, 0.f, 0.f, 0.f, 0.f}};
   if (!users) {
     const DecStep dec{query_index, dpos, dneg, (int)num_neg, 1};
     return apply_sorted_pairs(sorted, t_items, query, dim, dec, upstream, n_items, 0, target, none, L, s);
@@ -721,11 +619,11 @@ static int sort_step_elements(const rsa_rows_update_args& a, uint8_t* solo, hipS
 // The caller's hyper-parameters arrive as doubles (ABI 12): 1 - beta and the bias corrections are taken from THOSE values, as
 // torch.optim.SparseAdam takes them from its Python floats, and each kernel constant is rounded to fp32 once.  (As floats,
 // 1.f - float(0.999) = 0.0009999871: exp_avg_sq of every touched row 1.29e-5 short, the step size ~6e-6 off in one direction.)
-static AdamArgs adam_of(const rsa_rows_update_args& a) {
-  if (a.exp_avg == nullptr) return AdamArgs{nullptr, nullptr, 0.f, 0.f, 0.f, 0.f};
+static AdamRule adam_of(const rsa_rows_update_args& a) {
+  if (a.exp_avg == nullptr) return AdamRule{{nullptr, nullptr, 0.f, 0.f, 0.f, 0.f}};
   const double bc1 = 1.0 - pow(a.beta1, (double)a.step), bc2 = 1.0 - pow(a.beta2, (double)a.step);
-  return AdamArgs{a.exp_avg, a.exp_avg_sq, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), (float)a.eps,
-                  (float)(a.lr * sqrt(bc2) / bc1)};
+  return AdamRule{{a.exp_avg, a.exp_avg_sq, (float)(1.0 - a.beta1), (float)(1.0 - a.beta2), (float)a.eps,
+                   (float)(a.lr * sqrt(bc2) / bc1)}};
 }
 
 static int check_adam(const rsa_rows_update_args& a, const char* who) {
@@ -737,8 +635,8 @@ static int check_adam(const rsa_rows_update_args& a, const char* who) {
 
 // Adagrad's constants as adam_of takes Adam's: clr = lr / (1 + (step - 1) lr_decay) (torch.optim.Adagrad, step 1-based) in
 // double from the caller's doubles, each rounded to fp32 once.
-static AdagradArgs adagrad_of(const rsa_rows_update_args& a) {
-  return AdagradArgs{a.state_sum, (float)(a.lr / (1.0 + (double)(a.step - 1) * a.lr_decay)), (float)a.eps};
+static AdagradRule adagrad_of(const rsa_rows_update_args& a) {
+  return AdagradRule{{a.state_sum, (float)(a.lr / (1.0 + (double)(a.step - 1) * a.lr_decay)), (float)a.eps}};
 }
 
 // Which rule the block asks for, and that rule's fields; before any HIP call.  rule 0 is the block as it was before `rule`
@@ -766,11 +664,10 @@ static int apply_step_elements(const rsa_rows_update_args& a, int has_pos, hipSt
                 (long long)a.workspace_bytes, (long long)need);
   const SortedLayout L = sorted_layout(a.workspace, a.n_queries * (int64_t)(a.num_neg + 1));
   const DecStep dec{a.query_index, a.dpos, a.dneg, (int)a.num_neg, has_pos};
-  if (a.rule == RSA_ROWS_ADAGRAD)
-    return apply_sorted_pairs_adagrad(step_sorted(L, a.n_items), total, a.query, a.dim, dec, a.upstream, a.n_items, a.pad_row, a.target,
-                                      adagrad_of(a), L, s);
-  return apply_sorted_pairs(step_sorted(L, a.n_items), total, a.query, a.dim, dec, a.upstream, a.n_items, a.pad_row, a.target,
-                            adam_of(a), L, s);
+  auto apply = [&](const auto& rule) {
+    return apply_sorted_pairs(step_sorted(L, a.n_items), total, a.query, a.dim, dec, a.upstream, a.n_items, a.pad_row, a.target, rule, L, s);
+  };
+  return a.rule == RSA_ROWS_ADAGRAD ? apply(adagrad_of(a)) : apply(adam_of(a));
 }
 
 extern "C" int rsa_sort_step_elements(const rsa_rows_update_args* args, rsa_stream_t stream) {

@@ -509,37 +509,25 @@ class _device_of:
             self.guard.__exit__(*exc)
 
 
-class FusedBPRAdam:
-    """Complete lazy-Adam training step of a BPR two-tower model (nn.Embedding user and item tables) without
-    gradient tensors: the forward samples, scores, evaluates BPRLoss and accumulates the user-row gradients;
-    ``rsa_rows_update_sorted`` sorts the step's (item id, element) pairs, sums every touched row's gradient in
-    registers and applies torch.optim.SparseAdam's update to that row of (weight, exp_avg, exp_avg_sq); the user
-    rows go through the same kernel with the accumulated row gradients.  Equal (up to fp32 summation order) to
-    ``loss.backward()`` with sparse embeddings + ``torch.optim.SparseAdam.step()`` -- whose coalesce pass alone
-    takes 16 ms at B = 65 536, n = 64 -- and untouched rows keep their state (lazy)."""
-
-    def __init__(self, item_weight, user_weight, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        self.iw, self.uw = item_weight.data, user_weight.data
-        if self.iw.shape[1] not in (64, 128, 256):
-            raise NotImplementedError('FusedBPRAdam: embed_dim must be 64, 128 or 256')
-        self.lr, self.betas, self.eps, self.t = float(lr), betas, float(eps), 0
-        self.state = {k: torch.zeros_like(w) for k, w in (('im', self.iw), ('iv', self.iw), ('um', self.uw), ('uv', self.uw))}
+class _FusedBPRRowsStep:
+    """The step of ``FusedBPRAdam`` / ``FusedBPRAdagrad``, written once.  A subclass supplies its constructor (checks, the ``state``
+    tables), ``_hp()`` (the hyper-parameters of this step, as keywords of its row update), the pair ``_sorted`` / ``_presorted`` of
+    ``ops`` row updates and ``_state(side)``: the state tables that travel with the item ('i') or the user ('u') table."""
 
     def step(self, num_neg, *, user_ids, pos_ids, sampler=None, neg_ids=None):
         """One step; returns (loss, neg_ids).  num_neg % 64 == 0."""
         M = user_ids.numel()
         kind, kw = _sampler_cfg(sampler, neg_ids, M)
         self.t += 1
-        st = self.state
         with torch.no_grad():
             out = ops.fused_forward(self.iw, self.uw, num_neg, query_index=user_ids, pos_ids=pos_ids, sampler=kind,
                                     want_logp=False, fused_bpr=True, want_query_grad=True, **kw)
-            hp = dict(lr=self.lr, betas=self.betas, eps=self.eps, step=self.t)
+            hp = self._hp()
             # item rows first: their gradient needs the pre-update user rows (the user gradient is already complete)
-            ops.adam_rows_sorted(self.iw, st['im'], st['iv'], self.uw, out['neg_ids'], out['dneg'], query_index=user_ids,
-                                 pos_ids=pos_ids, dpos=out['dpos'], pad_row=0, **hp)
+            self._sorted(self.iw, *self._state('i'), self.uw, out['neg_ids'], out['dneg'], query_index=user_ids, pos_ids=pos_ids,
+                         dpos=out['dpos'], pad_row=0, **hp)
             ones = torch.ones(M, 1, dtype=torch.float32, device=self.iw.device)
-            ops.adam_rows_sorted(self.uw, st['um'], st['uv'], out['query_grad'], user_ids.view(M, 1), ones, pad_row=0, **hp)
+            self._sorted(self.uw, *self._state('u'), out['query_grad'], user_ids.view(M, 1), ones, pad_row=0, **hp)
         return out['loss'], out['neg_ids']
 
     # ---- one batch ahead (see PrefetchedBPRSGD): sampling and the two sorts (item rows, user rows) do not read the weights
@@ -548,7 +536,7 @@ class FusedBPRAdam:
         ``step_prepared``.  Tickets are stepped once each, in the order they were prepared; the results are those of the
         same sequence of ``step`` calls bit for bit."""
         if sampler_kind(sampler) not in (nat.SAMPLER_UNIFORM, nat.SAMPLER_POPULAR):
-            raise TypeError(f'FusedBPRAdam.prepare does not cover sampler {type(sampler).__name__}')
+            raise TypeError(f'{type(self).__name__}.prepare does not cover sampler {type(sampler).__name__}')
         if getattr(self, 'side', None) is None:
             self.side = torch.cuda.Stream(device=self.iw.device)
         main = torch.cuda.current_stream(self.iw.device)
@@ -569,19 +557,43 @@ class FusedBPRAdam:
         uid, pos, neg, n = ticket['user_ids'], ticket['pos_ids'], ticket['neg'], ticket['num_neg']
         M = uid.numel()
         self.t += 1
-        st = self.state
         with torch.no_grad():
             out = ops.fused_forward(self.iw, self.uw, n, query_index=uid, pos_ids=pos, neg_ids=neg, sampler=nat.SAMPLER_GIVEN,
                                     want_logp=False, fused_bpr=True, want_query_grad=True)
-            hp = dict(lr=self.lr, betas=self.betas, eps=self.eps, step=self.t)
-            ops.adam_rows_presorted(self.iw, st['im'], st['iv'], self.uw, ticket['ws'], M, n, out['dneg'], query_index=uid,
-                                    dpos=out['dpos'], pad_row=0, **hp)
+            hp = self._hp()
+            self._presorted(self.iw, *self._state('i'), self.uw, ticket['ws'], M, n, out['dneg'], query_index=uid, dpos=out['dpos'],
+                            pad_row=0, **hp)
             ones = torch.ones(M, 1, dtype=torch.float32, device=self.iw.device)
-            ops.adam_rows_presorted(self.uw, st['um'], st['uv'], out['query_grad'], ticket['ws_user'], M, 1, ones, pad_row=0, **hp)
+            self._presorted(self.uw, *self._state('u'), out['query_grad'], ticket['ws_user'], M, 1, ones, pad_row=0, **hp)
         return out['loss'], out['neg_ids']
 
 
-class FusedBPRAdagrad:
+class FusedBPRAdam(_FusedBPRRowsStep):
+    """Complete lazy-Adam training step of a BPR two-tower model (nn.Embedding user and item tables) without
+    gradient tensors: the forward samples, scores, evaluates BPRLoss and accumulates the user-row gradients;
+    ``rsa_rows_update_sorted`` sorts the step's (item id, element) pairs, sums every touched row's gradient in
+    registers and applies torch.optim.SparseAdam's update to that row of (weight, exp_avg, exp_avg_sq); the user
+    rows go through the same kernel with the accumulated row gradients.  Equal (up to fp32 summation order) to
+    ``loss.backward()`` with sparse embeddings + ``torch.optim.SparseAdam.step()`` -- whose coalesce pass alone
+    takes 16 ms at B = 65 536, n = 64 -- and untouched rows keep their state (lazy)."""
+
+    def __init__(self, item_weight, user_weight, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        self.iw, self.uw = item_weight.data, user_weight.data
+        if self.iw.shape[1] not in (64, 128, 256):
+            raise NotImplementedError('FusedBPRAdam: embed_dim must be 64, 128 or 256')
+        self.lr, self.betas, self.eps, self.t = float(lr), betas, float(eps), 0
+        self.state = {k: torch.zeros_like(w) for k, w in (('im', self.iw), ('iv', self.iw), ('um', self.uw), ('uv', self.uw))}
+
+    _sorted, _presorted = staticmethod(ops.adam_rows_sorted), staticmethod(ops.adam_rows_presorted)
+
+    def _hp(self):
+        return dict(lr=self.lr, betas=self.betas, eps=self.eps, step=self.t)
+
+    def _state(self, side):
+        return self.state[side + 'm'], self.state[side + 'v']
+
+
+class FusedBPRAdagrad(_FusedBPRRowsStep):
     """Complete Adagrad training step of a BPR two-tower model (nn.Embedding user and item tables) without gradient tensors,
     in the shape of ``FusedBPRAdam``: the forward samples, scores, evaluates BPRLoss and accumulates the user-row gradients;
     ``rsa_rows_update_sorted`` (rule RSA_ROWS_ADAGRAD) sorts the step's (item id, element) pairs, sums every touched row's
@@ -600,60 +612,13 @@ class FusedBPRAdagrad:
         self.lr, self.lr_decay, self.eps, self.t = float(lr), float(lr_decay), float(eps), 0
         self.state = {k: torch.full_like(w, float(initial_accumulator_value)) for k, w in (('is', self.iw), ('us', self.uw))}
 
+    _sorted, _presorted = staticmethod(ops.adagrad_rows_sorted), staticmethod(ops.adagrad_rows_presorted)
+
     def _hp(self):
         return dict(lr=self.lr, lr_decay=self.lr_decay, eps=self.eps, step=self.t)
 
-    def step(self, num_neg, *, user_ids, pos_ids, sampler=None, neg_ids=None):
-        """One step; returns (loss, neg_ids).  num_neg % 64 == 0."""
-        M = user_ids.numel()
-        kind, kw = _sampler_cfg(sampler, neg_ids, M)
-        self.t += 1
-        with torch.no_grad():
-            out = ops.fused_forward(self.iw, self.uw, num_neg, query_index=user_ids, pos_ids=pos_ids, sampler=kind,
-                                    want_logp=False, fused_bpr=True, want_query_grad=True, **kw)
-            # item rows first: their gradient needs the pre-update user rows (the user gradient is already complete)
-            ops.adagrad_rows_sorted(self.iw, self.state['is'], self.uw, out['neg_ids'], out['dneg'], query_index=user_ids,
-                                    pos_ids=pos_ids, dpos=out['dpos'], pad_row=0, **self._hp())
-            ones = torch.ones(M, 1, dtype=torch.float32, device=self.iw.device)
-            ops.adagrad_rows_sorted(self.uw, self.state['us'], out['query_grad'], user_ids.view(M, 1), ones, pad_row=0, **self._hp())
-        return out['loss'], out['neg_ids']
-
-    # ---- one batch ahead, as FusedBPRAdam: sampling and the two sorts (item rows, user rows) do not read the weights
-    def prepare(self, num_neg, *, user_ids, pos_ids, sampler):
-        """Draw the negatives of a batch and sort its (item id, element) pairs on a side stream -> ticket for
-        ``step_prepared``.  Tickets are stepped once each, in the order they were prepared; the results are those of the
-        same sequence of ``step`` calls bit for bit."""
-        if sampler_kind(sampler) not in (nat.SAMPLER_UNIFORM, nat.SAMPLER_POPULAR):
-            raise TypeError(f'FusedBPRAdagrad.prepare does not cover sampler {type(sampler).__name__}')
-        if getattr(self, 'side', None) is None:
-            self.side = torch.cuda.Stream(device=self.iw.device)
-        main = torch.cuda.current_stream(self.iw.device)
-        self.side.wait_stream(main)
-        with torch.no_grad(), torch.cuda.stream(self.side):
-            neg = sampler(torch.empty(user_ids.numel(), 1, device=self.iw.device), num_neg, None)[0]
-            _, ws = ops.sort_step_elements(pos_ids, neg, self.iw.shape[0], pad_row=0, want_solo=False)
-            _, ws_user = ops.sort_step_elements(None, user_ids.view(-1, 1), self.uw.shape[0], pad_row=0, want_solo=False)
-            ready = torch.cuda.Event()
-            ready.record(self.side)
-        for t in (neg, ws, ws_user):
-            t.record_stream(main)
-        return {'user_ids': user_ids, 'pos_ids': pos_ids, 'neg': neg, 'ws': ws, 'ws_user': ws_user, 'ready': ready,
-                'num_neg': int(num_neg)}
-
-    def step_prepared(self, ticket):
-        torch.cuda.current_stream(self.iw.device).wait_event(ticket['ready'])
-        uid, pos, neg, n = ticket['user_ids'], ticket['pos_ids'], ticket['neg'], ticket['num_neg']
-        M = uid.numel()
-        self.t += 1
-        with torch.no_grad():
-            out = ops.fused_forward(self.iw, self.uw, n, query_index=uid, pos_ids=pos, neg_ids=neg, sampler=nat.SAMPLER_GIVEN,
-                                    want_logp=False, fused_bpr=True, want_query_grad=True)
-            ops.adagrad_rows_presorted(self.iw, self.state['is'], self.uw, ticket['ws'], M, n, out['dneg'], query_index=uid,
-                                       dpos=out['dpos'], pad_row=0, **self._hp())
-            ones = torch.ones(M, 1, dtype=torch.float32, device=self.iw.device)
-            ops.adagrad_rows_presorted(self.uw, self.state['us'], out['query_grad'], ticket['ws_user'], M, 1, ones, pad_row=0,
-                                       **self._hp())
-        return out['loss'], out['neg_ids']
+    def _state(self, side):
+        return (self.state[side + 's'],)
 
 
 class BPRSGDStep:
@@ -678,8 +643,10 @@ class BPRSGDStep:
 class BPRAdamStep:
     """The same for ``train.fused_optimizer: 'adam'`` over one ``FusedBPRAdam``; with ``lookahead`` it is its own ``stepper``."""
 
+    optimizer = FusedBPRAdam
+
     def __init__(self, item_weight, user_weight, num_neg, lr, sampler, fuid, fiid, lookahead):
-        self.opt = FusedBPRAdam(item_weight, user_weight, lr=lr)
+        self.opt = self.optimizer(item_weight, user_weight, lr=lr)
         self.num_neg, self.sampler, self.fuid, self.fiid, self.lookahead = num_neg, sampler, fuid, fiid, lookahead
         self.step = self.opt.step_prepared
 
@@ -699,7 +666,4 @@ class BPRAdagradStep(BPRAdamStep):
     """The same for ``train.fused_optimizer: 'learner'`` with ``train.learner: 'adagrad'`` over one ``FusedBPRAdagrad``
     (torch.optim.Adagrad's defaults, as ``_make_optimizer`` leaves them)."""
 
-    def __init__(self, item_weight, user_weight, num_neg, lr, sampler, fuid, fiid, lookahead):
-        self.opt = FusedBPRAdagrad(item_weight, user_weight, lr=lr)
-        self.num_neg, self.sampler, self.fuid, self.fiid, self.lookahead = num_neg, sampler, fuid, fiid, lookahead
-        self.step = self.opt.step_prepared
+    optimizer = FusedBPRAdagrad

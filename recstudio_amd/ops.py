@@ -890,17 +890,18 @@ def _rows_update_args(target, query, query_index, n_queries, num_neg, dpos, dneg
     return a
 
 
-def _adam_fields(a, exp_avg, exp_avg_sq, lr, betas, eps, step, who):
-    a.exp_avg = ptr(_need(exp_avg, torch.float32, who + ': exp_avg'))
-    a.exp_avg_sq = ptr(_need(exp_avg_sq, torch.float32, who + ': exp_avg_sq'))
-    # (doubles, as the caller holds them: the library derives 1 - beta and the bias corrections from these, ABI 12)
-    a.lr, a.beta1, a.beta2, a.eps, a.step = float(lr), float(betas[0]), float(betas[1]), float(eps), int(step)
-
-
-def _adagrad_fields(a, state_sum, lr, lr_decay, eps, step, who):
-    a.rule, a.state_sum = nat.ROWS_ADAGRAD, ptr(_need(state_sum, torch.float32, who + ': state_sum'))
-    # (doubles: the library takes clr = lr / (1 + (step - 1) lr_decay) from these and rounds it to fp32 once)
-    a.lr, a.lr_decay, a.eps, a.step = float(lr), float(lr_decay), float(eps), int(step)
+def _rule_fields(a, rule, who):
+    """``rule``: ('adam', exp_avg, exp_avg_sq, lr, betas, eps, step) or ('adagrad', state_sum, lr, lr_decay, eps, step) -> its fields of
+    the block.  Doubles, as the caller holds them: the library derives 1 - beta and the bias corrections (ABI 12), or clr = lr /
+    (1 + (step - 1) lr_decay), from these and rounds each kernel constant to fp32 once."""
+    kind, *state, lr, hp, eps, step = rule
+    if kind == 'adam':
+        a.exp_avg = ptr(_need(state[0], torch.float32, who + ': exp_avg'))
+        a.exp_avg_sq = ptr(_need(state[1], torch.float32, who + ': exp_avg_sq'))
+        a.beta1, a.beta2 = float(hp[0]), float(hp[1])
+    else:
+        a.rule, a.state_sum, a.lr_decay = nat.ROWS_ADAGRAD, ptr(_need(state[0], torch.float32, who + ': state_sum')), float(hp)
+    a.lr, a.eps, a.step = float(lr), float(eps), int(step)
 
 
 @_on_device
@@ -925,14 +926,14 @@ def sort_step_elements(pos_ids, neg_ids, n_items, pad_row=0, want_solo=True):
     return solo, ws
 
 
-def _rows_update(who, target, query, dneg, *, neg_ids=None, workspace=None, n_queries=None, num_neg=None, adam=None,
-                 adagrad=None, query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
+def _rows_update(who, target, query, dneg, *, neg_ids=None, workspace=None, n_queries=None, num_neg=None, rule=None,
+                 query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
     """The one body of the rows-update wrappers.  No ``workspace``: sort + apply over ``neg_ids`` / ``pos_ids``
     (rsa_rows_update_sorted; queries and negatives per query derived here, the workspace allocated here).  ``workspace`` given:
-    the apply pass over the pairs ``sort_step_elements`` left in it (rsa_rows_update_presorted).  ``adam``: (exp_avg, exp_avg_sq,
-    lr, betas, eps, step) of the lazy-Adam form; ``adagrad``: (state_sum, lr, lr_decay, eps, step) of the Adagrad form."""
+    the apply pass over the pairs ``sort_step_elements`` left in it (rsa_rows_update_presorted).  ``rule``: the optimizer applied to
+    the touched rows (``_rule_fields``); None: plain accumulate."""
     presorted = workspace is not None
-    target = _need(target, torch.float32, 'weight' if adam or adagrad else 'target')
+    target = _need(target, torch.float32, 'weight' if rule else 'target')
     query = _need(query, torch.float32, 'query')
     neg_ids = None if presorted else _need(neg_ids, torch.int64, 'neg_ids')
     dneg = _need(dneg, torch.float32, 'dneg')
@@ -948,10 +949,8 @@ def _rows_update(who, target, query, dneg, *, neg_ids=None, workspace=None, n_qu
             return target
         n = neg_ids.numel() // M
     a = _rows_update_args(target, query, query_index, M, n, dpos, dneg, upstream, pad_row)
-    if adam:
-        _adam_fields(a, *adam, who)
-    if adagrad:
-        _adagrad_fields(a, *adagrad, who)
+    if rule:
+        _rule_fields(a, rule, who)
     if presorted:
         a.has_pos, a.workspace_bytes = int(dpos is not None), workspace.numel()
     else:
@@ -976,7 +975,7 @@ def adam_rows_sorted(weight, exp_avg, exp_avg_sq, query, neg_ids, dneg, *, lr, b
                      query_index=None, pos_ids=None, dpos=None, upstream=None, pad_row=0):
     """rsa_rows_update_sorted with the lazy-Adam state: lazy Adam (torch.optim.SparseAdam's rule) on the rows touched by the step, from the
     factored gradient (ids, coefficients, query rows) -- no gradient tensor."""
-    return _rows_update('adam_rows_sorted', weight, query, dneg, neg_ids=neg_ids, adam=(exp_avg, exp_avg_sq, lr, betas, eps, step),
+    return _rows_update('adam_rows_sorted', weight, query, dneg, neg_ids=neg_ids, rule=('adam', exp_avg, exp_avg_sq, lr, betas, eps, step),
                         query_index=query_index, pos_ids=pos_ids, dpos=dpos, upstream=upstream, pad_row=pad_row)
 
 
@@ -995,7 +994,7 @@ def adam_rows_presorted(weight, exp_avg, exp_avg_sq, query, workspace, n_queries
     """rsa_rows_update_presorted with the lazy-Adam state: the apply pass of adam_rows_sorted over the pairs ``sort_step_elements(want_solo=False)``
     left in ``workspace``."""
     return _rows_update('adam_rows_presorted', weight, query, dneg, workspace=workspace, n_queries=n_queries, num_neg=num_neg,
-                        adam=(exp_avg, exp_avg_sq, lr, betas, eps, step), query_index=query_index, dpos=dpos, upstream=upstream,
+                        rule=('adam', exp_avg, exp_avg_sq, lr, betas, eps, step), query_index=query_index, dpos=dpos, upstream=upstream,
                         pad_row=pad_row)
 
 
@@ -1005,7 +1004,7 @@ def adagrad_rows_sorted(weight, state_sum, query, neg_ids, dneg, *, lr, lr_decay
     """rsa_rows_update_sorted with rule = RSA_ROWS_ADAGRAD: torch.optim.Adagrad's update (state_sum += g^2; weight -= lr / (1 +
     (step - 1) lr_decay) * g / (sqrt(state_sum) + eps)) on the rows touched by the step, from the factored gradient -- no gradient
     tensor.  A row outside the step has a zero gradient, which the dense rule leaves as it is: this IS torch.optim.Adagrad."""
-    return _rows_update('adagrad_rows_sorted', weight, query, dneg, neg_ids=neg_ids, adagrad=(state_sum, lr, lr_decay, eps, step),
+    return _rows_update('adagrad_rows_sorted', weight, query, dneg, neg_ids=neg_ids, rule=('adagrad', state_sum, lr, lr_decay, eps, step),
                         query_index=query_index, pos_ids=pos_ids, dpos=dpos, upstream=upstream, pad_row=pad_row)
 
 
@@ -1015,7 +1014,7 @@ def adagrad_rows_presorted(weight, state_sum, query, workspace, n_queries, num_n
     """rsa_rows_update_presorted with rule = RSA_ROWS_ADAGRAD: the apply pass of adagrad_rows_sorted over the pairs
     ``sort_step_elements(want_solo=False)`` left in ``workspace``."""
     return _rows_update('adagrad_rows_presorted', weight, query, dneg, workspace=workspace, n_queries=n_queries, num_neg=num_neg,
-                        adagrad=(state_sum, lr, lr_decay, eps, step), query_index=query_index, dpos=dpos, upstream=upstream,
+                        rule=('adagrad', state_sum, lr, lr_decay, eps, step), query_index=query_index, dpos=dpos, upstream=upstream,
                         pad_row=pad_row)
 
 
