@@ -299,11 +299,24 @@ def _two_rank_worker(rank, world, port, backend, result_dir, layout='block'):
         with torch.no_grad():
             tower.weight.copy_(user)
         tbl = ShardedItemTable(plan.take(item_d, rank).contiguous().clone(), plan, rank, comm)
-        trainer = ShardedRetriever(tbl, tower, ra.UniformSampler(N), ra.BPRLoss(), 64, item_sgd_lr=0.5, sparse_query_rows=True)
+        trainer = ShardedRetriever(tbl, tower, ra.UniformSampler(N), ra.BPRLoss(), 64, item_sgd_lr=0.5, sparse_query_rows=True,
+                                   keep_neg_ids=True)
         assert trainer._fused_loss_kind() == 'bpr'           # loss + routed-order gradient inside the home kernel
         l0 = trainer.training_step(uid, pos)
         tot = sum_cpu(l0.detach().reshape(1))
         assert abs(float(tot) - 0.6931) < 0.05 and tower.weight.grad is None       # nn.Embedding tower: row-sparse gradient
+        # the step against float64 on the FULL table: loss_func.py:55-59 over both ranks' queries, the dense item gradient
+        # (padding row dropped), in-place SGD at rate 0.5
+        uid_a, pos_a, neg_a = (torch.cat(gather_cpu(t)) for t in (uid, pos, trainer.last_neg))
+        w64, q64 = item.double(), user.cpu().double()[uid_a]
+        x64 = (q64.unsqueeze(1) * w64[neg_a]).sum(-1) - (q64 * w64[pos_a]).sum(-1, keepdim=True)
+        dneg64 = torch.sigmoid(x64) / x64.numel()
+        grad64 = torch.zeros_like(w64)
+        grad64.index_add_(0, pos_a, -dneg64.sum(1, keepdim=True) * q64)
+        grad64.index_add_(0, neg_a.reshape(-1), (dneg64.unsqueeze(-1) * q64.unsqueeze(1)).reshape(-1, d))
+        grad64[0] = 0
+        np.testing.assert_allclose(float(tot), float(torch.nn.functional.softplus(x64).mean()), rtol=1e-5)
+        np.testing.assert_allclose(tbl.item_local.cpu(), plan.take(w64 - 0.5 * grad64, rank), rtol=2e-4, atol=1e-7)
         ids_all, rows_all = trainer.query_rows
         assert ids_all.shape == (world * B,) and rows_all.shape == (world * B, d) and torch.isfinite(rows_all).all()
         assert torch.equal(ids_all[rank * B:(rank + 1) * B], uid)
