@@ -896,6 +896,65 @@ typedef struct rsa_graph_dropout_args {
 } rsa_graph_dropout_args;
 int rsa_graph_dropout(const rsa_graph_dropout_args* args, rsa_stream_t stream);
 
+/* NGCF's BiCombiner layer with the normalise of the layer loop, fused (recstudio/model/module/graphmodule.py:70-86,
+ * recstudio/model/graph/ngcf.py:63-86).  x = the layer's input, m = the aggregated neighbours, both fp32 [n_rows, d_in]:
+ *   s = LeakyReLU((x + m) W1^T + b1),  p = LeakyReLU((x * m) W2^T + b2)      W1, W2 fp32 [d_out, d_in] (nn.Linear), b fp32 [d_out]
+ *   h = dropout(s + p)                                                        fp32 [n_rows, d_out], contiguous (nullable)
+ *   n = h / max(||h||_2, 1e-12)                                               written to columns [n_col, n_col + d_out) of a table
+ *                                                                             whose rows are n_stride floats apart (nullable)
+ * fp32 throughout, both products on the fp32 matrix cores; one launch.  d_in and d_out are multiples of 4, at most 128 each
+ * (both weight matrices are kept in LDS).
+ * THE DROPOUT.  q = (float)(1.0 - p).  Element (r, c) is kept iff u[r * d_out + c] < q and is then divided by q; u = element
+ * elem_base + r * d_out + c of ONE torch.rand call over n_rows * d_out outputs ("Philox state"), bit-equal to torch.rand_like of
+ * an [n_rows, d_out] tensor as long as torch draws that tensor in one call (it splits a tensor of several GiB into calls with
+ * states of their own; the element index here is 64-bit).  p == 0 reads no Philox state and draws nothing.  This is NOT the
+ * stream nn.Dropout's own kernel consumes.
+ * rsa_bi_combine_backward takes the same inputs and state, recomputes the pre-activations and the mask (nothing is saved), and
+ * writes dx, dm [n_rows, d_in], dw1, dw2 [d_out, d_in], db1, db2 [d_out] from g_h (the gradient arriving at h, nullable) and g_n
+ * (the gradient of the column block, in the same strided form as n, nullable).  The sums over the rows are per-wave partials in
+ * `workspace` (rsa_bi_combine_workspace_bytes) added in a fixed order by a last launch: no atomics, two runs are bit-equal.
+ * Three launches.
+ * A bad d_in / d_out / p / Philox state, a null or misaligned pointer (x, m, w1, w2, h, g_h and the column blocks: 16 bytes; strides
+ * and column offsets multiples of 4), neither h nor n (forward), neither g_h nor g_n (backward), a workspace that is too small:
+ * RSA_ERR_ARG before the first HIP call.  n_rows == 0 returns 0 and launches nothing.  Nothing is allocated, nothing synchronises. */
+typedef struct rsa_bi_combine_args {
+  int64_t size;                /* sizeof(rsa_bi_combine_args) */
+  const float* x;              /* [n_rows, d_in] */
+  const float* m;              /* [n_rows, d_in] */
+  const float* w1;             /* [d_out, d_in] linear_sum.weight */
+  const float* w2;             /* [d_out, d_in] linear_product.weight */
+  const float* b1;             /* [d_out] */
+  const float* b2;             /* [d_out] */
+  int64_t n_rows;
+  int32_t d_in;
+  int32_t d_out;
+  float negative_slope;
+  uint32_t grid_threads;       /* "Philox state" of the torch.rand(n_rows, d_out) call the dropout stands for (p != 0) */
+  double p;                    /* dropout probability in [0, 1) */
+  uint64_t seed;
+  uint64_t offset;
+  uint64_t elem_base;
+  float* h;                    /* forward: nullable [n_rows, d_out] out */
+  float* n;                    /* forward: nullable out, base of the wider table */
+  int64_t n_stride;            /* floats between its rows */
+  int64_t n_col;               /* first column of the block */
+  const float* g_h;            /* backward: nullable [n_rows, d_out] */
+  const float* g_n;            /* backward: nullable, base of the wider gradient table */
+  int64_t g_n_stride;
+  int64_t g_n_col;
+  float* dx;                   /* backward: [n_rows, d_in] out */
+  float* dm;                   /* backward: [n_rows, d_in] out */
+  float* dw1;                  /* backward: [d_out, d_in] out */
+  float* dw2;
+  float* db1;                  /* backward: [d_out] out */
+  float* db2;
+  void* workspace;             /* backward */
+  int64_t workspace_bytes;     /* >= rsa_bi_combine_workspace_bytes(n_rows, d_in, d_out) */
+} rsa_bi_combine_args;
+int64_t rsa_bi_combine_workspace_bytes(int64_t n_rows, int32_t d_in, int32_t d_out);
+int rsa_bi_combine(const rsa_bi_combine_args* args, rsa_stream_t stream);
+int rsa_bi_combine_backward(const rsa_bi_combine_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

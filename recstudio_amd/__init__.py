@@ -17,7 +17,7 @@ from .loss_func import (FullScoreLoss, PairwiseLoss, PointwiseLoss, BPRLoss,   #
 from .fused import retriever_scores                               # noqa: F401
 from .dataset import TripletDataset, SeqDataset, DataSampler, SortedDataSampler   # noqa: F401
 from .retriever import (BaseRetriever, TwoTowerRecommender, ItemTowerRecommender, BPR, SASRec, LightGCN,   # noqa: F401
-                        SGL, SimGCL, default_config, seed_everything)
+                        SGL, SimGCL, NGCF, default_config, seed_everything)
 from . import graphmodule                                         # noqa: F401
 from . import data_augmentation                                   # noqa: F401
 from . import eval                                                # noqa: F401

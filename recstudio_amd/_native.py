@@ -266,6 +266,18 @@ class GraphDropoutArgs(_Sized):
     ]
 
 
+class BiCombineArgs(_Sized):
+    """struct rsa_bi_combine_args."""
+    _fields_ = [
+        ('size', c_int64), ('x', c_void_p), ('m', c_void_p), ('w1', c_void_p), ('w2', c_void_p), ('b1', c_void_p), ('b2', c_void_p),
+        ('n_rows', c_int64), ('d_in', c_int32), ('d_out', c_int32), ('negative_slope', c_float), ('grid_threads', c_uint32),
+        ('p', c_double), ('seed', c_uint64), ('offset', c_uint64), ('elem_base', c_uint64), ('h', c_void_p), ('n', c_void_p),
+        ('n_stride', c_int64), ('n_col', c_int64), ('g_h', c_void_p), ('g_n', c_void_p), ('g_n_stride', c_int64),
+        ('g_n_col', c_int64), ('dx', c_void_p), ('dm', c_void_p), ('dw1', c_void_p), ('dw2', c_void_p), ('db1', c_void_p),
+        ('db2', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -276,7 +288,7 @@ STRUCTS = {
     'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
-    'rsa_graph_dropout_args': GraphDropoutArgs,
+    'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -364,6 +376,9 @@ SIGNATURES = {
     'rsa_softmax_lookup': (c_int, [POINTER(SoftmaxSampleArgs), c_void_p]),
     'rsa_spmm_csr': (c_int, [POINTER(SpmmArgs), c_void_p]),
     'rsa_graph_dropout': (c_int, [POINTER(GraphDropoutArgs), c_void_p]),
+    'rsa_bi_combine_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
+    'rsa_bi_combine': (c_int, [POINTER(BiCombineArgs), c_void_p]),
+    'rsa_bi_combine_backward': (c_int, [POINTER(BiCombineArgs), c_void_p]),
 }
 
 _lib = None

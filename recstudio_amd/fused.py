@@ -49,7 +49,10 @@ class _ScoreFn(torch.autograd.Function):
                                 cosine=cfg.get('cosine', False), mask_pad_pos=cfg.get('mask_pad_pos', False),
                                 n_queries=cfg.get('n_queries'), **_pop_kw(cfg))
         cfg['out'] = out
-        ctx.cfg = cfg
+        # (ctx must not hold `out`: its scores become this node's outputs, and a node that holds its own outputs is a cycle
+        # through the autograd engine that the collector cannot see -- the node, and every node upstream of it, would outlive the step)
+        ctx.cfg = {k: v for k, v in cfg.items() if k != 'out'}
+        ctx.neg_shape = tuple(out['neg_score'].shape)
         ctx.save_for_backward(item_weight, query_src, out['neg_ids'])
         pos = out.get('pos_score')
         if pos is None:
@@ -65,7 +68,7 @@ class _ScoreFn(torch.autograd.Function):
         need_item = ctx.needs_input_grad[0]
         need_q = ctx.needs_input_grad[1]
         if gneg is None:
-            gneg = torch.zeros_like(cfg['out']['neg_score'])
+            gneg = torch.zeros(ctx.neg_shape, dtype=torch.float32, device=item_weight.device)
         if pos_ids is not None and (gpos is None or gpos.numel() == 0):
             gpos = torch.zeros(pos_ids.numel(), dtype=torch.float32, device=item_weight.device)
         # dense user-table gradient straight from the kernel (no [M, d] intermediate, no second launch)
@@ -149,7 +152,8 @@ class _FusedBPRFn(torch.autograd.Function):
                                 n_queries=cfg['n_queries'], want_logp=False, fused_loss=loss, want_query_grad=fwd_qgrad,
                                 pos_logp=cfg.get('pos_logp'), neg_logp=cfg.get('neg_logp'), want_scores=False, **_pop_kw(cfg))
         cfg['out'] = out
-        ctx.cfg = cfg
+        ctx.cfg = {k: v for k, v in cfg.items() if k != 'out'}         # (not `out`: it holds this node's output, see _ScoreFn)
+        ctx.query_grad = out.get('query_grad')
         ctx.fwd_qgrad = fwd_qgrad
         ctx.save_for_backward(item_weight, query_src, out['neg_ids'], out['dpos'], out['dneg'])
         return out['loss']
@@ -175,7 +179,7 @@ class _FusedBPRFn(torch.autograd.Function):
                 row_item_grad=need_item and sparse, want_query_grad=need_q and not have_q and qtab is None,
                 query_table_grad=qtab)
         if have_q:
-            qgrad = cfg['out']['query_grad'] * g
+            qgrad = ctx.query_grad * g
         g_item = g_q = None
         if need_item:
             if sparse:

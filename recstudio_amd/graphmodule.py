@@ -5,14 +5,16 @@
 (graphmodule.py:176-188, mess_norm 'both'): the normalised adjacency ``D^-1/2 A D^-1/2`` in CSR with the norms folded into the edge
 values.  ``LightGCNNet`` is graphmodule.py:190-198 with ``LightGCNCombiner`` (:89-94, the identity on the neighbour message) and
 the layer mean of lightgcn.py:56-60 in one autograd node.  ``SimGCLNet`` is recstudio/model/graph/simgcl.py:8-26: the same
-propagation with every layer output perturbed inside the kernel and a layer mean that skips the input.  ``GraphUserEncoder`` /
-``GraphItemEncoder``: graphmodule.py:97-111.
+propagation with every layer output perturbed inside the kernel and a layer mean that skips the input.  ``BiCombiner`` is graphmodule.py:70-86 as
+one fused kernel (``rsa_bi_combine``, recstudio_amd/csrc/rsa_combine.hip), ``LeftAdj`` the ``GraphConv(norm='left')`` aggregation of
+NGCF in the CSR layout of ``NormAdj``, ``NGCFNet`` graphmodule.py:201-229 over the two with the ``cat`` of ngcf.py:73 written in
+place.  ``GraphUserEncoder`` / ``GraphItemEncoder``: graphmodule.py:97-111.
 """
 import torch
 
 from . import ops, rng
 
-__all__ = ['NormAdj', 'AugmentedAdj', 'LightGCNNet', 'SimGCLNet', 'GraphUserEncoder', 'GraphItemEncoder']
+__all__ = ['NormAdj', 'AugmentedAdj', 'LightGCNNet', 'SimGCLNet', 'BiCombiner', 'LeftAdj', 'NGCFNet', 'GraphUserEncoder', 'GraphItemEncoder']
 
 
 def _csr_by(key, other, weights, n):
@@ -330,6 +332,236 @@ class SimGCLNet(torch.nn.Module):
         return _SimGCLPropagateFn.apply(embeddings, adj, self.n_layers, self.eps, calls, noise_out)
 
     forward = propagate
+
+
+class _BiCombineFn(torch.autograd.Function):
+    """The fused layer as one autograd node over ``ops.bi_combine`` / ``ops.bi_combine_backward``.  Only the inputs and the Philox
+    state of the dropout are kept: the backward recomputes the layer and regenerates the mask.  ``out`` (the wider table) is
+    written in place and returned, so that the gradient of its column block arrives here as ``g_out``."""
+
+    @staticmethod
+    def forward(ctx, x, m, w1, b1, w2, b2, out, col, slope, p, philox):
+        ctx.save_for_backward(x, m, w1, b1, w2, b2)
+        ctx.col, ctx.slope, ctx.p, ctx.philox, ctx.has_out = col, slope, p, philox, out is not None
+        h = ops.bi_combine(x.detach(), m.detach(), w1.detach(), w2.detach(), b1.detach(), b2.detach(), negative_slope=slope, p=p,
+                           philox=philox, out=out, col=col)
+        if out is None:
+            return h
+        ctx.mark_dirty(out)
+        return h, out
+
+    @staticmethod
+    def backward(ctx, g_h, g_out=None):
+        x, m, w1, b1, w2, b2 = ctx.saved_tensors
+        if g_out is not None and not g_out.is_contiguous():
+            g_out = g_out.contiguous()
+        dx, dm, dw1, dw2, db1, db2 = ops.bi_combine_backward(x, m, w1, w2, b1, b2, g_h=g_h, g_out=g_out, col=ctx.col,
+                                                            negative_slope=ctx.slope, p=ctx.p, philox=ctx.philox)
+        g_table = None
+        if ctx.has_out and g_out is not None:
+            # the block's columns were overwritten by this node: nothing flows through them to whatever wrote `out` before
+            g_table = g_out.clone()
+            g_table[:, ctx.col:ctx.col + w1.shape[0]] = 0
+        return dx, dm, dw1, db1, dw2, db2, g_table, None, None, None, None
+
+
+class BiCombiner(torch.nn.Module):
+    """recstudio/model/module/graphmodule.py:70-86 with ``act = LeakyReLU(negative_slope)`` (ngcf.py:35), as ONE kernel
+    (``ops.bi_combine``, recstudio_amd/csrc/rsa_combine.hip):
+    ``h = dropout(act(linear_sum(x + m)) + act(linear_product(x * m)))``, and with ``out`` also ``normalize(h, dim=-1)`` written
+    into columns ``[col, col + output_size)`` of ``out`` -- the layer's block of NGCF's concatenated table (ngcf.py:73).  The
+    parameters are the reference's (``linear_sum`` / ``linear_product``, so a ``state_dict`` moves between the two).
+    DEVIATION: the dropout mask is NOT ``nn.Dropout``'s.  With q = fp32(1 - dropout), element (r, c) is kept iff
+    ``torch.rand_like(h)[r, c] < q`` -- one ``torch.rand`` call on the device generator (or ``generator``), which is advanced as
+    that call would -- and divided by q; ``nn.Dropout``'s fused kernel walks the same Philox stream in another layout, so the
+    two keep different elements from one seed (the same kind of deviation as SGL's edge mask).  In eval mode, and
+    with ``dropout == 0``, nothing is drawn.  input_size and output_size: multiples of 4, at most 128."""
+
+    def __init__(self, input_size, output_size, dropout=0.0, negative_slope=0.01):
+        super().__init__()
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f'BiCombiner: dropout must lie in [0, 1), got {dropout}')
+        for name, d in (('input_size', input_size), ('output_size', output_size)):
+            if int(d) % 4 or not 4 <= int(d) <= ops.BI_COMBINE_MAX_DIM:
+                raise ValueError(f'BiCombiner: {name} must be a multiple of 4 in [4, {ops.BI_COMBINE_MAX_DIM}] '
+                                 f'(the fused layer keeps both weight matrices in LDS), got {d}')
+        self.input_size, self.output_size = int(input_size), int(output_size)
+        self.dropout, self.negative_slope = float(dropout), float(negative_slope)
+        self.linear_sum = torch.nn.Linear(self.input_size, self.output_size)
+        self.linear_product = torch.nn.Linear(self.input_size, self.output_size)
+
+    def _p(self):
+        return self.dropout if self.training else 0.0
+
+    def forward(self, x, m, out=None, col=0, generator=None):
+        """``x``, ``m`` fp32 [N, input_size] on the GPU -> ``h`` [N, output_size]; with ``out`` -> ``(h, out)``, ``out`` being the
+        table whose columns ``[col, col + output_size)`` now hold ``normalize(h)`` (written in place)."""
+        if not x.is_cuda:
+            raise RuntimeError('BiCombiner: recstudio_amd runs on the GPU only; there is no CPU fallback (forward_torch is the twin)')
+        p = self._p()
+        philox = rng.reserve(x.shape[0] * self.output_size, 4, x.device, generator) if p != 0.0 and x.shape[0] else None
+        if philox is None:
+            p = 0.0
+        return _BiCombineFn.apply(x, m, self.linear_sum.weight, self.linear_sum.bias, self.linear_product.weight,
+                                  self.linear_product.bias, out, int(col), self.negative_slope, p, philox)
+
+    def forward_torch(self, x, m, generator=None):
+        """The same layer in plain torch ops with the same mask rule -> ``(h, normalize(h))``: the twin for tests and timings."""
+        act = torch.nn.functional.leaky_relu
+        h = act(self.linear_sum(x + m), self.negative_slope) + act(self.linear_product(x * m), self.negative_slope)
+        p = self._p()
+        if p != 0.0:
+            q = torch.tensor(1.0 - p, dtype=torch.float32, device=h.device)
+            u = torch.rand(h.shape, dtype=torch.float32, device=h.device, generator=generator)
+            h = torch.where(u < q, h / q, torch.zeros_like(h))
+        return h, torch.nn.functional.normalize(h, dim=-1)
+
+
+class LeftAdj:
+    """The aggregation matrix of NGCF over a symmetric ``NormAdj`` ``base``: dgl's ``GraphConv(norm='left')`` --
+    ``m[dst] = sum over the kept edges src -> dst of x[src] / max(out_deg(src), 1)``, the out-degree counted over the kept edges.
+    In the base's CSR layout (rows = destinations) that is ``values[e] = keep[e] * inv_out[indices[e]]`` with ``inv_out`` fp32 [n]
+    = 1 / max(out_deg, 1) taken in float64 and rounded once.  The transposed product of the backward is
+    ``dX = inv_out * (K^T dm)``: the kept-edge mask of the reverse edges ``t_keep[e] = keep[rev[e]]`` as the values and
+    ``inv_out`` as the ``row_scale`` of ``ops.spmm_csr`` (``t_keep`` None: every edge kept).  ``LeftAdj(base)`` is the full graph
+    (built once); ``LeftAdj.thinned`` draws a view per step."""
+
+    def __init__(self, base, values=None, t_keep=None, inv_out=None, keep=None, out_deg=None):
+        if not base.symmetric:
+            raise ValueError('LeftAdj: the base graph must be symmetric (every edge has its reverse edge)')
+        self.base, self.n_nodes, self.nnz = base, base.n_nodes, base.nnz
+        if values is None:
+            inv_out = (1.0 / base.out_deg.clamp_min(1).double()).to(torch.float32).to(base.indptr.device)
+            values = inv_out[base.indices.long()]
+        self.values, self.t_keep, self.inv_out, self.keep, self.out_deg = values, t_keep, inv_out, keep, out_deg
+
+    @classmethod
+    def thinned(cls, base, keep_prob, generator=None):
+        """Every edge kept with probability ``keep_prob`` by ``ops.graph_dropout`` (one ``torch.rand(nnz)`` on the device
+        generator; the two directions of an interaction fall separately, as dgl's DropEdge on the bidirectional graph); the
+        degrees are those of the thinned graph.  The per-edge values are formed with torch ops: one pass over [nnz]."""
+        if not base.indptr.is_cuda:
+            raise RuntimeError('LeftAdj.thinned: move the graph to the GPU first (to(device)); there is no CPU fallback')
+        long_row = min(max(base.chunk, 128), ops.GRAPH_DROPOUT_LONG_ROW)
+        _, t_values, _, out_deg, keep = ops.graph_dropout(base.indptr, base.indices, base.rev, keep_prob, generator=generator,
+                                                          want_keep=True, long_row=long_row)
+        inv_out = (1.0 / out_deg.clamp_min(1).double()).to(torch.float32)
+        values = keep.to(torch.float32) * inv_out[base.indices.long()]
+        return cls(base, values, (t_values != 0).to(torch.float32), inv_out, keep, out_deg)
+
+    def to(self, device):
+        device = torch.device(device)
+        if self.t_keep is not None:
+            mine = self.values.device
+            if device.type != mine.type or (device.index is not None and device.index != mine.index):
+                raise RuntimeError('LeftAdj: a thinned view lives on the device it was drawn on')
+            return self
+        self.base.to(device)
+        if self.values.device != self.base.indptr.device:
+            self.values, self.inv_out = self.values.to(device), self.inv_out.to(device)
+        return self
+
+    def aggregate(self, x):
+        """m = A x."""
+        b = self.base
+        return ops.spmm_csr(b.indptr, b.indices, self.values, x, plan=b.plan)
+
+    def aggregate_grad(self, dm, dx):
+        """dx += A^T dm, in place, in one launch."""
+        b = self.base
+        return ops.spmm_csr(b.indptr, b.indices, self.t_keep, dm, plan=b.plan, row_scale=self.inv_out, acc=dx)
+
+
+class _NGCFFn(torch.autograd.Function):
+    """All L layers as one autograd node.  The forward keeps every layer's input and aggregated neighbours (no mask, no
+    activation); the backward runs the layers from L down to 1: layer k's ``g_h`` is what layer k + 1 left at its input, its
+    ``g_n`` is the layer's column block of the output gradient, read in place."""
+
+    @staticmethod
+    def forward(ctx, x0, adj, cfgs, *params):
+        N, widths = x0.shape[0], [x0.shape[1]] + [c[0] for c in cfgs]
+        table = torch.empty(N, sum(widths), dtype=torch.float32, device=x0.device)
+        x = x0.detach().contiguous()
+        table[:, :widths[0]] = x
+        saved, col = [], widths[0]
+        for k, (d_out, slope, p, philox) in enumerate(cfgs):
+            w1, b1, w2, b2 = (t.detach() for t in params[4 * k:4 * k + 4])
+            m = adj.aggregate(x)
+            saved += [x, m]
+            x = ops.bi_combine(x, m, w1, w2, b1, b2, negative_slope=slope, p=p, philox=philox, want_h=k + 1 < len(cfgs),
+                               out=table, col=col)
+            col += d_out
+        ctx.adj, ctx.cfgs, ctx.widths = adj, cfgs, widths
+        ctx.save_for_backward(*saved, *params)
+        return table
+
+    @staticmethod
+    def backward(ctx, g_table):
+        L = len(ctx.cfgs)
+        saved, params = ctx.saved_tensors[:2 * L], ctx.saved_tensors[2 * L:]
+        g_table = g_table.contiguous()
+        grads, g_h, col = [None] * (4 * L), None, sum(ctx.widths)
+        for k in range(L - 1, -1, -1):
+            d_out, slope, p, philox = ctx.cfgs[k]
+            col -= d_out
+            w1, b1, w2, b2 = (t.detach() for t in params[4 * k:4 * k + 4])
+            dx, dm, dw1, dw2, db1, db2 = ops.bi_combine_backward(saved[2 * k], saved[2 * k + 1], w1, w2, b1, b2, g_h=g_h, g_out=g_table,
+                                                                col=col, negative_slope=slope, p=p, philox=philox)
+            grads[4 * k:4 * k + 4] = [dw1, db1, dw2, db2]
+            g_h = ctx.adj.aggregate_grad(dm, dx)
+        g_x0 = g_h + g_table[:, :ctx.widths[0]]                       # (block 0 is x_0 itself; L >= 1, so g_h is layer 1's)
+        return (g_x0, None, None, *grads)
+
+
+class NGCFNet(torch.nn.Module):
+    """recstudio/model/module/graphmodule.py:201-229 (``LightGCNNet_dglnn`` with ``normalize=2``, ``mess_norm='left'``) over
+    ``BiCombiner`` layers, with the concatenation of ngcf.py:73 written in place: layer k aggregates ``m = A x`` (``LeftAdj``,
+    one ``ops.spmm_csr``), then the fused combiner produces the next input ``x <- h`` (unnormalised) and writes ``normalize(h)``
+    into its column block of the result ``cat(x_0, n_1, ..., n_L)``.  In training mode layer k's dropout draws the k-th of L
+    consecutive ``torch.rand`` calls on the device generator (``BiCombiner``'s mask rule); in eval mode nothing is drawn."""
+
+    def __init__(self, combiners, n_layers=None):
+        super().__init__()
+        self.combiners = combiners if isinstance(combiners, torch.nn.ModuleList) else torch.nn.ModuleList(combiners)
+        self.n_layers = len(self.combiners) if n_layers is None else int(n_layers)
+        if self.n_layers != len(self.combiners) or self.n_layers < 1:
+            raise ValueError(f'NGCFNet: {len(self.combiners)} combiners for {n_layers} layers (at least one)')
+        for a, b in zip(self.combiners[:-1], self.combiners[1:]):
+            if a.output_size != b.input_size:
+                raise ValueError('NGCFNet: a layer\'s output_size must be the next layer\'s input_size')
+        self.out_dim = self.combiners[0].input_size + sum(c.output_size for c in self.combiners)
+
+    def propagate(self, adj, embeddings, generator=None):
+        if not isinstance(adj, LeftAdj):
+            raise TypeError('NGCFNet: adj must be a LeftAdj (LeftAdj(base) or LeftAdj.thinned(base, keep_prob))')
+        if not embeddings.is_cuda:
+            raise RuntimeError('NGCFNet: recstudio_amd runs on the GPU only; there is no CPU fallback')
+        if tuple(embeddings.shape) != (adj.n_nodes, self.combiners[0].input_size):
+            raise ValueError(f'NGCFNet: embeddings must be [{adj.n_nodes}, {self.combiners[0].input_size}], got {tuple(embeddings.shape)}')
+        adj.to(embeddings.device)
+        cfgs, params = [], []
+        for c in self.combiners:
+            p = c.dropout if self.training else 0.0
+            philox = rng.reserve(adj.n_nodes * c.output_size, 4, embeddings.device, generator) if p != 0.0 else None
+            cfgs.append((c.output_size, c.negative_slope, p, philox))
+            params += [c.linear_sum.weight, c.linear_sum.bias, c.linear_product.weight, c.linear_product.bias]
+        return _NGCFFn.apply(embeddings, adj, tuple(cfgs), *params)
+
+    forward = propagate
+
+    def propagate_torch(self, adj, embeddings, generator=None):
+        """The same table from ``torch.sparse.mm`` and ``BiCombiner.forward_torch``, same masks from the same generator state:
+        the twin for tests and timings."""
+        b = adj.base
+        A = torch.sparse_csr_tensor(b.indptr, b.indices.long(), adj.values, size=(adj.n_nodes, adj.n_nodes))
+        x, blocks = embeddings, [embeddings]
+        for c in self.combiners:
+            train = c.training
+            c.train(self.training)
+            x, n = c.forward_torch(x, torch.sparse.mm(A, x), generator=generator)
+            c.train(train)
+            blocks.append(n)
+        return torch.cat(blocks, dim=1)
 
 
 class GraphItemEncoder(torch.nn.Module):

@@ -1542,3 +1542,102 @@ def graph_dropout(indptr, indices, rev, keep_prob, *, node_drop=None, generator=
         a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
     _launch('rsa_graph_dropout', ctypes.byref(a))
     return (values, t_values, in_deg, out_deg) + ((keep,) if want_keep else ())
+
+
+# ------------------------------------------------------------------ NGCF's BiCombiner layer
+BI_COMBINE_MAX_DIM = 128          # both weight matrices are kept in LDS (rsa_combine.hip, "WEIGHTS IN LDS")
+
+
+def _bi_combine_args(who, x, m, w1, w2, b1, b2, negative_slope, p, philox):
+    x, m = _need(x, torch.float32, 'x'), _need(m, torch.float32, 'm')
+    w1, w2 = _need(w1, torch.float32, 'w1'), _need(w2, torch.float32, 'w2')
+    b1, b2 = _need(b1, torch.float32, 'b1'), _need(b2, torch.float32, 'b2')
+    if x.dim() != 2 or m.shape != x.shape:
+        raise ValueError(f'{who}: x and m must be [N, d_in] tensors of one shape, got {tuple(x.shape)} and {tuple(m.shape)}')
+    N, d_in = x.shape
+    if w1.dim() != 2 or w1.shape[1] != d_in or w2.shape != w1.shape:
+        raise ValueError(f'{who}: w1 and w2 must be [d_out, {d_in}] (nn.Linear layout), got {tuple(w1.shape)} and {tuple(w2.shape)}')
+    d_out = w1.shape[0]
+    if tuple(b1.shape) != (d_out,) or tuple(b2.shape) != (d_out,):
+        raise ValueError(f'{who}: b1 and b2 must be [{d_out}]')
+    for name, d in (('d_in', d_in), ('d_out', d_out)):
+        if d % 4 or not 4 <= d <= BI_COMBINE_MAX_DIM:
+            raise ValueError(f'{who}: {name} must be a multiple of 4 in [4, {BI_COMBINE_MAX_DIM}] (the weights are kept in LDS), got {d}')
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'{who}: the dropout probability must lie in [0, 1), got {p}')
+    a = nat.BiCombineArgs()
+    a.x, a.m, a.w1, a.w2, a.b1, a.b2 = ptr(x), ptr(m), ptr(w1), ptr(w2), ptr(b1), ptr(b2)
+    a.n_rows, a.d_in, a.d_out, a.negative_slope, a.p = N, d_in, d_out, float(negative_slope), p
+    if p != 0.0:
+        if not isinstance(philox, rng.PhiloxCall):
+            raise TypeError(f'{who}: dropout needs philox, a rng.PhiloxCall (rng.reserve(N * d_out, 4, device))')
+        a.seed, a.offset, a.grid_threads, a.elem_base = philox.seed, philox.offset, philox.grid_threads, philox.elem_base
+    elif philox is not None:
+        raise ValueError(f'{who}: philox without dropout (p = 0 draws nothing)')
+    return a, (x, m, w1, w2, b1, b2), N, d_in, d_out
+
+
+def _column_block(who, name, table, col, N, d_out):
+    """(table, row stride, col) of the [N, d_out] block at column ``col`` of the wider fp32 table ``table``."""
+    _need_view(table, torch.float32, name)
+    col = int(col)
+    if table.dim() != 2 or table.shape[0] != N or table.stride(1) != 1 or table.stride(0) % 4 or col % 4 or col < 0 \
+            or col + d_out > table.shape[1] or table.data_ptr() % 16:
+        raise ValueError(f'{who}: {name} must be a 16-byte aligned [{N}, >= col + {d_out}] table with unit column stride and a row '
+                         f'stride and column offset that are multiples of 4 (got {tuple(table.shape)}, strides {table.stride()}, col {col})')
+    return table, table.stride(0), col
+
+
+@_on_device
+def bi_combine(x, m, w1, w2, b1, b2, *, negative_slope=0.01, p=0.0, philox=None, want_h=True, out=None, col=0):
+    """rsa_bi_combine: NGCF's BiCombiner layer in one launch.  ``x``, ``m`` fp32 [N, d_in]; ``w1``, ``w2`` fp32 [d_out, d_in]
+    (``nn.Linear`` layout), ``b1``, ``b2`` fp32 [d_out]; d_in, d_out multiples of 4, at most 128.
+    ``h = dropout(LeakyReLU((x + m) w1^T + b1) + LeakyReLU((x * m) w2^T + b2))`` -> fp32 [N, d_out] (``want_h``), and
+    ``h / max(||h||_2, 1e-12)`` into columns ``[col, col + d_out)`` of the wider table ``out`` (fp32 [N, >= col + d_out]) when it is
+    given; the other columns of ``out`` are not touched.  -> ``h`` (None without ``want_h``).
+    Dropout with probability ``p``: with q = fp32(1 - p), element (r, c) is kept iff ``u[r, c] < q`` and divided by q, ``u`` =
+    ``torch.rand(N, d_out)`` in the generator state ``philox`` (``rng.reserve(N * d_out, 4, device)``) was reserved in -- bit-equal
+    to ``torch.rand_like(h)`` as long as torch draws ``h`` in one call (it splits a tensor of several GiB; the element index here
+    is 64-bit).  ``p == 0`` takes no ``philox``."""
+    a, keep, N, d_in, d_out = _bi_combine_args('bi_combine', x, m, w1, w2, b1, b2, negative_slope, p, philox)
+    if not want_h and out is None:
+        raise ValueError('bi_combine: neither h nor a table for the normalised block was asked for')
+    h = torch.empty(N, d_out, dtype=torch.float32, device=keep[0].device) if want_h else None
+    a.h = ptr(h)
+    if out is not None:
+        out, a.n_stride, a.n_col = _column_block('bi_combine', 'out', out, col, N, d_out)
+        a.n = ptr(out)
+    _launch('rsa_bi_combine', ctypes.byref(a))
+    return h
+
+
+@_on_device
+def bi_combine_backward(x, m, w1, w2, b1, b2, *, g_h=None, g_out=None, col=0, negative_slope=0.01, p=0.0, philox=None):
+    """rsa_bi_combine_backward: the gradients of ``bi_combine`` from ``g_h`` (fp32 [N, d_out], the gradient arriving at ``h``)
+    and / or ``g_out`` (the gradient of the wider table; its columns ``[col, col + d_out)`` are the gradient of the normalised
+    block).  The layer is recomputed from ``x``, ``m`` and the mask regenerated from ``philox`` (the state the forward was given):
+    nothing the forward produced is read.  -> ``(dx, dm, dw1, dw2, db1, db2)``.  No atomics; bit-equal from run to run."""
+    a, keep, N, d_in, d_out = _bi_combine_args('bi_combine_backward', x, m, w1, w2, b1, b2, negative_slope, p, philox)
+    if g_h is None and g_out is None:
+        raise ValueError('bi_combine_backward: neither g_h nor g_out is given')
+    dev = keep[0].device
+    if g_h is not None:
+        g_h = _need(g_h, torch.float32, 'g_h')
+        if tuple(g_h.shape) != (N, d_out):
+            raise ValueError(f'bi_combine_backward: g_h must be [{N}, {d_out}]')
+        a.g_h = ptr(g_h)
+    if g_out is not None:
+        g_out, a.g_n_stride, a.g_n_col = _column_block('bi_combine_backward', 'g_out', g_out, col, N, d_out)
+        a.g_n = ptr(g_out)
+    dx, dm = torch.empty(N, d_in, dtype=torch.float32, device=dev), torch.empty(N, d_in, dtype=torch.float32, device=dev)
+    if N == 0:
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
+        return dx, dm, z(d_out, d_in), z(d_out, d_in), z(d_out), z(d_out)
+    dw = torch.empty(2, d_out, d_in, dtype=torch.float32, device=dev)
+    db = torch.empty(2, d_out, dtype=torch.float32, device=dev)
+    ws, a.workspace_bytes = _workspace(dev, 'rsa_bi_combine_workspace_bytes', N, d_in, d_out)
+    a.workspace = ptr(ws)
+    a.dx, a.dm, a.dw1, a.dw2, a.db1, a.db2 = ptr(dx), ptr(dm), ptr(dw[0]), ptr(dw[1]), ptr(db[0]), ptr(db[1])
+    _launch('rsa_bi_combine_backward', ctypes.byref(a))
+    return dx, dm, dw[0], dw[1], db[0], db[1]

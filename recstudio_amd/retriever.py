@@ -1334,6 +1334,74 @@ class SimGCL(LightGCN):
         return loss + cl_output['cl_loss']
 
 
+class NGCF(LightGCN):
+    """recstudio/model/graph/ngcf.py:14-96, recstudio/model/graph/config/ngcf.yaml (layer_size [64, 64, 64, 64], mess_dropout
+    [0.1, 0.1, 0.1], node_dropout 0.1 -- ``None`` switches it off --, l2_reg_weight 1e-5, batch_size 2048, learning_rate 1e-4,
+    negative_count 1).  The base tables are propagated by ``graphmodule.NGCFNet``: per layer one ``rsa_spmm_csr`` over the
+    left-normalised graph (``graphmodule.LeftAdj``) and one fused ``BiCombiner`` (``rsa_bi_combine``); the result is
+    ``cat(x_0, normalize(h_1), ..., normalize(h_L))``, sum(layer_size) wide (at most 256, the widest table the fused BPR tail and
+    the MFMA top-k take), and everything behind it -- the fused forward, ``training_step`` (BPR plus the l2 regulariser of the BASE
+    rows), ``evaluate`` / ``topk`` -- is LightGCN's.  ``embed_dim`` must equal ``layer_size[0]``.  Evaluation propagates over
+    the full graph without any dropout.
+
+    The device generator of a training step is consumed in this order: the edge mask (``torch.rand(nnz)``, with ``node_dropout``),
+    then the L message-dropout calls in layer order (``torch.rand(n_nodes, layer_size[k])``), then the negatives.
+
+    Two deliberate deviations from the reference, both in WHICH elements fall, neither in how many.  (1) ``node_dropout`` is an
+    edge dropout in the reference too (``EdgeDropout`` -> ``dgl.DropEdge``); here the kept edges are defined by the device
+    ``torch.rand`` stream in CSR edge order (``rsa_graph_dropout``), as for SGL.  (2) The message dropout keeps element (r, c)
+    iff ``torch.rand_like(h)[r, c] < fp32(1 - p)`` and divides by that; ``nn.Dropout``'s kernel walks the same Philox stream in
+    another layout (``graphmodule.BiCombiner``)."""
+
+    MAX_WIDTH = 256
+
+    def __init__(self, config=None, **kwargs):
+        super().__init__(config, **kwargs)
+        model, given = self.config['model'], config or {}
+        for key, value in (('layer_size', [64, 64, 64, 64]), ('node_dropout', 0.1)):
+            model.setdefault(key, value)
+        model['n_layers'] = len(model['layer_size']) - 1
+        model.setdefault('mess_dropout', [0.1] * (len(model['layer_size']) - 1))
+        if 'l2_reg_weight' not in given.get('model', {}):
+            model['l2_reg_weight'] = 1e-5
+        for key, value in (('batch_size', 2048), ('learning_rate', 1e-4)):
+            if key not in given.get('train', {}):
+                self.config['train'][key] = value
+        layers = [int(v) for v in model['layer_size']]
+        if len(layers) < 2 or len(model['mess_dropout']) != len(layers) - 1:
+            raise ValueError(f'NGCF: layer_size {layers} needs at least one layer and one mess_dropout per layer, got '
+                             f'{model["mess_dropout"]}')
+        if self.embed_dim != layers[0]:
+            raise ValueError(f'NGCF: embed_dim ({self.embed_dim}) must equal layer_size[0] ({layers[0]})')
+        if sum(layers) > self.MAX_WIDTH:
+            raise ValueError(f'NGCF: the concatenated table is sum(layer_size) = {sum(layers)} wide; the fused BPR tail and the '
+                             f'top-k kernels take tables of at most {self.MAX_WIDTH} columns')
+        drop = model['node_dropout']
+        if drop is not None and not 0.0 <= float(drop) < 1.0:
+            raise ValueError(f'NGCF: node_dropout must be None or lie in [0, 1), got {drop}')
+
+    def _init_model(self, train_data, drop_unused_field=True):
+        from . import graphmodule
+        super()._init_model(train_data, drop_unused_field)
+        del self.LightGCNNet
+        model = self.config['model']
+        layers = [int(v) for v in model['layer_size']]
+        self.combiners = torch.nn.ModuleList(graphmodule.BiCombiner(a, b, dropout=float(p))
+                                             for a, b, p in zip(layers[:-1], layers[1:], model['mess_dropout']))
+        self.NGCFNet = graphmodule.NGCFNet(self.combiners, len(layers) - 1)
+        self.left_adj = graphmodule.LeftAdj(self.adj_mat)
+        self.last_view = None
+
+    def _propagate(self, embeddings):
+        from . import graphmodule
+        drop = self.config['model']['node_dropout']
+        adj = self.left_adj
+        if self.training and drop:
+            self.adj_mat.to(embeddings.device)
+            adj = self.last_view = graphmodule.LeftAdj.thinned(self.adj_mat, 1.0 - float(drop))
+        return self.NGCFNet.propagate(adj, embeddings)
+
+
 class _EmbedFn(torch.autograd.Function):
     """item_encoder(ids) with the HIP gather forward and the HIP row scatter-add backward."""
 
