@@ -83,6 +83,16 @@ class InfoNCELoss(torch.nn.Module):
         return torch.mean(full_lse(query, all_reps.contiguous()) - sim_ii)
 
 
+def _contrast(loss_fn, view1, view2, uid, iid):
+    """``view1`` / ``view2``: the (user table, item table) of the two propagations -> the InfoNCE of the rows ``uid`` of the
+    user tables plus that of the rows ``iid`` of the item tables, each against the whole second table (its row 0 is skipped)."""
+    from .retriever import _EmbedFn
+    # the batch rows through the gather / sorted-scatter node, not index_add
+    user_cl_loss, item_cl_loss = (loss_fn(_EmbedFn.apply(t1, idx), _EmbedFn.apply(t2, idx), all_reps=t2)
+                                  for t1, t2, idx in zip(view1, view2, (uid, iid)))
+    return user_cl_loss + item_cl_loss
+
+
 class SGLAugmentation(torch.nn.Module):
     """data_augmentation.py:403-450: two views of the graph per step (``aug_type`` 'ED' edge dropout, 'ND' node dropout, 'RW' one
     edge-dropout graph per layer), the base tables propagated through each, and InfoNCE (cosine, all nodes as negatives)
@@ -116,15 +126,10 @@ class SGLAugmentation(torch.nn.Module):
         return all_embeddings[:self.num_users], all_embeddings[self.num_users:], view
 
     def forward(self, batch, user_emb, item_emb, adj_mat, gnn_net):
-        from .retriever import _EmbedFn
-        user_all_vec1, item_all_vec1, view1 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
-        user_all_vec2, item_all_vec2, view2 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
+        *tables1, view1 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
+        *tables2, view2 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
         self.last_views = (view1, view2)
-        uid, iid = batch[self.fuid], batch[self.fiid]
-        # the batch rows through the gather / sorted-scatter node, not index_add
-        user_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(user_all_vec1, uid), _EmbedFn.apply(user_all_vec2, uid), all_reps=user_all_vec2)
-        item_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(item_all_vec1, iid), _EmbedFn.apply(item_all_vec2, iid), all_reps=item_all_vec2)
-        return {'cl_loss': user_cl_loss + item_cl_loss}
+        return {'cl_loss': _contrast(self.InfoNCELoss_fn, tables1, tables2, batch[self.fuid], batch[self.fiid])}
 
 
 class SimGCLAugmentation(torch.nn.Module):
@@ -152,13 +157,9 @@ class SimGCLAugmentation(torch.nn.Module):
         return all_embeddings[:self.num_users], all_embeddings[self.num_users:]
 
     def forward(self, batch, user_emb, item_emb, adj_mat, gnn_net):
-        from .retriever import _EmbedFn
         device = user_emb.weight.device
         u_idx = torch.unique(batch[self.fuid]).to(device)
         i_idx = torch.unique(batch[self.fiid]).to(device)
-        user_all_vec1, item_all_vec1 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
-        user_all_vec2, item_all_vec2 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
-        # the batch rows through the gather / sorted-scatter node, not index_add; all_reps is the whole table (row 0 is skipped)
-        user_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(user_all_vec1, u_idx), _EmbedFn.apply(user_all_vec2, u_idx), all_reps=user_all_vec2)
-        item_cl_loss = self.InfoNCELoss_fn(_EmbedFn.apply(item_all_vec1, i_idx), _EmbedFn.apply(item_all_vec2, i_idx), all_reps=item_all_vec2)
-        return {'cl_loss': user_cl_loss + item_cl_loss}
+        tables1 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
+        tables2 = self.get_gnn_embeddings(user_emb, item_emb, adj_mat, gnn_net)
+        return {'cl_loss': _contrast(self.InfoNCELoss_fn, tables1, tables2, u_idx, i_idx)}

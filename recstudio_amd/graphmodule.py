@@ -9,12 +9,35 @@ propagation with every layer output perturbed inside the kernel and a layer mean
 one fused kernel (``rsa_bi_combine``, recstudio_amd/csrc/rsa_combine.hip), ``LeftAdj`` the ``GraphConv(norm='left')`` aggregation of
 NGCF in the CSR layout of ``NormAdj``, ``NGCFNet`` graphmodule.py:201-229 over the two with the ``cat`` of ngcf.py:73 written in
 place.  ``GraphUserEncoder`` / ``GraphItemEncoder``: graphmodule.py:97-111.
+
+Every adjacency answers ``csr(transposed=False)`` with one ``Csr`` operand and ``_spmm`` is the one place that launches
+``ops.spmm_csr`` on it.  The layer means run on two schedules: ``_chain`` (forward over L operands, with or without the input in
+the mean; also the backward of one graph for all layers) and ``_horner`` (h <- g + B_k h from the last operand down: the backward
+of one graph per layer and of the skip-input mean).  ``_PropagateFn`` is the one autograd node over the two.  The contract
+(DESIGN 4.9): L launches forward, L backward, no memset, nothing kept for the backward but the graph.
 """
+from collections import namedtuple
+
 import torch
 
 from . import ops, rng
 
 __all__ = ['NormAdj', 'AugmentedAdj', 'LightGCNNet', 'SimGCLNet', 'BiCombiner', 'LeftAdj', 'NGCFNet', 'GraphUserEncoder', 'GraphItemEncoder']
+
+# One matrix operand of ``ops.spmm_csr``: tensors and the plan only, built on demand -- never the adjacency it came from.
+Csr = namedtuple('Csr', 'indptr indices values plan row_scale')
+
+
+def _spmm(op, x, **kw):
+    return ops.spmm_csr(op.indptr, op.indices, op.values, x, plan=op.plan, row_scale=op.row_scale, **kw)
+
+
+def _stays_put(view, device, message):
+    """A view drawn per step lives on the device it was drawn on."""
+    device, mine = torch.device(device), view.values.device
+    if device.type != mine.type or (device.index is not None and device.index != mine.index):
+        raise RuntimeError(message)
+    return view
 
 
 def _csr_by(key, other, weights, n):
@@ -112,14 +135,17 @@ class NormAdj:
             raise RuntimeError('NormAdj.augmented: move the graph to the GPU first (to(device)); there is no CPU fallback')
         if node_drop is not None:
             node_drop = torch.as_tensor(node_drop).to(self.indptr.device)
+        return AugmentedAdj(self, *self._dropout(keep_prob, node_drop, generator))
+
+    def _dropout(self, keep_prob, node_drop=None, generator=None):
+        """``ops.graph_dropout`` on this graph -> (values, t_values, in_deg, out_deg, keep)."""
         long_row = min(max(self.chunk, 128), ops.GRAPH_DROPOUT_LONG_ROW)      # (a small test chunk also shortens the rows that are shared)
-        values, t_values, in_deg, out_deg, keep = ops.graph_dropout(self.indptr, self.indices, self.rev, keep_prob, node_drop=node_drop,
-                                                                    generator=generator, want_keep=True, long_row=long_row)
-        return AugmentedAdj(self, values, t_values, in_deg, out_deg, keep)
+        return ops.graph_dropout(self.indptr, self.indices, self.rev, keep_prob, node_drop=node_drop, generator=generator,
+                                 want_keep=True, long_row=long_row)
 
     def csr(self, transposed=False):
-        return (self.t_indptr, self.t_indices, self.t_values, self.t_plan) if transposed else \
-            (self.indptr, self.indices, self.values, self.plan)
+        return Csr(self.t_indptr, self.t_indices, self.t_values, self.t_plan, None) if transposed else \
+            Csr(self.indptr, self.indices, self.values, self.plan, None)
 
 
 class AugmentedAdj:
@@ -132,87 +158,81 @@ class AugmentedAdj:
         self.values, self.t_values, self.in_deg, self.out_deg, self.keep = values, t_values, in_deg, out_deg, keep
 
     def to(self, device):
-        device, mine = torch.device(device), self.values.device
-        if device.type != mine.type or (device.index is not None and device.index != mine.index):
-            raise RuntimeError('AugmentedAdj: a view lives on the device it was drawn on')
-        return self
+        return _stays_put(self, device, 'AugmentedAdj: a view lives on the device it was drawn on')
 
     def csr(self, transposed=False):
-        return (self.base.indptr, self.base.indices, self.t_values if transposed else self.values, self.base.plan)
+        return Csr(self.base.indptr, self.base.indices, self.t_values if transposed else self.values, self.base.plan, None)
 
 
-def _layer_mean(csr, e0, n_layers):
-    """(E_0 + A E_0 + ... + A^L E_0) / (L + 1): L launches of ``ops.spmm_csr``, each adding its layer to the running sum in its
-    epilogue; the last one writes no layer output and scales the sum."""
-    indptr, indices, values, plan = csr
-    L = int(n_layers)
-    acc = e0.detach().clone(memory_format=torch.contiguous_format)
-    x, spare = e0.detach().contiguous(), [None, None]
-    for k in range(L):
-        last = k == L - 1
-        y = None
-        if not last:
-            y = spare[k % 2] = torch.empty_like(acc) if spare[k % 2] is None else spare[k % 2]
-        ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=acc, acc_scale=1.0 / (L + 1) if last else 1.0)
-        x = y
-    return acc
-
-
-def _layer_mean_each(csrs, e0):
-    """(E_0 + E_1 + ... + E_L) / (L + 1) with E_k = A_k E_{k-1}, one matrix per layer: the launches of ``_layer_mean``."""
+def _chain(csrs, e0, with_input, eps=0.0, calls=None, noise_out=None):
+    """The layer mean over the operands ``csrs`` = A_1 .. A_L, E_k = A_k E'_{k-1}, in L launches and no memset; E'_k is E_k
+    perturbed by call ``calls[k - 1]`` (or E_k without ``calls``).  Each launch adds its layer to the running sum in its epilogue;
+    the last one writes no layer output and scales the sum.
+    ``with_input``: (E_0 + E_1 + ... + E_L) / (L + 1) -- the sum starts as a copy of E_0 and every launch adds in place.
+    Without: (E'_1 + ... + E'_L) / L -- layer 1 writes its output only, layer 2 starts the sum from it (``acc`` = y_1 is read,
+    ``acc_out`` written), the later ones add in place; L = 1 is layer 1's output.
+    ``noise_out``: a list that receives the L tables of uniforms (tests)."""
     L = len(csrs)
-    acc = e0.detach().clone(memory_format=torch.contiguous_format)
     x, spare = e0.detach().contiguous(), [None, None]
-    for k, (indptr, indices, values, plan) in enumerate(csrs):
+    acc = e0.detach().clone(memory_format=torch.contiguous_format) if with_input else None
+    for k, op in enumerate(csrs):
         last = k == L - 1
+        kw = {}
+        if calls is not None:
+            kw.update(noise=calls[k], noise_eps=eps)
+            if noise_out is not None:
+                noise_out.append(torch.empty_like(x))
+                kw['noise_out'] = noise_out[-1]
         y = None
-        if not last:
-            y = spare[k % 2] = torch.empty_like(acc) if spare[k % 2] is None else spare[k % 2]
-        ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=acc, acc_scale=1.0 / (L + 1) if last else 1.0)
+        if not last or (k == 0 and not with_input):
+            y = spare[k % 2] = torch.empty_like(x) if spare[k % 2] is None else spare[k % 2]
+        scale = 1.0 / (L + 1 if with_input else L) if last else 1.0
+        if with_input or k > 1:
+            kw.update(acc=acc, acc_scale=scale)
+        elif k == 1:
+            acc = torch.empty_like(x)
+            kw.update(acc=x, acc_out=acc, acc_scale=scale)
+        _spmm(op, x, y=y, **kw)
         x = y
-    return acc
+    return x if acc is None else acc
 
 
-def _horner_mean(csrs, g):
-    """(g + B_1 (g + B_2 (g + ... B_L g))) / (L + 1) for the matrices ``csrs`` = B_1 .. B_L: h <- g + B_k h from k = L down to
-    1, each step ONE launch (``acc`` = g is read, ``acc_out`` = the new h written), the last one scaling."""
-    L = len(csrs)
+def _horner(csrs, g, scale):
+    """scale * (g + B_1 (g + B_2 (g + ... B_L g))) for the operands ``csrs`` = B_1 .. B_L: h <- g + B_k h from k = L down to 1,
+    from h = g, each step ONE launch (``acc`` = g is read, ``acc_out`` = the new h written), the last one scaling.  The matrices
+    do not commute, so the order matters.  No operands: g."""
     g = g.detach().contiguous()
-    h, spare = g, [torch.empty_like(g), torch.empty_like(g) if L > 1 else None]
-    for j, k in enumerate(range(L - 1, -1, -1)):
-        indptr, indices, values, plan = csrs[k]
-        out = spare[j % 2]
-        ops.spmm_csr(indptr, indices, values, h, plan=plan, acc=g, acc_out=out, acc_scale=1.0 / (L + 1) if k == 0 else 1.0)
+    h, spare = g, [None, None]
+    for j, op in enumerate(reversed(csrs)):
+        out = spare[j % 2] = torch.empty_like(g) if spare[j % 2] is None else spare[j % 2]
+        _spmm(op, h, acc=g, acc_out=out, acc_scale=scale if j == len(csrs) - 1 else 1.0)
         h = out
     return h
 
 
-class _PropagateEachFn(torch.autograd.Function):
-    """One matrix per layer (RandomWalkLightGCN, sgl.py:9-24): with E_k = A_k E_{k-1} the mean's gradient is
-    (g + A_1^T (g + A_2^T (g + ... A_L^T g))) / (L + 1) -- the matrices do not commute, so the recurrence runs from layer L down."""
-
-    @staticmethod
-    def forward(ctx, e0, adjs):
-        ctx.adjs = adjs
-        return _layer_mean_each([a.csr() for a in adjs], e0)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _horner_mean([a.csr(transposed=True) for a in ctx.adjs], g), None
-
-
 class _PropagateFn(torch.autograd.Function):
-    """The layers are linear, so no layer output is kept: the backward is the same L launches, with the transposed matrix, on
-    the incoming gradient -- dE_0 = 1 / (L + 1) * sum_k (A^T)^k g."""
+    """The layer mean over the graphs ``adjs`` (one per layer) as one autograd node.  The layers are linear -- a perturbed layer
+    too: sign has derivative zero and the uniforms do not depend on the input, so E'_k = A E'_{k-1} + const -- and nothing but the
+    graphs is kept for the backward, which is L launches over the transposed operands B_k = A_k^T on the incoming gradient:
+      with the input, one graph for all layers:  1 / (L + 1) * sum_{k = 0 .. L} B^k g, the forward's own schedule;
+      with the input, one graph per layer (RandomWalkLightGCN, sgl.py:9-24):  (g + B_1 (g + B_2 (g + ... B_L g))) / (L + 1);
+      without the input:  1 / L * sum_{k = 1 .. L} B^k g = B_1 (g + B_2 (g + ... B_L g)) / L."""
 
     @staticmethod
-    def forward(ctx, e0, adj, n_layers):
-        ctx.adj, ctx.n_layers = adj, n_layers
-        return _layer_mean(adj.csr(), e0, n_layers)
+    def forward(ctx, e0, adjs, with_input, eps, calls, noise_out):
+        ctx.adjs, ctx.with_input = adjs, with_input
+        return _chain([a.csr() for a in adjs], e0, with_input, eps, calls, noise_out)
 
     @staticmethod
     def backward(ctx, g):
-        return _layer_mean(ctx.adj.csr(transposed=True), g, ctx.n_layers), None, None
+        csrs, L = [a.csr(transposed=True) for a in ctx.adjs], len(ctx.adjs)
+        if not ctx.with_input:
+            dx = _spmm(csrs[0], _horner(csrs[1:], g, 1.0 / L))
+        elif all(a is ctx.adjs[0] for a in ctx.adjs):
+            dx = _chain(csrs, g, True)
+        else:
+            dx = _horner(csrs, g, 1.0 / (L + 1))
+        return dx, None, None, None, None, None
 
 
 class LightGCNNet(torch.nn.Module):
@@ -234,76 +254,16 @@ class LightGCNNet(torch.nn.Module):
             a.to(embeddings.device)
         if self.n_layers == 0:
             return embeddings
-        if each and any(a is not adj[0] for a in adj):
-            return _PropagateEachFn.apply(embeddings, tuple(adj))
-        return _PropagateFn.apply(embeddings, adj[0] if each else adj, self.n_layers)
+        return _PropagateFn.apply(embeddings, tuple(adj) if each else (adj,) * self.n_layers, True, 0.0, None, None)
 
     forward = propagate
-
-
-def _skip_input_mean(csr, e0, n_layers, eps=0.0, calls=None, noise_out=None):
-    """(E'_1 + ... + E'_L) / L with E_k = A E'_{k-1}, E'_0 = E_0 and E'_k = E_k perturbed by call ``calls[k - 1]`` (or E_k without
-    ``calls``): L launches of ``ops.spmm_csr`` and no memset -- layer 1 writes its output only, layer 2 starts the running sum from
-    layer 1's output (``acc`` = y_1 is read, ``acc_out`` written), the later ones add in place, the last one scales by 1 / L and
-    writes no layer output.  ``noise_out``: a list that receives the L tables of uniforms (tests)."""
-    indptr, indices, values, plan = csr
-    L = int(n_layers)
-    x, spare, acc = e0.detach().contiguous(), [None, None], None
-    for k in range(L):
-        last = k == L - 1
-        noise = {}
-        if calls is not None:
-            noise = {'noise': calls[k], 'noise_eps': eps}
-            if noise_out is not None:
-                noise_out.append(torch.empty_like(x))
-                noise['noise_out'] = noise_out[-1]
-        y = None
-        if not last or k == 0:
-            y = spare[k % 2] = torch.empty_like(x) if spare[k % 2] is None else spare[k % 2]
-        if k == 0:
-            ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, **noise)
-        elif k == 1:
-            acc = torch.empty_like(x)
-            ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=x, acc_out=acc, acc_scale=1.0 / L if last else 1.0, **noise)
-        else:
-            ops.spmm_csr(indptr, indices, values, x, plan=plan, y=y, acc=acc, acc_scale=1.0 / L if last else 1.0, **noise)
-        x = y
-    return x if L == 1 else acc
-
-
-def _skip_input_mean_grad(csr_t, g, n_layers):
-    """(A^T g + ... + (A^T)^L g) / L for the transposed matrix ``csr_t``: h <- g + A^T h, L - 1 times from h = g (one launch each,
-    ``acc`` = g read, ``acc_out`` = the new h written, the last one scaling by 1 / L), then one launch A^T h."""
-    indptr, indices, values, plan = csr_t
-    L = int(n_layers)
-    g = g.detach().contiguous()
-    h, spare = g, [None, None]
-    for j in range(L - 1):
-        out = spare[j % 2] = torch.empty_like(g) if spare[j % 2] is None else spare[j % 2]
-        ops.spmm_csr(indptr, indices, values, h, plan=plan, acc=g, acc_out=out, acc_scale=1.0 / L if j == L - 2 else 1.0)
-        h = out
-    return ops.spmm_csr(indptr, indices, values, h, plan=plan)
-
-
-class _SimGCLPropagateFn(torch.autograd.Function):
-    """sign has derivative zero and the uniforms do not depend on the input, so a perturbed layer is E'_k = A E'_{k-1} + const:
-    perturbed or not, dE_0 = 1 / L * sum_{k = 1 .. L} (A^T)^k g, and nothing but the graph is kept for the backward."""
-
-    @staticmethod
-    def forward(ctx, e0, adj, n_layers, eps, calls, noise_out):
-        ctx.adj, ctx.n_layers = adj, n_layers
-        return _skip_input_mean(adj.csr(), e0, n_layers, eps, calls, noise_out)
-
-    @staticmethod
-    def backward(ctx, g):
-        return _skip_input_mean_grad(ctx.adj.csr(transposed=True), g, ctx.n_layers), None, None, None, None, None
 
 
 class SimGCLNet(torch.nn.Module):
     """recstudio/model/graph/simgcl.py:8-26 with the layer mean of :77-81 in one autograd node: E_k = A E'_{k-1} and, when
     ``perturbed``, E'_k = E_k + sign(E_k) * normalize(rand_like(E_k), dim=-1) * eps; the result is mean(E'_1 .. E'_L) -- the
     input E_0 is NOT part of the mean, unlike LightGCN's.  The noise is added in the epilogue of the propagation kernel
-    (``ops.spmm_csr(noise=...)``) from the device generator's stream: layer k draws what the k-th of L consecutive
+    (the ``noise`` of ``ops.spmm_csr``) from the device generator's stream: layer k draws what the k-th of L consecutive
     ``torch.rand_like(E)`` calls would (bit-equal while ``n_nodes * d < 2**31``), and the generator is advanced by those L calls."""
 
     def __init__(self, n_layers, eps):
@@ -329,7 +289,7 @@ class SimGCLNet(torch.nn.Module):
             if self.eps != 0.0:          # (eps 0 still consumes the stream of the L rand_like calls, as the reference does)
                 calls = [rng.PhiloxCall(first.seed, first.offset + k * step, first.grid_threads, first.elem_base)
                          for k in range(self.n_layers)]
-        return _SimGCLPropagateFn.apply(embeddings, adj, self.n_layers, self.eps, calls, noise_out)
+        return _PropagateFn.apply(embeddings, (adj,) * self.n_layers, False, self.eps, calls, noise_out)
 
     forward = propagate
 
@@ -442,9 +402,7 @@ class LeftAdj:
         degrees are those of the thinned graph.  The per-edge values are formed with torch ops: one pass over [nnz]."""
         if not base.indptr.is_cuda:
             raise RuntimeError('LeftAdj.thinned: move the graph to the GPU first (to(device)); there is no CPU fallback')
-        long_row = min(max(base.chunk, 128), ops.GRAPH_DROPOUT_LONG_ROW)
-        _, t_values, _, out_deg, keep = ops.graph_dropout(base.indptr, base.indices, base.rev, keep_prob, generator=generator,
-                                                          want_keep=True, long_row=long_row)
+        _, t_values, _, out_deg, keep = base._dropout(keep_prob, generator=generator)
         inv_out = (1.0 / out_deg.clamp_min(1).double()).to(torch.float32)
         values = keep.to(torch.float32) * inv_out[base.indices.long()]
         return cls(base, values, (t_values != 0).to(torch.float32), inv_out, keep, out_deg)
@@ -452,24 +410,24 @@ class LeftAdj:
     def to(self, device):
         device = torch.device(device)
         if self.t_keep is not None:
-            mine = self.values.device
-            if device.type != mine.type or (device.index is not None and device.index != mine.index):
-                raise RuntimeError('LeftAdj: a thinned view lives on the device it was drawn on')
-            return self
+            return _stays_put(self, device, 'LeftAdj: a thinned view lives on the device it was drawn on')
         self.base.to(device)
         if self.values.device != self.base.indptr.device:
             self.values, self.inv_out = self.values.to(device), self.inv_out.to(device)
         return self
 
+    def csr(self, transposed=False):
+        b = self.base
+        return Csr(b.indptr, b.indices, self.t_keep, b.plan, self.inv_out) if transposed else \
+            Csr(b.indptr, b.indices, self.values, b.plan, None)
+
     def aggregate(self, x):
         """m = A x."""
-        b = self.base
-        return ops.spmm_csr(b.indptr, b.indices, self.values, x, plan=b.plan)
+        return _spmm(self.csr(), x)
 
     def aggregate_grad(self, dm, dx):
         """dx += A^T dm, in place, in one launch."""
-        b = self.base
-        return ops.spmm_csr(b.indptr, b.indices, self.t_keep, dm, plan=b.plan, row_scale=self.inv_out, acc=dx)
+        return _spmm(self.csr(transposed=True), dm, acc=dx)
 
 
 class _NGCFFn(torch.autograd.Function):

@@ -1177,8 +1177,14 @@ class LightGCN(BaseRetriever):
         self.num_users, self.num_items = train_data.num_users, train_data.num_items
         self.user_emb = torch.nn.Embedding(self.num_users, self.embed_dim, padding_idx=0)
         self.item_emb = torch.nn.Embedding(self.num_items, self.embed_dim, padding_idx=0)
-        self.LightGCNNet = graphmodule.LightGCNNet(self.config['model']['n_layers'])
+        net = self._get_gnn_net()
+        setattr(self, type(net).__name__, net)
         self.adj_mat = self._get_graph(train_data)
+
+    def _get_gnn_net(self):
+        """The propagation module; ``_init_model`` registers it under its class name."""
+        from . import graphmodule
+        return graphmodule.LightGCNNet(self.config['model']['n_layers'])
 
     def _get_graph(self, train_data):
         """The normalised adjacency of the training interactions (``model.spmm_chunk``: the chunk size of its plan, default
@@ -1319,11 +1325,13 @@ class SimGCL(LightGCN):
                 self.config['train'][key] = value
 
     def _init_model(self, train_data, drop_unused_field=True):
-        from . import data_augmentation, graphmodule
+        from . import data_augmentation
         super()._init_model(train_data, drop_unused_field)
-        del self.LightGCNNet
-        self.SimGCLNet = graphmodule.SimGCLNet(self.config['model']['n_layers'], self.config['model']['eps'])
         self.augmentation_model = data_augmentation.SimGCLAugmentation(self.config['model'], train_data)
+
+    def _get_gnn_net(self):
+        from . import graphmodule
+        return graphmodule.SimGCLNet(self.config['model']['n_layers'], self.config['model']['eps'])
 
     def _propagate(self, embeddings):
         return self.SimGCLNet.propagate(self.adj_mat, embeddings)
@@ -1383,14 +1391,16 @@ class NGCF(LightGCN):
     def _init_model(self, train_data, drop_unused_field=True):
         from . import graphmodule
         super()._init_model(train_data, drop_unused_field)
-        del self.LightGCNNet
+        self.left_adj = graphmodule.LeftAdj(self.adj_mat)
+        self.last_view = None
+
+    def _get_gnn_net(self):
+        from . import graphmodule
         model = self.config['model']
         layers = [int(v) for v in model['layer_size']]
         self.combiners = torch.nn.ModuleList(graphmodule.BiCombiner(a, b, dropout=float(p))
                                              for a, b, p in zip(layers[:-1], layers[1:], model['mess_dropout']))
-        self.NGCFNet = graphmodule.NGCFNet(self.combiners, len(layers) - 1)
-        self.left_adj = graphmodule.LeftAdj(self.adj_mat)
-        self.last_view = None
+        return graphmodule.NGCFNet(self.combiners, len(layers) - 1)
 
     def _propagate(self, embeddings):
         from . import graphmodule

@@ -29,40 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def timed(fns, reps, warmup):
-    """[ms per call] per function, the functions called in turn."""
-    for _ in range(warmup):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(reps):
-        for i, f in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            b.synchronize()
-            ms[i].append(a.elapsed_time(b))
-    return ms
-
-
-def row(t):
-    return dict(ms=statistics.median(t), ms_min_max=(min(t), max(t)))
-
-
-def peak_above(fn):
-    """Peak bytes allocated while ``fn`` runs, above what was allocated before it."""
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    before = torch.cuda.memory_allocated()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - before
-    del out
-    return peak
+from graph_bench import peak_above, row, timed, zipf_graph      # noqa: E402
 
 
 def main():
@@ -81,16 +48,12 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit('bench_ngcf.py measures on the GPU: none found')
     import recstudio_amd as ra
-    from recstudio_amd import dataset, graphmodule, ops, rng
+    from recstudio_amd import graphmodule, ops, rng
     dev = torch.device('cuda')
     d, p = a.dim, a.dropout
     nu, ni = a.users + 1, a.items + 1
     n = nu + ni
-    users, items = dataset.synthetic_interactions(a.users, a.items, a.inter, alpha=1.0)
-    users, items = torch.from_numpy(users), torch.from_numpy(items)
-    u_dev, i_dev = users.to(dev), items.to(dev) + nu
-    adj = graphmodule.NormAdj(torch.cat([u_dev, i_dev]), torch.cat([i_dev, u_dev]), n, symmetric=True)      # built on the device
-    del u_dev, i_dev
+    adj, users, items = zipf_graph(a.users, a.items, a.inter, dev)
     torch.cuda.empty_cache()
     res = dict(device=torch.cuda.get_device_name(0), users=a.users, items=a.items, interactions=a.inter, rows=n, nnz=adj.nnz, dim=d,
                dropout=p, chunk=adj.plan.chunk, reps=a.reps, warmup=a.warmup)

@@ -26,27 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def timed(fns, reps, warmup):
-    """[ms per call] per function, the functions called in turn."""
-    for _ in range(warmup):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(reps):
-        for i, f in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            b.synchronize()
-            ms[i].append(a.elapsed_time(b))
-    return ms
-
-
-def row(t):
-    return dict(ms=statistics.median(t), ms_min_max=(min(t), max(t)))
+from graph_bench import row, timed, zipf_graph      # noqa: E402
 
 
 def main():
@@ -64,15 +44,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit('bench_sgl.py measures on the GPU: none found')
     import recstudio_amd as ra
-    from recstudio_amd import dataset, graphmodule, ops
+    from recstudio_amd import ops
     dev = torch.device('cuda')
     nu, ni = a.users + 1, a.items + 1
     n = nu + ni
-    users, items = dataset.synthetic_interactions(a.users, a.items, a.inter, alpha=1.0)
-    users, items = torch.from_numpy(users), torch.from_numpy(items)
-    u_dev, i_dev = users.to(dev), items.to(dev) + nu
-    adj = graphmodule.NormAdj(torch.cat([u_dev, i_dev]), torch.cat([i_dev, u_dev]), n, symmetric=True)      # built on the device
-    del u_dev, i_dev
+    adj, users, items = zipf_graph(a.users, a.items, a.inter, dev)
     nnz, rev = adj.nnz, adj.rev
     torch.cuda.empty_cache()
     deg = adj.indptr[1:] - adj.indptr[:-1]
