@@ -68,8 +68,9 @@ struct PhiloxCall {
 // Layout of the rsa_scratch_bytes() block (zero-filled once by the caller):
 //   [0]     NaN / inf flag word of the in-kernel loss reduction (cleared by the kernel that read it)
 //   [64]    valid-row counter of the BCE losses (reset by a memset before each use)
-//   [256]   64-bit {arrivals, fixed-point loss sum} words of the in-kernel loss reduction: the top word, then 32
-//           sub-words 128 bytes apart (self-resetting; 4.2 KB of the 16 KB reserved here)
+//   [256]   64-bit {arrivals in bits 56..63, 2^-34 fixed-point loss sum in bits 0..55} words of the in-kernel loss
+//           reduction: the top word, then 32 sub-words 128 bytes apart (zero again after EVERY launch, whatever the
+//           losses were; 4.2 KB of the 16 KB reserved here)
 //   [256 + 4 * SCRATCH_MAX_GRID]   256 stage-1 partials of rsa_mean_rows
 constexpr int SCRATCH_MAX_GRID = 4096;
 constexpr int64_t SCRATCH_COUNTER = 0, SCRATCH_BCE_COUNT = 64, SCRATCH_FUSED_PARTIALS = 256,
@@ -334,8 +335,8 @@ __device__ __forceinline__ int32_t lookup_popular(const P& p, float u, float& pr
 }
 
 // loss = mean of the per-query losses, in the SAME launch, with ONE device-scope atomic per workgroup and no
-// second phase: every workgroup adds {its share of the mean as a 2^-38 fixed-point integer, 1 arrival} to one 64-bit
-// word (bits 0..49 sum, bits 50..63 arrivals); integer addition is associative, so the total is bit-reproducible
+// second phase: every workgroup adds {its share of the mean as a 2^-34 fixed-point integer, 1 arrival} to one 64-bit
+// word (bits 0..55 sum, bits 56..63 arrivals); integer addition is associative, so the total is bit-reproducible
 // whatever the arrival order.  The workgroup whose add returns gridDim.x - 1 earlier arrivals holds the complete sum
 // (returned value + its own share), writes the mean and resets the word.  A NaN / inf partial (SampledSoftmax with a
 // padded positive, loss_func.py:88-89) first sets a sticky flag word with a RETURNING atomic and only then arrives
@@ -344,15 +345,32 @@ __device__ __forceinline__ int32_t lookup_popular(const P& p, float u, float& pr
 // release / acquire pair at workgroup exit writes back / invalidates the whole XCD L2 (measured: +90 us per launch);
 // the first version exchanged float partials and counted arrivals with a second, dependent atomic -- two memory
 // round trips in every workgroup's tail, 7.5 us of a 43 us launch at B = 4096.
-// The words hold each workgroup's share of the MEAN (its loss sum / n_queries) at 2^-38 resolution, so the range does
-// not depend on the batch size: a mean loss up to 2^11 fits the 50-bit field whatever B is (quantisation <= grid * 2^-39
-// ~ 4e-9 absolute); a share >= 2^10 (or NaN / inf) saturates to +inf / NaN through the flag word.  Totals must be >= 0
-// (every loss on this path is).
+// The words hold each workgroup's share of the MEAN (its loss sum / n_queries) at 2^-34 resolution, so the range does
+// not depend on the batch size.  A share at or above LOSS_SHARE_CAP = 2^10 - 2^-35 (or NaN / inf) saturates to +inf / NaN
+// through the flag word; every other share rounds to an integer below 2^44, and LOSS_MAX_GRID = 4096 of them (the
+// largest grid of any caller: static_asserts at the launch sites) total less than 2^56, so the 56-bit sum field cannot
+// carry into the arrival count: the result is the mean (any mean below 2^10 * grid whose shares stay under the cap; a
+// mean below 2^11 needs two workgroups with about half each), or +inf / NaN, never another finite number, and the
+// words are zero after every launch.  Quantisation: every share is rounded to nearest, <= grid * 2^-35 absolute
+// (6e-8 at 2048 workgroups, before the one fp32 rounding of the result).  The 8-bit count holds the <= 128 members of
+// a sub-word and the <= 32 sub-words of the top word.  The first layout (2^-38 resolution, count at bit 50) held totals
+// below 2^12 only: a mean in [2^12, 2^10 * grid) with every share under the cap carried into the count, one workgroup
+// took itself for the last an arrival early, wrote a wrong finite loss, and the true last arrival left its {1, sum}
+// in the scratch for the next launch.  Totals must be >= 0 (every loss on this path is).
 // Two levels: workgroup b adds to sub-word b % 32 (the sub-words sit in different 128-byte lines), and the workgroup
 // that completes a sub-word forwards its total to the top word -- atomics on ONE address are performed one after the
 // other at the memory side (~8 ns each), and at B = 4096 all 1024 workgroups finish together: a single word cost an
 // 8 us tail on a 37 us launch.
-constexpr int LOSS_FRAC_BITS = 38, LOSS_COUNT_SHIFT = 50, LOSS_SUBWORDS = 32;
+constexpr int LOSS_FRAC_BITS = 34, LOSS_COUNT_SHIFT = 56, LOSS_SUBWORDS = 32;
+constexpr int LOSS_SHARE_BITS = 10;                  // a share below 2^10 - 2^-35 is added, anything else saturates
+constexpr int LOSS_MAX_GRID = SCRATCH_MAX_GRID;      // the largest grid a caller of reduce_mean_loss may launch
+constexpr double LOSS_SHARE_CAP = (double)(1 << LOSS_SHARE_BITS) - 1.0 / (double)(1ll << (LOSS_FRAC_BITS + 1));
+constexpr int loss_log2_ceil(long long v) { return v <= 1 ? 0 : 1 + loss_log2_ceil((v + 1) / 2); }
+static_assert(LOSS_FRAC_BITS + LOSS_SHARE_BITS + loss_log2_ceil(LOSS_MAX_GRID) <= LOSS_COUNT_SHIFT,
+              "reduce_mean_loss: LOSS_MAX_GRID capped shares must not carry out of the sum field");
+static_assert((LOSS_MAX_GRID + LOSS_SUBWORDS - 1) / LOSS_SUBWORDS < (1 << (64 - LOSS_COUNT_SHIFT)) &&
+                  LOSS_SUBWORDS < (1 << (64 - LOSS_COUNT_SHIFT)),
+              "reduce_mean_loss: the arrival count of a sub-word / of the top word must fit above the sum field");
 __device__ __forceinline__ void reduce_mean_loss(float wave_loss, float* __restrict__ loss_out,
                                                  unsigned int* __restrict__ flag_word,
                                                  float* __restrict__ loss_partials, int64_t n_queries) {
@@ -367,7 +385,7 @@ __device__ __forceinline__ void reduce_mean_loss(float wave_loss, float* __restr
     unsigned long long* words = reinterpret_cast<unsigned long long*>(loss_partials);     // 8-byte aligned (offset 256)
     constexpr unsigned long long FIELD = (1ull << LOSS_COUNT_SHIFT) - 1, ONE = 1ull << LOSS_COUNT_SHIFT;
     const double share = (double)part / (double)n_queries;       // this workgroup's share of the mean
-    const bool bad = !(fabs(share) < 1024.0);                    // NaN, inf or out of the fixed-point range
+    const bool bad = !(fabs(share) < LOSS_SHARE_CAP);            // NaN, inf or out of the fixed-point range
     const long long fixed = bad ? 0ll : __double2ll_rn(share * (double)(1ll << LOSS_FRAC_BITS));
     unsigned long long add = ((unsigned long long)fixed & FIELD) + ONE;
     if (bad) {

@@ -276,6 +276,7 @@ __device__ __forceinline__ float finish_score(int mode, float dot, float inorm2,
 #ifndef RSA_FWD_GRID_CAP
 #define RSA_FWD_GRID_CAP (256 * 8)
 #endif
+static_assert(RSA_FWD_GRID_CAP <= LOSS_MAX_GRID, "the fused loss epilogues reduce their loss with reduce_mean_loss");
 #ifndef RSA_QG_MIN_WAVES
 #define RSA_QG_MIN_WAVES 1
 #endif

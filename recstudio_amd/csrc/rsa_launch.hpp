@@ -55,10 +55,12 @@ struct WalkGeometry {
   int wpq_log2;
   unsigned blocks;
 };
+constexpr int OWNER_WALK_GRID_CAP = 4096;
+static_assert(OWNER_WALK_GRID_CAP <= LOSS_MAX_GRID, "the owner BPR walk reduces its loss with reduce_mean_loss");
 static inline WalkGeometry owner_walk_geometry(int64_t slots, int64_t n_queries) {
   const int64_t tiles_per_query = slots / (n_queries > 0 ? n_queries : 1) / 64;
   const int wpq_log2 = tiles_per_query >= 8 ? 2 : (tiles_per_query >= 3 ? 1 : 0);
-  return WalkGeometry{wpq_log2, grid_1d(n_queries, 4 >> wpq_log2, 4096)};
+  return WalkGeometry{wpq_log2, grid_1d(n_queries, 4 >> wpq_log2, OWNER_WALK_GRID_CAP)};
 }
 
 // ---------------------------------------------------------------- workspaces

@@ -861,11 +861,14 @@ __global__ __launch_bounds__(256) void shard_home_small_kernel(const HomeArgs a)
   }
 }
 
+constexpr int HOME_GRID_CAP = 2048;
+static_assert(HOME_GRID_CAP <= LOSS_MAX_GRID, "the home kernels reduce their loss with reduce_mean_loss");
+
 template <int LOSS>
 static void launch_home(const HomeArgs& h, hipStream_t s) {
   const int n = h.n;
   const int qpw = n <= 64 ? 8 : (n <= 128 ? 4 : (n <= 256 ? 2 : 1));
-  const dim3 grid(grid_1d(h.n_queries, 4 * qpw, 2048)), block(256);
+  const dim3 grid(grid_1d(h.n_queries, 4 * qpw, HOME_GRID_CAP)), block(256);
   const bool small = dispatch_int<8, 4, 2>(qpw, [&](auto QPW) {
     hipLaunchKernelGGL((shard_home_small_kernel<LOSS, QPW()>), grid, block, 0, s, h);
   });
