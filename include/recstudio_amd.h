@@ -955,6 +955,52 @@ int64_t rsa_bi_combine_workspace_bytes(int64_t n_rows, int32_t d_in, int32_t d_o
 int rsa_bi_combine(const rsa_bi_combine_args* args, rsa_stream_t stream);
 int rsa_bi_combine_backward(const rsa_bi_combine_args* args, rsa_stream_t stream);
 
+/* The attention core of the sequence towers, fused: what nn.MultiheadAttention computes between in_proj and out_proj as the
+ * reference's nn.TransformerEncoder calls it (recstudio/model/seq/sasrec.py:25-36, :60-63).  qkv fp32 [n_seq, seq_len, 3 D],
+ * D = n_head * head_dim, exactly what F.linear(x, in_proj_weight, in_proj_bias) returns: columns [0, D) are q, [D, 2 D) k,
+ * [2 D, 3 D) v, head h in columns h * head_dim .. of each.  Per sequence b and head h:
+ *   s_ij  = scale * <q_i, k_j>
+ *   key j is allowed for query i iff (!causal or j <= i) and !key_pad[b, j]
+ *   P_i.  = softmax over the allowed j;  lse_i = log sum_allowed exp(s_ij)                  lse fp32 [n_seq, n_head, seq_len]
+ *   Pt_ij = keep_ij * P_ij / q;  out_i = sum_j Pt_ij v_j                                    out fp32 [n_seq, seq_len, D], heads
+ *                                                                                           concatenated (out_proj's input)
+ * A query with no allowed key gets out = 0, lse = -inf and passes no gradient (torch returns NaN there).  fp32 throughout, the
+ * products on the fp32 matrix cores; one launch; nothing of size seq_len^2 is written (`keep` aside) or saved.
+ * 1 <= seq_len <= 64, head_dim 16, 32 or 64, any n_head >= 1, any n_seq; 64-bit element offsets.
+ * THE DROPOUT.  q = (float)(1.0 - p).  Element (b, h, i, j) is kept iff u < q, u = element elem_base + ((b * n_head + h) * seq_len
+ * + i) * seq_len + j of ONE torch.rand([n_seq, n_head, seq_len, seq_len]) call ("Philox state"); disallowed positions own their
+ * index like any other.  p == 0 reads no Philox state and draws nothing.  n_seq * n_head * seq_len^2 >= 2^31 with p > 0 is refused
+ * (torch splits that call).  This is NOT the stream nn.Dropout's or the SDPA kernels' dropout consumes.
+ * rsa_attention_backward takes qkv, key_pad, out and lse as the forward left them, g_out (the gradient of out) and the same Philox
+ * state; it recomputes S and P = exp(s - lse), regenerates the mask and writes EVERY element of dqkv [n_seq, seq_len, 3 D] (zeros
+ * where nothing flows).  All sums run inside one wave: no atomics, no workspace, two runs are bit-equal.
+ * seq_len / head_dim / n_head outside the range, p outside [0, 1), a bad Philox state, a null or non-16-byte-aligned qkv / out /
+ * g_out / dqkv, a null lse: RSA_ERR_ARG before the first HIP call.  n_seq == 0 returns 0 and launches nothing.  Nothing is
+ * allocated, nothing synchronises. */
+typedef struct rsa_attention_args {
+  int64_t size;                /* sizeof(rsa_attention_args) */
+  const float* qkv;            /* [n_seq, seq_len, 3 * n_head * head_dim] */
+  const uint8_t* key_pad;      /* nullable [n_seq, seq_len]: non-zero = key j of sequence b is not attended */
+  int64_t n_seq;
+  int32_t seq_len;
+  int32_t n_head;
+  int32_t head_dim;
+  int32_t causal;
+  float scale;                 /* 1 / sqrt(head_dim) for nn.MultiheadAttention */
+  uint32_t grid_threads;       /* "Philox state" of the torch.rand([n_seq, n_head, seq_len, seq_len]) call (p != 0) */
+  double p;                    /* dropout probability in [0, 1) */
+  uint64_t seed;
+  uint64_t offset;
+  uint64_t elem_base;
+  float* out;                  /* forward: out; backward: in */
+  float* lse;                  /* forward: out; backward: in */
+  uint8_t* keep;               /* forward: nullable [n_seq, n_head, seq_len, seq_len] out (tests) */
+  const float* g_out;          /* backward: [n_seq, seq_len, D] */
+  float* dqkv;                 /* backward: [n_seq, seq_len, 3 D] out */
+} rsa_attention_args;
+int rsa_attention(const rsa_attention_args* args, rsa_stream_t stream);
+int rsa_attention_backward(const rsa_attention_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

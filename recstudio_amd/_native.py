@@ -278,6 +278,16 @@ class BiCombineArgs(_Sized):
     ]
 
 
+class AttentionArgs(_Sized):
+    """struct rsa_attention_args."""
+    _fields_ = [
+        ('size', c_int64), ('qkv', c_void_p), ('key_pad', c_void_p), ('n_seq', c_int64), ('seq_len', c_int32), ('n_head', c_int32),
+        ('head_dim', c_int32), ('causal', c_int32), ('scale', c_float), ('grid_threads', c_uint32), ('p', c_double),
+        ('seed', c_uint64), ('offset', c_uint64), ('elem_base', c_uint64), ('out', c_void_p), ('lse', c_void_p), ('keep', c_void_p),
+        ('g_out', c_void_p), ('dqkv', c_void_p),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -289,6 +299,7 @@ STRUCTS = {
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
+    'rsa_attention_args': AttentionArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -379,6 +390,8 @@ SIGNATURES = {
     'rsa_bi_combine_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
     'rsa_bi_combine': (c_int, [POINTER(BiCombineArgs), c_void_p]),
     'rsa_bi_combine_backward': (c_int, [POINTER(BiCombineArgs), c_void_p]),
+    'rsa_attention': (c_int, [POINTER(AttentionArgs), c_void_p]),
+    'rsa_attention_backward': (c_int, [POINTER(AttentionArgs), c_void_p]),
 }
 
 _lib = None

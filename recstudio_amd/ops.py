@@ -1641,3 +1641,84 @@ def bi_combine_backward(x, m, w1, w2, b1, b2, *, g_h=None, g_out=None, col=0, ne
     a.dx, a.dm, a.dw1, a.dw2, a.db1, a.db2 = ptr(dx), ptr(dm), ptr(dw[0]), ptr(dw[1]), ptr(db[0]), ptr(db[1])
     _launch('rsa_bi_combine_backward', ctypes.byref(a))
     return dx, dm, dw[0], dw[1], db[0], db[1]
+
+
+# ------------------------------------------------------------------ the attention core of the sequence towers
+SEQ_ATTENTION_MAX_LEN = 64             # one tile holds the sequence (rsa_attention.hip, "TILE")
+SEQ_ATTENTION_HEAD_DIMS = (16, 32, 64)
+
+
+def _seq_attention_args(who, qkv, key_pad, n_head, causal, scale, p, philox):
+    qkv = _need(qkv, torch.float32, 'qkv')
+    n_head = int(n_head)
+    if qkv.dim() != 3 or n_head < 1 or qkv.shape[2] % (3 * n_head):
+        raise ValueError(f'{who}: qkv must be [B, L, 3 * n_head * head_dim] (n_head {n_head}), got {tuple(qkv.shape)}')
+    B, L, D3 = qkv.shape
+    D = D3 // 3
+    dh = D // n_head
+    if dh not in SEQ_ATTENTION_HEAD_DIMS:
+        raise ValueError(f'{who}: head_dim must be one of {SEQ_ATTENTION_HEAD_DIMS}, got {dh}')
+    if not 1 <= L <= SEQ_ATTENTION_MAX_LEN:
+        raise ValueError(f'{who}: the sequence length must lie in [1, {SEQ_ATTENTION_MAX_LEN}] (one tile holds it), got {L}')
+    if key_pad is not None:
+        if key_pad.dtype == torch.bool:
+            key_pad = key_pad.view(torch.uint8) if key_pad.is_contiguous() else key_pad.contiguous().view(torch.uint8)
+        key_pad = _need(key_pad, torch.uint8, 'key_pad')
+        if tuple(key_pad.shape) != (B, L):
+            raise ValueError(f'{who}: key_pad must be [{B}, {L}], got {tuple(key_pad.shape)}')
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'{who}: the dropout probability must lie in [0, 1), got {p}')
+    a = nat.AttentionArgs()
+    a.qkv, a.key_pad = ptr(qkv), ptr(key_pad)
+    a.n_seq, a.seq_len, a.n_head, a.head_dim, a.causal = B, L, n_head, dh, 1 if causal else 0
+    a.scale = 1.0 / math.sqrt(dh) if scale is None else float(scale)
+    a.p = p
+    if p != 0.0:
+        if not isinstance(philox, rng.PhiloxCall):
+            raise TypeError(f'{who}: dropout needs philox, a rng.PhiloxCall (rng.reserve(B * n_head * L * L, 4, device))')
+        if B * n_head * L * L >= 1 << 31:
+            raise ValueError(f'{who}: B * n_head * L * L = {B * n_head * L * L} >= 2^31: torch.rand splits such a call, the mask '
+                             'would not be its')
+        a.seed, a.offset, a.grid_threads, a.elem_base = philox.seed, philox.offset, philox.grid_threads, philox.elem_base
+    elif philox is not None:
+        raise ValueError(f'{who}: philox without dropout (p = 0 draws nothing)')
+    return a, (qkv, key_pad), B, L, D
+
+
+@_on_device
+def seq_attention(qkv, key_pad, n_head, *, causal=True, scale=None, p=0.0, philox=None, want_keep=False):
+    """rsa_attention: the attention core of ``nn.MultiheadAttention`` in one launch.  ``qkv`` fp32 [B, L, 3 D] =
+    ``F.linear(x, in_proj_weight, in_proj_bias)`` (q, k, v side by side, head h in columns ``h * dh ..`` of each); ``key_pad``
+    bool / uint8 [B, L] or None (non-zero: that key is not attended); L <= 64, dh = D / n_head in {16, 32, 64}.
+    Key j is allowed for query i iff ``(not causal or j <= i) and not key_pad[b, j]``; ``P`` = softmax of ``scale * q k^T`` over
+    the allowed keys (``scale`` defaults to ``1 / sqrt(dh)``), ``out = (keep * P / q) v``.
+    -> ``(out [B, L, D], lse [B, n_head, L][, keep uint8 [B, n_head, L, L]])``.  A query without an allowed key gets ``out = 0``
+    and ``lse = -inf`` (torch: NaN).
+    Dropout with probability ``p``: with q = fp32(1 - p), element (b, h, i, j) is kept iff ``u[b, h, i, j] < q``, ``u`` =
+    ``torch.rand(B, n_head, L, L)`` in the generator state ``philox`` (``rng.reserve(B * n_head * L * L, 4, device)``) was reserved
+    in.  ``p == 0`` takes no ``philox``."""
+    a, keepalive, B, L, D = _seq_attention_args('seq_attention', qkv, key_pad, n_head, causal, scale, p, philox)
+    dev = keepalive[0].device
+    out = torch.empty(B, L, D, dtype=torch.float32, device=dev)
+    lse = torch.empty(B, a.n_head, L, dtype=torch.float32, device=dev)
+    keep = torch.empty(B, a.n_head, L, L, dtype=torch.uint8, device=dev) if want_keep else None
+    a.out, a.lse, a.keep = ptr(out), ptr(lse), ptr(keep)
+    _launch('rsa_attention', ctypes.byref(a))
+    return (out, lse) + ((keep,) if want_keep else ())
+
+
+@_on_device
+def seq_attention_backward(qkv, key_pad, n_head, out, lse, g_out, *, causal=True, scale=None, p=0.0, philox=None):
+    """rsa_attention_backward: ``dqkv`` [B, L, 3 D] of ``seq_attention`` from ``g_out`` (the gradient of ``out``), the forward's
+    ``out`` and ``lse`` and the Philox state the forward was given.  The scores and the mask are recomputed; every element is
+    written (zeros where nothing flows).  No atomics; bit-equal from run to run."""
+    a, keepalive, B, L, D = _seq_attention_args('seq_attention_backward', qkv, key_pad, n_head, causal, scale, p, philox)
+    out, lse, g_out = _need(out, torch.float32, 'out'), _need(lse, torch.float32, 'lse'), _need(g_out, torch.float32, 'g_out')
+    if tuple(out.shape) != (B, L, D) or tuple(g_out.shape) != (B, L, D) or tuple(lse.shape) != (B, a.n_head, L):
+        raise ValueError(f'seq_attention_backward: out and g_out must be [{B}, {L}, {D}] and lse [{B}, {a.n_head}, {L}], got '
+                         f'{tuple(out.shape)}, {tuple(g_out.shape)}, {tuple(lse.shape)}')
+    dqkv = torch.empty(B, L, 3 * D, dtype=torch.float32, device=out.device)
+    a.out, a.lse, a.g_out, a.dqkv = ptr(out), ptr(lse), ptr(g_out), ptr(dqkv)
+    _launch('rsa_attention_backward', ctypes.byref(a))
+    return dqkv

@@ -30,6 +30,7 @@ from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, Pairwise
                         SoftmaxLoss)
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
+from .seqmodule import FusedTransformerEncoder
 
 __all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'LightGCN', 'SGL', 'SimGCL', 'default_config',
            'seed_everything']
@@ -1495,19 +1496,25 @@ class _SegEmbedFn(torch.autograd.Function):
 
 class SASRecQueryEncoder(torch.nn.Module):
     """recstudio/model/seq/sasrec.py:8-67: item-embedding gather of the history (HIP) + learned positions
-    + causal nn.TransformerEncoder (stock PyTorch-ROCm, out of scope) + last-position pooling."""
+    + nn.TransformerEncoder (causal unless ``bidirectional``) + last-position pooling.  The encoder is stock PyTorch-ROCm by
+    default; with ``fused_attention`` its layers run through ``seqmodule.FusedTransformerEncoder`` (the attention core as one
+    HIP kernel) over the same parameters: ``state_dict`` is the same either way."""
 
     def __init__(self, fiid, embed_dim, max_seq_len, n_head, hidden_size, dropout, activation, layer_norm_eps, n_layer,
-                 item_encoder):
+                 item_encoder, bidirectional=False, fused_attention=False):
         super().__init__()
         self.fiid = fiid
         self.item_encoder = item_encoder
+        self.bidirectional = bool(bidirectional)
+        self.fused_attention = bool(fused_attention)
         self.position_emb = torch.nn.Embedding(max_seq_len, embed_dim)
         layer = torch.nn.TransformerEncoderLayer(d_model=embed_dim, nhead=n_head, dim_feedforward=hidden_size,
                                                  dropout=dropout, activation=activation, layer_norm_eps=layer_norm_eps,
                                                  batch_first=True, norm_first=False)
         self.transformer_layer = torch.nn.TransformerEncoder(layer, num_layers=n_layer)
         self.dropout = torch.nn.Dropout(p=dropout)
+        # (no parameters of its own: it reads transformer_layer's at call time)
+        self._fused = FusedTransformerEncoder(self.transformer_layer, max_seq_len) if self.fused_attention else None
 
     def forward(self, batch):
         user_hist = batch['in_' + self.fiid]
@@ -1517,6 +1524,9 @@ class SASRecQueryEncoder(torch.nn.Module):
         if not isinstance(self.item_encoder, torch.nn.Embedding):
             # the row-sharded catalog (shard.ShardedRows put here by BaseRetriever._setup_shard): ids out, rows back
             rows = self.item_encoder(user_hist)
+        elif self._fused is not None and not user_hist.is_cuda:
+            # the torch-op twin of the fused tower (seqmodule.seq_attention_torch) on CPU tensors: parity checks without a device
+            rows = self.item_encoder(user_hist)
         elif seg is not None and user_hist.is_cuda:
             # the device loader handed over the CSR view (flat item column, start, end): the fused segment gather emits
             # [B, L, d] directly; ``in_item_id`` only serves the padding mask and the backward
@@ -1525,8 +1535,14 @@ class SASRecQueryEncoder(torch.nn.Module):
         else:
             rows = _EmbedFn.apply(self.item_encoder.weight, user_hist)
         seq = rows + self.position_emb(positions)
-        causal = torch.triu(torch.ones(L, L, dtype=torch.bool, device=user_hist.device), 1)
-        out = self.transformer_layer(self.dropout(seq), mask=causal, src_key_padding_mask=user_hist == 0)
+        if self._fused is not None:
+            out = self._fused(self.dropout(seq), key_pad=user_hist == 0, causal=not self.bidirectional)
+        else:
+            if self.bidirectional:
+                mask = torch.zeros(L, L, dtype=torch.bool, device=user_hist.device)
+            else:
+                mask = torch.triu(torch.ones(L, L, dtype=torch.bool, device=user_hist.device), 1)
+            out = self.transformer_layer(self.dropout(seq), mask=mask, src_key_padding_mask=user_hist == 0)
         last = (batch['seqlen'] - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, out.shape[-1])
         return out.gather(1, last).squeeze(1)
 
@@ -1540,7 +1556,7 @@ class SASRec(BaseRetriever):
         super().__init__(config, **kwargs)
         m = self.config['model']
         for k, v in (('hidden_size', 128), ('layer_num', 2), ('head_num', 2), ('dropout_rate', 0.5),
-                     ('activation', 'gelu'), ('layer_norm_eps', 1e-12)):
+                     ('activation', 'gelu'), ('layer_norm_eps', 1e-12), ('fused_attention', False)):
             m.setdefault(k, v)
         for k, v in (('negative_count', 1), ('init_method', 'normal')):
             if k not in user.get('train', {}):
@@ -1553,7 +1569,7 @@ class SASRec(BaseRetriever):
         m = self.config['model']
         return SASRecQueryEncoder(self.fiid, self.embed_dim, train_data.config['max_seq_len'], m['head_num'],
                                   m['hidden_size'], m['dropout_rate'], m['activation'], m['layer_norm_eps'],
-                                  m['layer_num'], self.item_encoder)
+                                  m['layer_num'], self.item_encoder, fused_attention=m['fused_attention'])
 
     def _get_query_feat(self, data):
         return data if isinstance(data, dict) else super()._get_query_feat(data)
