@@ -1001,6 +1001,49 @@ typedef struct rsa_attention_args {
 int rsa_attention(const rsa_attention_args* args, rsa_stream_t stream);
 int rsa_attention_backward(const rsa_attention_args* args, rsa_stream_t stream);
 
+/* The GRU recurrence of the sequence towers (GRU4Rec, NARM), fused: the SEQUENTIAL part of torch.nn.GRU (one layer, one
+ * direction, batch_first) as the reference's module.GRULayer runs it (recstudio/model/seq/gru4rec.py).  Gate order r, z, n:
+ *   gh_t = w_hh h_{t-1} (+ b_hh)    r = sigma(gi_r + gh_r)    z = sigma(gi_z + gh_z)    n = tanh(gi_n + r * gh_n)
+ *   h_t  = (1 - z) * n + z * h_{t-1}                          (b_hn sits INSIDE r * (.), as in torch)
+ * gi fp32 [n_seq, seq_len, 3 hidden] = F.linear(x, W_ih, b_ih) is the caller's GEMM; h_{-1} = h0 (null: 0).  out fp32
+ * [n_seq, seq_len, hidden] holds every h_t.  All seq_len steps run in ONE launch with w_hh resident in registers; the products
+ * run on the fp32 matrix cores.  hidden 32, 64 or 128, any seq_len, any n_seq; 64-bit element offsets.
+ * LENGTHS (nullable, device int64 [n_seq]): row b stops at lengths[b]: out[b, t >= lengths[b]] is +0 (nn.GRU runs on over the
+ * padding; both consumers of the reference discard those positions).  Null: every row has seq_len steps and the op is nn.GRU at
+ * every position.  The entry cannot read device memory: a device value outside [0, seq_len] is clamped into it by the kernel.
+ * lengths_host (nullable, HOST int64 [n_seq]) is the caller's own copy, when it has one: an entry outside [0, seq_len] is
+ * RSA_ERR_ARG.
+ * rsa_gru_backward takes gi, out, h0, w_hh, lengths as the forward had them, gh fp32 [n_seq, seq_len, 3 hidden] =
+ * F.linear(h_prev, w_hh, b_hh) with h_prev[:, t] = h_{t-1} (the caller's GEMM over all positions: h_prev is h0 followed by
+ * out[:, :-1]) and g_out, the gradient of out.  With dh_t = g_out_t + carry it walks t = seq_len - 1 .. 0:
+ *   dn = dh (1 - z)(1 - n^2)    dz = dh (h_{t-1} - n) z (1 - z)    dr = dn gh_n r (1 - r)    carry = dh z + w_hh^T [dr, dz, dn r]
+ * and writes EVERY element of dgi = [dr, dz, dn] [n_seq, seq_len, 3 hidden], dgh_n = dn r [n_seq, seq_len, hidden] (the r and z
+ * parts of dgh equal those of dgi) and dh0 [n_seq, hidden], +0 at t >= lengths[b].  d w_hh = dgh^T h_prev, d b_hh and the input
+ * Linear's gradients are the caller's GEMMs.  No atomics, no workspace; two runs are bit-equal.
+ * hidden outside {32, 64, 128}, negative n_seq / seq_len, a bad lengths_host entry, a null w_hh, a null or non-16-byte-aligned
+ * gi / out (/ gh / g_out / dgi / dgh_n / dh0): RSA_ERR_ARG before the first HIP call.  n_seq == 0 returns 0 and launches
+ * nothing.  Nothing is allocated, nothing synchronises. */
+typedef struct rsa_gru_args {
+  int64_t size;                /* sizeof(rsa_gru_args) */
+  const float* gi;             /* [n_seq, seq_len, 3 * hidden] */
+  const float* w_hh;           /* [3 * hidden, hidden] */
+  const float* b_hh;           /* nullable [3 * hidden] (forward only: the backward's gh carries it) */
+  const float* h0;             /* nullable [n_seq, hidden] */
+  const int64_t* lengths;      /* nullable device [n_seq] */
+  const int64_t* lengths_host; /* nullable HOST [n_seq]: checked against [0, seq_len] */
+  int64_t n_seq;
+  int32_t seq_len;
+  int32_t hidden;
+  float* out;                  /* forward: out; backward: in */
+  const float* gh;             /* backward: [n_seq, seq_len, 3 * hidden] */
+  const float* g_out;          /* backward: [n_seq, seq_len, hidden] */
+  float* dgi;                  /* backward: [n_seq, seq_len, 3 * hidden] out */
+  float* dgh_n;                /* backward: [n_seq, seq_len, hidden] out */
+  float* dh0;                  /* backward: [n_seq, hidden] out */
+} rsa_gru_args;
+int rsa_gru(const rsa_gru_args* args, rsa_stream_t stream);
+int rsa_gru_backward(const rsa_gru_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

@@ -288,6 +288,15 @@ class AttentionArgs(_Sized):
     ]
 
 
+class GruArgs(_Sized):
+    """struct rsa_gru_args."""
+    _fields_ = [
+        ('size', c_int64), ('gi', c_void_p), ('w_hh', c_void_p), ('b_hh', c_void_p), ('h0', c_void_p), ('lengths', c_void_p),
+        ('lengths_host', c_void_p), ('n_seq', c_int64), ('seq_len', c_int32), ('hidden', c_int32), ('out', c_void_p),
+        ('gh', c_void_p), ('g_out', c_void_p), ('dgi', c_void_p), ('dgh_n', c_void_p), ('dh0', c_void_p),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -299,7 +308,7 @@ STRUCTS = {
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
-    'rsa_attention_args': AttentionArgs,
+    'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -392,6 +401,8 @@ SIGNATURES = {
     'rsa_bi_combine_backward': (c_int, [POINTER(BiCombineArgs), c_void_p]),
     'rsa_attention': (c_int, [POINTER(AttentionArgs), c_void_p]),
     'rsa_attention_backward': (c_int, [POINTER(AttentionArgs), c_void_p]),
+    'rsa_gru': (c_int, [POINTER(GruArgs), c_void_p]),
+    'rsa_gru_backward': (c_int, [POINTER(GruArgs), c_void_p]),
 }
 
 _lib = None

@@ -1722,3 +1722,73 @@ def seq_attention_backward(qkv, key_pad, n_head, out, lse, g_out, *, causal=True
     a.out, a.lse, a.g_out, a.dqkv = ptr(out), ptr(lse), ptr(g_out), ptr(dqkv)
     _launch('rsa_attention_backward', ctypes.byref(a))
     return dqkv
+
+
+# ------------------------------------------------------------------ the GRU recurrence of the sequence towers
+GRU_HIDDEN_SIZES = (32, 64, 128)
+
+
+def _gru_args(who, gi, w_hh, h0, lengths):
+    gi, w_hh = _need(gi, torch.float32, 'gi'), _need(w_hh, torch.float32, 'w_hh')
+    if gi.dim() != 3 or w_hh.dim() != 2 or w_hh.shape[0] != 3 * w_hh.shape[1] or gi.shape[2] != w_hh.shape[0]:
+        raise ValueError(f'{who}: gi must be [B, L, 3 H] and w_hh [3 H, H], got {tuple(gi.shape)} and {tuple(w_hh.shape)}')
+    B, L, H3 = gi.shape
+    H = H3 // 3
+    if H not in GRU_HIDDEN_SIZES:
+        raise ValueError(f'{who}: the hidden size must be one of {GRU_HIDDEN_SIZES}, got {H}')
+    if h0 is not None:
+        h0 = _need(h0, torch.float32, 'h0')
+        if tuple(h0.shape) != (B, H):
+            raise ValueError(f'{who}: h0 must be [{B}, {H}], got {tuple(h0.shape)}')
+    lengths_host = None
+    if lengths is not None:
+        if lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,):
+            raise ValueError(f'{who}: lengths must be int64 [{B}], got {lengths.dtype} {tuple(lengths.shape)}')
+        if not lengths.is_cuda:
+            # a host copy: the native entry checks it against [0, L]; the device copy is what the kernel reads
+            lengths_host = lengths.contiguous()
+            lengths = lengths_host.to(gi.device)
+        lengths = _need(lengths, torch.int64, 'lengths')
+    a = nat.GruArgs()
+    a.gi, a.w_hh, a.h0, a.lengths = ptr(gi), ptr(w_hh), ptr(h0), ptr(lengths)
+    a.lengths_host = lengths_host.data_ptr() if lengths_host is not None else None
+    a.n_seq, a.seq_len, a.hidden = B, L, H
+    return a, (gi, w_hh, h0, lengths, lengths_host), B, L, H
+
+
+@_on_device
+def gru_sequence(gi, w_hh, *, b_hh=None, h0=None, lengths=None):
+    """rsa_gru: the sequential part of a one-layer, batch-first ``nn.GRU`` in one launch.  ``gi`` fp32 [B, L, 3 H] =
+    ``F.linear(x, W_ih, b_ih)`` (gates r | z | n), ``w_hh`` [3 H, H], ``b_hh`` [3 H] or None (``b_hn`` inside ``r * (.)``),
+    ``h0`` [B, H] or None (zeros), ``lengths`` int64 [B] or None; H in {32, 64, 128}.
+    -> ``out`` [B, L, H], every ``h_t``.  With ``lengths`` row b stops at ``lengths[b]`` and ``out[b, t >= lengths[b]]`` is 0
+    (values outside [0, L] are clamped on the device; a CPU ``lengths`` tensor is checked instead and raises)."""
+    a, keepalive, B, L, H = _gru_args('gru_sequence', gi, w_hh, h0, lengths)
+    if b_hh is not None:
+        b_hh = _need(b_hh, torch.float32, 'b_hh')
+        if tuple(b_hh.shape) != (3 * H,):
+            raise ValueError(f'gru_sequence: b_hh must be [{3 * H}], got {tuple(b_hh.shape)}')
+    out = torch.empty(B, L, H, dtype=torch.float32, device=keepalive[0].device)
+    a.b_hh, a.out = ptr(b_hh), ptr(out)
+    _launch('rsa_gru', ctypes.byref(a))
+    return out
+
+
+@_on_device
+def gru_sequence_backward(gi, gh, out, w_hh, g_out, *, h0=None, lengths=None):
+    """rsa_gru_backward: ``(dgi [B, L, 3 H], dgh_n [B, L, H], dh0 [B, H])`` of ``gru_sequence`` from ``g_out`` (the gradient of
+    ``out``), the forward's ``out`` and ``gh = F.linear(h_prev, w_hh, b_hh)`` with ``h_prev = cat(h0, out[:, :-1])``.  The r and z
+    parts of ``dgh`` are those of ``dgi``; ``dgh_n`` is its n part.  Every element is written (zeros at ``t >= lengths[b]``).
+    No atomics; bit-equal from run to run."""
+    a, keepalive, B, L, H = _gru_args('gru_sequence_backward', gi, w_hh, h0, lengths)
+    gh, out, g_out = _need(gh, torch.float32, 'gh'), _need(out, torch.float32, 'out'), _need(g_out, torch.float32, 'g_out')
+    if tuple(gh.shape) != (B, L, 3 * H) or tuple(out.shape) != (B, L, H) or tuple(g_out.shape) != (B, L, H):
+        raise ValueError(f'gru_sequence_backward: gh must be [{B}, {L}, {3 * H}] and out, g_out [{B}, {L}, {H}], got '
+                         f'{tuple(gh.shape)}, {tuple(out.shape)}, {tuple(g_out.shape)}')
+    dev = out.device
+    dgi = torch.empty(B, L, 3 * H, dtype=torch.float32, device=dev)
+    dgh_n = torch.empty(B, L, H, dtype=torch.float32, device=dev)
+    dh0 = torch.empty(B, H, dtype=torch.float32, device=dev)
+    a.gh, a.out, a.g_out, a.dgi, a.dgh_n, a.dh0 = ptr(gh), ptr(out), ptr(g_out), ptr(dgi), ptr(dgh_n), ptr(dh0)
+    _launch('rsa_gru_backward', ctypes.byref(a))
+    return dgi, dgh_n, dh0

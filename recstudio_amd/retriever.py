@@ -30,9 +30,9 @@ from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, Pairwise
                         SoftmaxLoss)
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
-from .seqmodule import FusedTransformerEncoder
+from .seqmodule import FusedGRU, FusedTransformerEncoder
 
-__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'LightGCN', 'SGL', 'SimGCL', 'default_config',
+__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'GRU4Rec', 'LightGCN', 'SGL', 'SimGCL', 'default_config',
            'seed_everything']
 
 
@@ -1576,6 +1576,81 @@ class SASRec(BaseRetriever):
 
     def _get_loss_func(self):
         return BinaryCrossEntropyLoss()         # sasrec.py:117-119
+
+    def _get_sampler(self, train_data):
+        return UniformSampler(train_data.num_items)
+
+
+class GRU4RecQueryEncoder(torch.nn.Module):
+    """recstudio/model/seq/gru4rec.py:36-53: item-embedding gather of the history (HIP) + nn.Dropout + module.GRULayer (an
+    ``nn.GRU`` with ``bias=False``, ``batch_first=True``) + last-position pooling + nn.Linear(hidden_size, embed_dim).  With
+    ``fused_gru`` the GRU runs through ``seqmodule.FusedGRU`` (the recurrence as one HIP kernel, stopped at ``seqlen``) over the
+    same parameters: ``state_dict`` is the same either way.  In train mode the device generator is consumed once per call, by
+    the ``nn.Dropout`` on the gathered rows."""
+
+    def __init__(self, fiid, embed_dim, hidden_size, dropout, n_layer, item_encoder, fused_gru=True):
+        super().__init__()
+        self.fiid = fiid
+        self.item_encoder = item_encoder
+        self.fused_gru = bool(fused_gru)
+        self.dropout = torch.nn.Dropout(p=dropout)
+        self.gru = torch.nn.GRU(input_size=embed_dim, hidden_size=hidden_size, num_layers=n_layer, bias=False, batch_first=True,
+                                bidirectional=False)
+        self.dense = torch.nn.Linear(hidden_size, embed_dim)
+        # (no parameters of its own: it reads gru's at call time)
+        self._fused = FusedGRU(self.gru) if self.fused_gru else None
+
+    def forward(self, batch):
+        user_hist = batch['in_' + self.fiid]
+        L = user_hist.shape[1]
+        seg = batch.get('_seg')
+        if not isinstance(self.item_encoder, torch.nn.Embedding) or not user_hist.is_cuda:
+            # the row-sharded catalog (shard.ShardedRows put here by BaseRetriever._setup_shard): ids out, rows back; or CPU
+            # tensors (the torch-op twin of the fused recurrence: parity checks without a device)
+            rows = self.item_encoder(user_hist)
+        elif seg is not None:
+            flat, start, end = seg
+            rows = _SegEmbedFn.apply(self.item_encoder.weight, flat, start, end, L, user_hist)
+        else:
+            rows = _EmbedFn.apply(self.item_encoder.weight, user_hist)
+        seqlen = batch['seqlen']
+        if self._fused is not None:
+            out, _ = self._fused(self.dropout(rows), lengths=seqlen, want_state=False)
+        else:
+            out, _ = self.gru(self.dropout(rows))
+        last = (seqlen - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, out.shape[-1])
+        return self.dense(out.gather(1, last).squeeze(1))
+
+
+class GRU4Rec(BaseRetriever):
+    """recstudio/model/seq/gru4rec.py:17-63 with the retriever tail on the fused BPR path."""
+
+    def __init__(self, config=None, **kwargs):
+        # recstudio/model/seq/config/gru4rec.yaml on top of basemodel.yaml; the caller's config wins
+        user = config or {}
+        super().__init__(config, **kwargs)
+        m = self.config['model']
+        for k, v in (('hidden_size', 128), ('dropout_rate', 0.3), ('layer_num', 1), ('fused_gru', True)):
+            m.setdefault(k, v)
+        if 'negative_count' not in user.get('train', {}):
+            self.config['train']['negative_count'] = 1
+
+    def _get_dataset_class():
+        return SeqDataset
+
+    def _get_query_encoder(self, train_data):
+        m = self.config['model']
+        return GRU4RecQueryEncoder(self.fiid, self.embed_dim, m['hidden_size'], m['dropout_rate'], m['layer_num'],
+                                   self.item_encoder, fused_gru=m['fused_gru'])
+
+    def _get_query_feat(self, data):
+        return data if isinstance(data, dict) else super()._get_query_feat(data)
+
+    def _get_score_func(self):
+        return InnerProductScorer()
+
+    def _get_loss_func(self):
+        return BPRLoss()
 
     def _get_sampler(self, train_data):
         return UniformSampler(train_data.num_items)
