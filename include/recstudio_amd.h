@@ -1044,6 +1044,52 @@ typedef struct rsa_gru_args {
 int rsa_gru(const rsa_gru_args* args, rsa_stream_t stream);
 int rsa_gru_backward(const rsa_gru_args* args, rsa_stream_t stream);
 
+/* Feed-forward (additive) attention pooling of the sequence towers (NARM, STAMP), fused: the reference's
+ * module.AttentionLayer(attention_type='feedforward', one hidden layer, sigmoid) with ONE query per sequence, softmax=False and
+ * value = key (recstudio/model/module/layers.py:322-399):
+ *   hid_bs = sigmoid(qh_b + W_k k_bs)    a_bs = key_pad[b, s] ? 0 : (w2 . hid_bs + b2) * scale    out_b = sum_s a_bs k_bs
+ * key fp32 [n_seq, seq_len, d]; qh fp32 [n_seq, m] = W1[:, :q_dim] q (+ b1) is the caller's GEMM; w_k = W1[:, q_dim:] is a
+ * column block of the wider W1: row c starts at w_k + c * w_k_stride; w2 [m]; b2 a DEVICE pointer to one float; key_pad nullable
+ * uint8 [n_seq, seq_len] (non-zero: weight 0 -- a fill with 0, not a softmax mask).  d and m each 32, 64 or 128; any seq_len >= 1.
+ * rsa_ff_attention writes out [n_seq, d] and a [n_seq, seq_len] (+0 at padded positions) in one launch and nothing else.
+ * rsa_ff_attention_backward takes the same inputs and g_out [n_seq, d], recomputes hid and a (nothing is saved), and writes EVERY
+ * element of dkey [n_seq, seq_len, d] (+0 at padded positions), dqh [n_seq, m], dw_k [m, d] (dense), dw2 [m] and db2 [1]:
+ *   da = g_b . k_bs   de = da * scale   dpre = de * w2 (.) hid (1 - hid)   dkey = a g_b + W_k^T dpre   dqh = sum_s dpre
+ *   dw_k = sum_bs dpre k^T   dw2 = sum_bs de hid   db2 = sum_bs de
+ * The sums over rows go through per-wave partial slots in `workspace` (rsa_ff_attention_workspace_bytes) added in a fixed order
+ * by a last launch: no atomics, two runs are bit-equal.  64-bit element offsets.
+ * d or m outside {32, 64, 128}, seq_len < 1, negative n_seq, a null or misaligned (16 bytes: key, qh, w_k, out, g_out; w_k_stride
+ * a multiple of 4, >= d) pointer, a workspace that is too small: RSA_ERR_ARG before the first HIP call.  n_seq == 0 returns 0 and
+ * launches nothing.  Nothing is allocated, nothing synchronises. */
+typedef struct rsa_ff_attention_args {
+  int64_t size;                /* sizeof(rsa_ff_attention_args) */
+  const float* key;            /* [n_seq, seq_len, d] */
+  const float* qh;             /* [n_seq, m] */
+  const float* w_k;            /* [m, d] block of a wider matrix */
+  int64_t w_k_stride;          /* floats between its rows */
+  const float* w2;             /* [m] */
+  const float* b2;             /* device [1] */
+  const uint8_t* key_pad;      /* nullable [n_seq, seq_len] */
+  int64_t n_seq;
+  int32_t seq_len;
+  int32_t d;
+  int32_t m;
+  float scale;
+  float* out;                  /* forward: [n_seq, d] out */
+  float* a;                    /* forward: [n_seq, seq_len] out */
+  const float* g_out;          /* backward: [n_seq, d] */
+  float* dkey;                 /* backward: [n_seq, seq_len, d] out */
+  float* dqh;                  /* backward: [n_seq, m] out */
+  float* dw_k;                 /* backward: [m, d] out */
+  float* dw2;                  /* backward: [m] out */
+  float* db2;                  /* backward: [1] out */
+  void* workspace;             /* backward */
+  int64_t workspace_bytes;     /* >= rsa_ff_attention_workspace_bytes(n_seq, seq_len, d, m) */
+} rsa_ff_attention_args;
+int64_t rsa_ff_attention_workspace_bytes(int64_t n_seq, int32_t seq_len, int32_t d, int32_t m);
+int rsa_ff_attention(const rsa_ff_attention_args* args, rsa_stream_t stream);
+int rsa_ff_attention_backward(const rsa_ff_attention_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

@@ -297,6 +297,16 @@ class GruArgs(_Sized):
     ]
 
 
+class FfAttentionArgs(_Sized):
+    """struct rsa_ff_attention_args."""
+    _fields_ = [
+        ('size', c_int64), ('key', c_void_p), ('qh', c_void_p), ('w_k', c_void_p), ('w_k_stride', c_int64), ('w2', c_void_p),
+        ('b2', c_void_p), ('key_pad', c_void_p), ('n_seq', c_int64), ('seq_len', c_int32), ('d', c_int32), ('m', c_int32),
+        ('scale', c_float), ('out', c_void_p), ('a', c_void_p), ('g_out', c_void_p), ('dkey', c_void_p), ('dqh', c_void_p),
+        ('dw_k', c_void_p), ('dw2', c_void_p), ('db2', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -308,7 +318,7 @@ STRUCTS = {
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
-    'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs,
+    'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs, 'rsa_ff_attention_args': FfAttentionArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -403,6 +413,9 @@ SIGNATURES = {
     'rsa_attention_backward': (c_int, [POINTER(AttentionArgs), c_void_p]),
     'rsa_gru': (c_int, [POINTER(GruArgs), c_void_p]),
     'rsa_gru_backward': (c_int, [POINTER(GruArgs), c_void_p]),
+    'rsa_ff_attention_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    'rsa_ff_attention': (c_int, [POINTER(FfAttentionArgs), c_void_p]),
+    'rsa_ff_attention_backward': (c_int, [POINTER(FfAttentionArgs), c_void_p]),
 }
 
 _lib = None

@@ -1792,3 +1792,88 @@ def gru_sequence_backward(gi, gh, out, w_hh, g_out, *, h0=None, lengths=None):
     a.gh, a.out, a.g_out, a.dgi, a.dgh_n, a.dh0 = ptr(gh), ptr(out), ptr(g_out), ptr(dgi), ptr(dgh_n), ptr(dh0)
     _launch('rsa_gru_backward', ctypes.byref(a))
     return dgi, dgh_n, dh0
+
+
+# ------------------------------------------------------------------ feed-forward attention pooling (NARM, STAMP)
+FF_ATTENTION_DIMS = (32, 64, 128)      # key width and hidden width: W_k is kept in LDS (rsa_ffattn.hip, "WEIGHTS IN LDS")
+
+
+def _ff_attention_args(who, key, qh, w_k, w2, b2, key_pad, scale):
+    key, qh = _need(key, torch.float32, 'key'), _need(qh, torch.float32, 'qh')
+    w_k = _need_view(w_k, torch.float32, 'w_k')
+    w2, b2 = _need(w2, torch.float32, 'w2'), _need(b2, torch.float32, 'b2')
+    if key.dim() != 3 or key.shape[1] < 1:
+        raise ValueError(f'{who}: key must be [B, S, D] with S >= 1, got {tuple(key.shape)}')
+    B, S, D = key.shape
+    if w_k.dim() != 2 or w_k.shape[1] != D:
+        raise ValueError(f'{who}: w_k must be [M, {D}] (the key columns of the hidden Linear), got {tuple(w_k.shape)}')
+    M = w_k.shape[0]
+    for name, d in (('D', D), ('M', M)):
+        if d not in FF_ATTENTION_DIMS:
+            raise ValueError(f'{who}: {name} must be one of {FF_ATTENTION_DIMS}, got {d}')
+    if w_k.stride(1) != 1 or w_k.stride(0) % 4 or w_k.stride(0) < D or w_k.data_ptr() % 16:
+        raise ValueError(f'{who}: w_k must be a 16-byte aligned column block with unit column stride and a row stride that is a '
+                         f'multiple of 4 (got strides {w_k.stride()}, offset {w_k.storage_offset()})')
+    if tuple(qh.shape) != (B, M):
+        raise ValueError(f'{who}: qh must be [{B}, {M}], got {tuple(qh.shape)}')
+    if w2.numel() != M or b2.numel() != 1:
+        raise ValueError(f'{who}: w2 must hold {M} elements and b2 one, got {tuple(w2.shape)} and {tuple(b2.shape)}')
+    if key_pad is not None:
+        if key_pad.dtype == torch.bool:
+            key_pad = key_pad.view(torch.uint8) if key_pad.is_contiguous() else key_pad.contiguous().view(torch.uint8)
+        key_pad = _need(key_pad, torch.uint8, 'key_pad')
+        if tuple(key_pad.shape) != (B, S):
+            raise ValueError(f'{who}: key_pad must be [{B}, {S}], got {tuple(key_pad.shape)}')
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f'{who}: scale must be finite, got {scale}')
+    a = nat.FfAttentionArgs()
+    a.key, a.qh, a.w_k, a.w_k_stride, a.w2, a.b2, a.key_pad = ptr(key), ptr(qh), ptr(w_k), w_k.stride(0), ptr(w2), ptr(b2), ptr(key_pad)
+    a.n_seq, a.seq_len, a.d, a.m, a.scale = B, S, D, M, scale
+    return a, (key, qh, w_k, w2, b2, key_pad), B, S, D, M
+
+
+@_on_device
+def ff_attention_pool(key, qh, w_k, w2, b2, key_pad=None, *, scale):
+    """rsa_ff_attention: the reference's feed-forward ``AttentionLayer`` with one query per sequence, ``softmax=False`` and
+    value = key, in one launch.  ``key`` fp32 [B, S, D]; ``qh`` fp32 [B, M] = ``F.linear(query, W1[:, :q_dim], b1)``; ``w_k`` fp32
+    [M, D] = ``W1[:, q_dim:]``, read in place through its row stride (a column block of ``W1``: no copy); ``w2`` fp32 [M] (or
+    [1, M]); ``b2`` fp32 [1] on the device; ``key_pad`` bool / uint8 [B, S] or None; D, M in {32, 64, 128}, any S >= 1.
+    ``a[b, s] = 0 if key_pad[b, s] else (w2 . sigmoid(qh[b] + w_k key[b, s]) + b2) * scale`` (``scale`` as fp32: the reference's
+    ``1 / sqrt(q_dim)``), ``out[b] = sum_s a[b, s] key[b, s]``.  -> ``(out [B, D], a [B, S])``; nothing of size B S M is written.
+    A sequence that is padded whole gets ``out = 0``; B = 0 returns empty tensors without a launch."""
+    a, keepalive, B, S, D, M = _ff_attention_args('ff_attention_pool', key, qh, w_k, w2, b2, key_pad, scale)
+    dev = keepalive[0].device
+    out = torch.empty(B, D, dtype=torch.float32, device=dev)
+    w = torch.empty(B, S, dtype=torch.float32, device=dev)
+    if B == 0:
+        return out, w
+    a.out, a.a = ptr(out), ptr(w)
+    _launch('rsa_ff_attention', ctypes.byref(a))
+    return out, w
+
+
+@_on_device
+def ff_attention_pool_backward(key, qh, w_k, w2, b2, key_pad, g_out, *, scale):
+    """rsa_ff_attention_backward: the gradients of ``ff_attention_pool`` from ``g_out`` (fp32 [B, D], the gradient of ``out``).
+    The hidden layer and the weights are recomputed from ``key`` and ``qh``: nothing the forward produced is read.
+    -> ``(dkey [B, S, D], dqh [B, M], dw_k [M, D], dw2 [M], db2 [1])``; every element is written, +0 at padded positions.  The
+    gradients of the query and of ``W1[:, :q_dim]`` / ``b1`` follow from ``dqh`` on the caller's side.  No atomics; bit-equal from
+    run to run."""
+    a, keepalive, B, S, D, M = _ff_attention_args('ff_attention_pool_backward', key, qh, w_k, w2, b2, key_pad, scale)
+    g_out = _need(g_out, torch.float32, 'g_out')
+    if tuple(g_out.shape) != (B, D):
+        raise ValueError(f'ff_attention_pool_backward: g_out must be [{B}, {D}], got {tuple(g_out.shape)}')
+    dev = keepalive[0].device
+    dkey = torch.empty(B, S, D, dtype=torch.float32, device=dev)
+    dqh = torch.empty(B, M, dtype=torch.float32, device=dev)
+    if B == 0:
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)      # noqa: E731
+        return dkey, dqh, z(M, D), z(M), z(1)
+    dw_k = torch.empty(M, D, dtype=torch.float32, device=dev)
+    dw2 = torch.empty(M + 1, dtype=torch.float32, device=dev)
+    ws, a.workspace_bytes = _workspace(dev, 'rsa_ff_attention_workspace_bytes', B, S, D, M)
+    a.workspace, a.g_out = ptr(ws), ptr(g_out)
+    a.dkey, a.dqh, a.dw_k, a.dw2, a.db2 = ptr(dkey), ptr(dqh), ptr(dw_k), ptr(dw2[:M]), ptr(dw2[M:])
+    _launch('rsa_ff_attention_backward', ctypes.byref(a))
+    return dkey, dqh, dw_k, dw2[:M], dw2[M:]

@@ -30,10 +30,14 @@ from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, Pairwise
                         SoftmaxLoss)
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
-from .seqmodule import FusedGRU, FusedTransformerEncoder
+from .seqmodule import AttentionLayer, FusedGRU, FusedTransformerEncoder, MLPModule
 
-__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'GRU4Rec', 'LightGCN', 'SGL', 'SimGCL', 'default_config',
-           'seed_everything']
+__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'GRU4Rec', 'NARM', 'STAMP', 'LightGCN', 'SGL',
+           'SimGCL', 'default_config', 'seed_everything']
+
+# ``model.fused_attention_pool`` of NARM and STAMP (the attention pooling as one HIP kernel): on where the kernel beat the
+# reference's op sequence in the same run, forward and forward + backward, at both models' shapes
+FUSED_ATTENTION_POOL_DEFAULT = True
 
 
 def default_config():
@@ -1654,3 +1658,145 @@ class GRU4Rec(BaseRetriever):
 
     def _get_sampler(self, train_data):
         return UniformSampler(train_data.num_items)
+
+
+def _history_rows(item_encoder, batch, fiid):
+    """``item_encoder(in_item_id)`` [B, L, d] of a sequence tower: the HIP gather (from the device loader's CSR view when the
+    batch carries one) for an ``nn.Embedding`` on device tensors, the module itself otherwise (a sharded catalog; CPU tensors)."""
+    user_hist = batch['in_' + fiid]
+    seg = batch.get('_seg')
+    if not isinstance(item_encoder, torch.nn.Embedding) or not user_hist.is_cuda:
+        return item_encoder(user_hist)
+    if seg is not None:
+        flat, start, end = seg
+        return _SegEmbedFn.apply(item_encoder.weight, flat, start, end, user_hist.shape[1], user_hist)
+    return _EmbedFn.apply(item_encoder.weight, user_hist)
+
+
+def _last_position(out, seqlen):
+    """SeqPoolingLayer(pooling_type='last'): ``out[b, seqlen[b] - 1]``."""
+    last = (seqlen - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, out.shape[-1])
+    return out.gather(1, last).squeeze(1)
+
+
+class NARMQueryEncoder(torch.nn.Module):
+    """recstudio/model/seq/narm.py:15-47: item-embedding gather of the history (HIP) + nn.Dropout + module.GRULayer (an ``nn.GRU``
+    with ``bias=False``) -> ``c_global`` = the state at the last position; ``c_local`` = ``AttentionLayer(q_dim=hidden_size,
+    mlp_layers=[hidden_size], bias=False)`` of that state over every GRU state (``seqmodule.AttentionLayer``: the pooling as one
+    HIP kernel with ``fused_attention_pool``); ``fc`` = nn.Dropout + nn.Linear(2 hidden_size, embed_dim, bias=False) of their
+    concatenation.  The GRU sits under ``gru_layer.2.gru`` as in the reference; with ``fused_gru`` it runs through
+    ``seqmodule.FusedGRU``.  ``state_dict`` is the same whichever flags are set.
+    In train mode the device generator is consumed TWICE per call, in this order: the ``nn.Dropout`` on the gathered rows
+    (``gru_layer.1``), then the ``nn.Dropout`` on ``cat(c_global, c_local)`` (``fc.0``).
+    The fused GRU writes zeros at ``t >= seqlen`` where ``nn.GRU`` runs on; the padding mask gives those positions weight 0 and
+    gradient 0 either way, so the query is the same."""
+
+    def __init__(self, fiid, embed_dim, hidden_size, layer_num, dropout_rate, item_encoder=None, fused_gru=True,
+                 fused_attention_pool=True):
+        super().__init__()
+        self.fiid = fiid
+        self.item_encoder = item_encoder
+        self.fused_gru = bool(fused_gru)
+        gru_layer = torch.nn.Module()
+        gru_layer.gru = torch.nn.GRU(input_size=embed_dim, hidden_size=hidden_size, num_layers=layer_num, bias=False,
+                                     batch_first=True, bidirectional=False)
+        # (the reference's Sequential(item_encoder, Dropout, GRULayer): the item encoder is registered once, above)
+        self.gru_layer = torch.nn.ModuleDict({'1': torch.nn.Dropout(dropout_rate[0]), '2': gru_layer})
+        self.attn_layer = AttentionLayer(q_dim=hidden_size, mlp_layers=[hidden_size], bias=False)
+        self.attn_layer.fused = bool(fused_attention_pool)
+        self.fc = torch.nn.Sequential(torch.nn.Dropout(dropout_rate[1]), torch.nn.Linear(hidden_size * 2, embed_dim, bias=False))
+        self._fused = FusedGRU(gru_layer.gru) if self.fused_gru else None
+
+    def forward(self, batch):
+        user_hist = batch['in_' + self.fiid]
+        rows = self.gru_layer['1'](_history_rows(self.item_encoder, batch, self.fiid))
+        seqlen = batch['seqlen']
+        if self._fused is not None:
+            gru_vec, _ = self._fused(rows, lengths=seqlen, want_state=False)
+        else:
+            gru_vec, _ = self.gru_layer['2'].gru(rows)
+        c_global = h_t = _last_position(gru_vec, seqlen)                                           # B x H
+        c_local = self.attn_layer(query=h_t.unsqueeze(1), key=gru_vec, value=gru_vec, key_padding_mask=user_hist == 0,
+                                  need_weight=False).squeeze(1)                                    # B x H
+        return self.fc(torch.cat((c_global, c_local), dim=1))                                      # B x D
+
+
+class _SeqSoftmaxRetriever(BaseRetriever):
+    """What NARM and STAMP share: SeqDataset, InnerProductScorer, SoftmaxLoss and no sampler -- ``training_step`` takes the
+    'full_softmax' path, which never holds [B, N]."""
+
+    def _get_dataset_class():
+        return SeqDataset
+
+    def _get_query_feat(self, data):
+        return data if isinstance(data, dict) else super()._get_query_feat(data)
+
+    def _get_score_func(self):
+        return InnerProductScorer()
+
+    def _get_loss_func(self):
+        return SoftmaxLoss()
+
+    def _get_sampler(self, train_data):
+        return None
+
+
+class NARM(_SeqSoftmaxRetriever):
+    """recstudio/model/seq/narm.py:50-88 with the retriever tail on the fused full-softmax path."""
+
+    def __init__(self, config=None, **kwargs):
+        # recstudio/model/seq/config/narm.yaml on top of basemodel.yaml; the caller's config wins
+        super().__init__(config, **kwargs)
+        m = self.config['model']
+        for k, v in (('hidden_size', 128), ('dropout_rate', [0.25, 0.5]), ('layer_num', 1), ('fused_gru', True),
+                     ('fused_attention_pool', FUSED_ATTENTION_POOL_DEFAULT)):
+            m.setdefault(k, v)
+
+    def _get_dataset_class():
+        return SeqDataset
+
+    def _get_query_encoder(self, train_data):
+        m = self.config['model']
+        return NARMQueryEncoder(self.fiid, self.embed_dim, m['hidden_size'], m['layer_num'], m['dropout_rate'], self.item_encoder,
+                                fused_gru=m['fused_gru'], fused_attention_pool=m['fused_attention_pool'])
+
+
+class STAMPQueryEncoder(torch.nn.Module):
+    """recstudio/model/seq/stamp.py:6-32: ``m_t`` = the last item's embedding, ``m_s`` = the mean of the history's, ``m_a`` =
+    ``AttentionLayer(q_dim=2 embed_dim, k_dim=embed_dim, mlp_layers=[embed_dim])`` of ``cat(m_t, m_s)`` over the history rows
+    (``seqmodule.AttentionLayer``: one HIP kernel with ``fused_attention_pool``), query = ``mlpA(m_a) * mlpB(m_t)`` (two
+    ``MLPModule([embed_dim, embed_dim], Tanh)``).  No dropout is active: the generator is not consumed."""
+
+    def __init__(self, fiid, embed_dim, item_encoder, fused_attention_pool=True):
+        super().__init__()
+        self.fiid = fiid
+        self.item_encoder = item_encoder
+        self.attention_layer = AttentionLayer(q_dim=2 * embed_dim, k_dim=embed_dim, mlp_layers=[embed_dim])
+        self.attention_layer.fused = bool(fused_attention_pool)
+        self.mlpA = MLPModule([embed_dim, embed_dim], torch.nn.Tanh())
+        self.mlpB = MLPModule([embed_dim, embed_dim], torch.nn.Tanh())
+
+    def forward(self, batch):
+        user_hist = batch['in_' + self.fiid]
+        seq_emb = _history_rows(self.item_encoder, batch, self.fiid)
+        m_t = _last_position(seq_emb, batch['seqlen'])
+        m_s = seq_emb.sum(dim=1) / batch['seqlen'].unsqueeze(1).float()                            # B x D
+        query = torch.cat((m_t, m_s), dim=1)                                                       # B x 2D
+        m_a = self.attention_layer(query.unsqueeze(1), seq_emb, seq_emb, key_padding_mask=(user_hist == 0)).squeeze(1)
+        return self.mlpA(m_a) * self.mlpB(m_t)
+
+
+class STAMP(_SeqSoftmaxRetriever):
+    """recstudio/model/seq/stamp.py:35-61 with the retriever tail on the fused full-softmax path."""
+
+    def __init__(self, config=None, **kwargs):
+        # recstudio/model/seq/config/stamp.yaml (embed_dim 64) on top of basemodel.yaml; the caller's config wins
+        super().__init__(config, **kwargs)
+        self.config['model'].setdefault('fused_attention_pool', FUSED_ATTENTION_POOL_DEFAULT)
+
+    def _get_dataset_class():
+        return SeqDataset
+
+    def _get_query_encoder(self, train_data):
+        return STAMPQueryEncoder(self.fiid, self.embed_dim, self.item_encoder,
+                                 fused_attention_pool=self.config['model']['fused_attention_pool'])

@@ -27,6 +27,22 @@ b_ih)``; in the backward ``gh = F.linear(h_prev, W_hh, b_hh)`` over all position
 dependent steps are ONE launch of ``ops.gru_sequence`` (``rsa_gru``, recstudio_amd/csrc/rsa_gru.hip) per direction.
 ``lengths``: row b stops at ``lengths[b]``; ``out[b, t >= lengths[b]]`` is 0 and ``h_n[b]`` is the state at ``lengths[b] - 1``
 (``nn.GRU`` runs on over the padding; the reference's consumers discard those positions).  ``gru_sequence_torch`` is the twin.
+
+THE FEED-FORWARD ATTENTION POOLING (NARM, STAMP).  recstudio/model/module/layers.py:322-399 (``AttentionLayer``) with
+``attention_type='feedforward'`` scores every position of the history against ONE query vector per sequence through a
+one-hidden-layer MLP and returns the weighted sum of the history rows.  ``MLPModule`` and ``AttentionLayer`` here take the
+reference's constructor arguments and hold its parameters under its ``state_dict`` keys (``mlp.0.model.1.weight`` = ``W1``
+[M, q_dim + k_dim], ``mlp.0.model.1.bias`` = ``b1`` with ``bias=True``, ``mlp.1.weight`` = ``w2`` [1, M], ``mlp.1.bias`` = ``b2``).
+The rule, with ``softmax=False`` and value = key (the only way the two models call it):
+
+    qh_b = W1[:, :q_dim] q_b (+ b1)        hid_bs = sigmoid(qh_b + W1[:, q_dim:] k_bs)
+    a_bs = key_pad[b, s] ? 0 : (w2 . hid_bs + b2) / sqrt(q_dim)        out_b = sum_s a_bs k_bs
+
+The divisor is ``sqrt(q_dim)`` (the reference reads ``.size(-1)`` of the EXPANDED query, before the concatenation); the mask
+fills with 0 -- there is no softmax --; ``b2`` reaches every live position.  ``qh`` stays a torch GEMM; everything per position is
+ONE launch of ``ops.ff_attention_pool`` (``rsa_ff_attention``, recstudio_amd/csrc/rsa_ffattn.hip), which never writes the
+``[B, S, q_dim + k_dim]`` concatenation or the ``[B, S, M]`` hidden layer, and whose backward recomputes instead of saving.
+``ff_attention_pool_torch`` is the twin: the reference's op sequence literally.
 """
 import math
 
@@ -35,7 +51,8 @@ import torch.nn.functional as F
 
 from . import ops, rng
 
-__all__ = ['seq_attention', 'seq_attention_torch', 'FusedTransformerEncoder', 'gru_sequence', 'gru_sequence_torch', 'FusedGRU']
+__all__ = ['seq_attention', 'seq_attention_torch', 'FusedTransformerEncoder', 'gru_sequence', 'gru_sequence_torch', 'FusedGRU',
+           'ff_attention_pool', 'ff_attention_pool_torch', 'MLPModule', 'AttentionLayer']
 
 
 def allowed_keys(key_pad, causal, B, L, device):
@@ -266,3 +283,182 @@ def last_state(out, h0, lengths):
     last = out.gather(1, idx).squeeze(1) if L else out.new_zeros(B, H)
     empty = (lengths <= 0).view(B, 1)
     return torch.where(empty, h0 if h0 is not None else torch.zeros_like(last), last)
+
+
+def ff_attention_pool_torch(query, key, w1, b1, w2, b2, key_pad=None):
+    """The feed-forward attention pooling in the reference's own op sequence (recstudio/model/module/layers.py:371-389 around
+    the MLP of :346-354), any float dtype: ``query`` [B, q_dim], ``key`` [B, S, k_dim], ``w1`` [M, q_dim + k_dim], ``b1`` [M] or
+    None, ``w2`` [1, M], ``b2`` [1], ``key_pad`` bool [B, S] or None -> ``(out [B, k_dim], a [B, S])``."""
+    q = query.unsqueeze(1)                                                       # the caller's query.unsqueeze(1): B x 1 x q_dim
+    q = q.unsqueeze(2).expand(-1, -1, key.size(1), -1)                           # layers.py:371
+    k = key.unsqueeze(1).expand(-1, q.size(1), -1, -1)                           # layers.py:372
+    x = torch.cat((q, k), dim=-1)                                                # layers.py:374
+    hid = torch.sigmoid(F.linear(x, w1, b1))                                     # MLPModule: Dropout(0), Linear, Sigmoid (:198-205)
+    w = F.linear(hid, w2, b2).squeeze(-1)                                        # layers.py:353, :374   B x 1 x S
+    w = w / (q.size(-1) ** 0.5)                                                  # layers.py:378
+    if key_pad is not None:
+        w = w.masked_fill(key_pad.bool().unsqueeze(1).expand(-1, q.size(1), -1), 0.0)   # layers.py:380-384 (softmax=False)
+    out = w @ key                                                                # layers.py:389   B x 1 x D
+    return out.squeeze(1), w.squeeze(1)
+
+
+class _FfAttentionFn(torch.autograd.Function):
+    """``ops.ff_attention_pool`` / ``ops.ff_attention_pool_backward`` and the small GEMMs on the query side as one autograd node.
+    Saved: the inputs and ``qh`` [B, M] -- nothing of size B S M; the backward recomputes the hidden layer and the weights."""
+
+    @staticmethod
+    def forward(ctx, query, key, w1, b1, w2, b2, key_pad):
+        query, key = query.detach().contiguous(), key.detach().contiguous()
+        w1, w2, b2 = w1.detach(), w2.detach(), b2.detach()
+        q_dim = query.shape[1]
+        qh = F.linear(query, w1[:, :q_dim], None if b1 is None else b1.detach())
+        scale = 1.0 / math.sqrt(q_dim)
+        out, a = ops.ff_attention_pool(key, qh, w1[:, q_dim:], w2, b2, key_pad, scale=scale)
+        ctx.save_for_backward(query, key, w1, w2, b2, key_pad, qh)
+        ctx.scale, ctx.has_b1 = scale, b1 is not None
+        ctx.mark_non_differentiable(a)
+        return out, a
+
+    @staticmethod
+    def backward(ctx, g_out, _g_a):
+        query, key, w1, w2, b2, key_pad, qh = ctx.saved_tensors
+        q_dim = query.shape[1]
+        dkey, dqh, dw_k, dw2, db2 = ops.ff_attention_pool_backward(key, qh, w1[:, q_dim:], w2, b2, key_pad, g_out.contiguous(),
+                                                                   scale=ctx.scale)
+        dquery = dqh @ w1[:, :q_dim] if ctx.needs_input_grad[0] else None
+        dw1 = torch.cat([dqh.t() @ query, dw_k], dim=1) if ctx.needs_input_grad[2] else None
+        db1 = dqh.sum(0) if ctx.has_b1 and ctx.needs_input_grad[3] else None
+        return dquery, dkey, dw1, db1, dw2.view_as(w2), db2.view_as(b2), None
+
+
+def ff_attention_kernel_ok(query, key, w1):
+    """Whether ``ops.ff_attention_pool`` takes these tensors: fp32 on the device, key width and hidden width in
+    ``ops.FF_ATTENTION_DIMS``, and ``W1[:, q_dim:]`` a 16-byte aligned column block."""
+    return (key.is_cuda and query.is_cuda and w1.is_cuda and key.dtype == query.dtype == w1.dtype == torch.float32
+            and query.dim() == 2 and key.dim() == 3 and key.shape[1] >= 1 and key.shape[2] in ops.FF_ATTENTION_DIMS
+            and w1.shape[0] in ops.FF_ATTENTION_DIMS and query.shape[1] % 4 == 0 and w1.is_contiguous()
+            and w1.shape[1] == query.shape[1] + key.shape[2] and w1.data_ptr() % 16 == 0)
+
+
+def ff_attention_pool(query, key, w1, b1, w2, b2, key_pad=None):
+    """``(out [B, k_dim], a [B, S])`` of the feed-forward attention pooling: the fused kernel where ``ff_attention_kernel_ok``,
+    ``ff_attention_pool_torch`` otherwise (CPU tensors: the parity path)."""
+    if ff_attention_kernel_ok(query, key, w1):
+        if key_pad is not None and key_pad.dtype == torch.bool:
+            key_pad = key_pad.contiguous().view(torch.uint8)
+        return _FfAttentionFn.apply(query, key, w1, b1, w2, b2, key_pad)
+    return ff_attention_pool_torch(query, key, w1, b1, w2, b2, key_pad)
+
+
+def get_act(activation, dim=None):
+    """recstudio/model/module/layers.py:22-47, the activations the sequence towers name."""
+    if activation is None or isinstance(activation, torch.nn.Module):
+        return activation
+    if not isinstance(activation, str):
+        raise ValueError('"activation_func" must be a str or a instance of torch.nn.Module. ')
+    table = {'relu': torch.nn.ReLU, 'sigmoid': torch.nn.Sigmoid, 'tanh': torch.nn.Tanh, 'leakyrelu': torch.nn.LeakyReLU,
+             'gelu': torch.nn.GELU, 'identity': torch.nn.Identity}
+    if activation.lower() not in table:
+        raise ValueError(f'activation function type "{activation}"  is not supported, check spelling or pass in a instance of '
+                         'torch.nn.Module.')
+    return table[activation.lower()]()
+
+
+class MLPModule(torch.nn.Module):
+    """recstudio/model/module/layers.py:150-222: per layer ``Dropout``, ``Linear``, (``BatchNorm1d``,) activation, in one
+    ``nn.Sequential`` named ``model`` -- the first Linear is ``model.1``."""
+
+    def __init__(self, mlp_layers, activation_func='ReLU', dropout=0.0, bias=True, batch_norm=False, last_activation=True,
+                 last_bn=True):
+        super().__init__()
+        self.mlp_layers = mlp_layers
+        self.batch_norm = batch_norm
+        self.bias = bias
+        self.dropout = dropout
+        self.activation_func = activation_func
+        layers = []
+        last_bn = self.batch_norm and last_bn
+        n = len(mlp_layers) - 2
+        for idx, (d_in, d_out) in enumerate(zip(mlp_layers[:-1], mlp_layers[1:])):
+            layers.append(torch.nn.Dropout(dropout))
+            layers.append(torch.nn.Linear(d_in, d_out, bias=bias))
+            if (idx == n and last_bn) or (idx < n and batch_norm):
+                layers.append(torch.nn.BatchNorm1d(d_out))
+            if activation_func is not None and (idx < n or last_activation):
+                layers.append(get_act(activation_func, dim=d_out))
+        self.model = torch.nn.Sequential(*layers)
+
+    def add_modules(self, *args):
+        for block in args:
+            assert isinstance(block, torch.nn.Module)
+        for block in args:
+            self.model.add_module(str(len(self.model._modules)), block)
+
+    def forward(self, input):
+        return self.model(input)
+
+
+class AttentionLayer(torch.nn.Module):
+    """recstudio/model/module/layers.py:322-399, same constructor arguments, same ``state_dict``.  ``forward`` takes the fused
+    pooling (``ff_attention_pool``) when ``self.fused`` (default True; a plain attribute, not a parameter) and the call is the one
+    NARM and STAMP make -- ``attention_type='feedforward'``, one hidden layer with a sigmoid, query length 1, ``value is key``,
+    ``softmax=False`` -- on tensors ``ff_attention_kernel_ok`` accepts; every other call runs the reference's op sequence
+    (``ff_attention_pool_torch`` for the feed-forward type).  On CPU tensors that twin is the parity path."""
+
+    def __init__(self, q_dim, k_dim=None, v_dim=None, mlp_layers=[], activation='sigmoid', n_head=1, dropout=0.0, bias=True,
+                 attention_type='feedforward', batch_first=True):
+        super().__init__()
+        assert attention_type in ('feedforward', 'multi-head', 'scaled-dot-product'), \
+            'expecting attention_type to be one of [feedforeard, multi-head, scaled-dot-product]'
+        self.attention_type = attention_type
+        self.fused = True
+        if k_dim is None:
+            k_dim = q_dim
+        if v_dim is None:
+            v_dim = k_dim
+        if attention_type == 'feedforward':
+            mlp_layers = [q_dim + k_dim] + list(mlp_layers) + [1]
+            self.mlp = torch.nn.Sequential(MLPModule(mlp_layers=mlp_layers[:-1], activation_func=activation, bias=bias),
+                                           torch.nn.Linear(mlp_layers[-2], mlp_layers[-1]))
+        elif attention_type == 'multi-head':
+            self.attn_layer = torch.nn.MultiheadAttention(embed_dim=q_dim, num_heads=n_head, dropout=dropout, bias=bias, kdim=k_dim,
+                                                          vdim=v_dim, batch_first=batch_first)
+        else:
+            assert q_dim == k_dim, 'expecting q_dim is equal to k_dim in scaled-dot-product attention'
+
+    def _one_sigmoid_layer(self):
+        """(W1, b1, w2, b2) when the MLP is Dropout(0) / Linear / Sigmoid + Linear(M, 1), else None."""
+        if self.attention_type != 'feedforward':
+            return None
+        body = self.mlp[0].model
+        if len(body) != 3 or not isinstance(body[1], torch.nn.Linear) or not isinstance(body[2], torch.nn.Sigmoid) \
+                or (body[0].p != 0.0 and self.training):
+            return None
+        return body[1].weight, body[1].bias, self.mlp[1].weight, self.mlp[1].bias
+
+    def forward(self, query, key, value, key_padding_mask=None, need_weight=False, attn_mask=None, softmax=False,
+                average_attn_weights=True):
+        # query: B x L x D1; key: B x S x D2; value: B x S x D; key_padding_mask: B x S
+        if self.attention_type == 'multi-head':
+            attn_output, attn_output_weight = self.attn_layer(query, key, value, key_padding_mask, True, attn_mask,
+                                                              average_attn_weights)
+            return (attn_output, attn_output_weight) if need_weight else attn_output
+        params = self._one_sigmoid_layer()
+        if params is not None and query.dim() == 3 and query.shape[1] == 1 and value is key and not softmax:
+            pool = ff_attention_pool if self.fused else ff_attention_pool_torch
+            out, w = pool(query[:, 0], key, *params, key_padding_mask)
+            return (out.unsqueeze(1), w.unsqueeze(1)) if need_weight else out.unsqueeze(1)
+        if self.attention_type == 'feedforward':
+            query = query.unsqueeze(2).expand(-1, -1, key.size(1), -1)
+            key = key.unsqueeze(1).expand(-1, query.size(1), -1, -1)
+            attn_output_weight = self.mlp(torch.cat((query, key), dim=-1)).squeeze(-1)      # B x L x S
+        else:
+            attn_output_weight = query @ key.transpose(1, 2)
+        attn_output_weight = attn_output_weight / (query.size(-1) ** 0.5)
+        if key_padding_mask is not None:
+            key_padding_mask = key_padding_mask.unsqueeze(1).expand(-1, query.size(1), -1)
+            attn_output_weight = attn_output_weight.masked_fill(key_padding_mask, -torch.inf if softmax else 0.0)
+        if softmax:
+            attn_output_weight = torch.softmax(attn_output_weight, dim=-1)
+        attn_output = attn_output_weight @ value                                             # B x L x D
+        return (attn_output, attn_output_weight) if need_weight else attn_output
