@@ -22,6 +22,7 @@ from . import graphmodule                                         # noqa: F401
 from . import seqmodule                                           # noqa: F401
 from .seqmodule import FusedTransformerEncoder, seq_attention_torch, FusedGRU, gru_sequence_torch   # noqa: F401
 from .seqmodule import AttentionLayer, MLPModule, ff_attention_pool, ff_attention_pool_torch   # noqa: F401
+from .seqmodule import caser_conv_torch   # noqa: F401
 from . import data_augmentation                                   # noqa: F401
 from . import eval                                                # noqa: F401
 from . import fused                                               # noqa: F401

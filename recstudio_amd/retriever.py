@@ -30,7 +30,7 @@ from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, Pairwise
                         SoftmaxLoss)
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
-from .seqmodule import AttentionLayer, FusedGRU, FusedTransformerEncoder, MLPModule
+from .seqmodule import AttentionLayer, FusedGRU, FusedTransformerEncoder, MLPModule, caser_conv_torch, caser_pack
 
 __all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'GRU4Rec', 'NARM', 'STAMP', 'LightGCN', 'SGL',
            'SimGCL', 'default_config', 'seed_everything']
@@ -1800,3 +1800,42 @@ class STAMP(_SeqSoftmaxRetriever):
     def _get_query_encoder(self, train_data):
         return STAMPQueryEncoder(self.fiid, self.embed_dim, self.item_encoder,
                                  fused_attention_pool=self.config['model']['fused_attention_pool'])
+
+
+class CaserQueryEncoder(torch.nn.Module):
+    """recstudio/model/seq/caser.py:16-56, same constructor arguments, same submodules (``user_embedding``, ``item_embedding`` --
+    the tower's OWN [num_items, embed_dim] table, not the item encoder --, ``vertical_filter``, ``horizontal_filter.{i}``, ``fc``)
+    and so the same ``state_dict``.  The history ids are padded to ``max_seq_len`` (:39) and gathered through ``_history_rows``;
+    everything between that gather and the dropout in front of ``fc`` is ``seqmodule.caser_conv_torch``, the reference's op
+    sequence over the ``Conv2d`` modules' own parameters; then ``nn.Dropout``, ``relu(fc(.))`` and ``cat((z, P_u))``: a query of
+    width 2 embed_dim.  In train mode the generator is consumed ONCE per call, by that ``nn.Dropout`` on ``o`` [B, n_v d + L n_h].
+    The tower only: no retriever is built on it while its convolutions have no kernel."""
+
+    def __init__(self, fiid, fuid, num_users, num_items, embed_dim, max_seq_len, n_v, n_h, dropout=0.2) -> None:
+        super().__init__()
+        self.fiid = fiid
+        self.fuid = fuid
+        self.max_seq_len = max_seq_len
+        self.user_embedding = torch.nn.Embedding(num_users, embed_dim, 0)
+        self.item_embedding = torch.nn.Embedding(num_items, embed_dim, 0)
+        self.dropout = torch.nn.Dropout(p=dropout)
+        self.vertical_filter = torch.nn.Conv2d(in_channels=1, out_channels=n_v, kernel_size=(self.max_seq_len, 1))
+        self.horizontal_filter = torch.nn.ModuleList([
+            torch.nn.Conv2d(in_channels=1, out_channels=n_h, kernel_size=(h, embed_dim)) for h in range(1, max_seq_len + 1)])
+        self.fc = torch.nn.Linear(n_v * embed_dim + n_h * max_seq_len, embed_dim, bias=True)
+
+    def conv_features(self, batch):
+        """``o`` [B, n_v d + L n_h]: what goes into the dropout."""
+        item_seq = batch['in_' + self.fiid]
+        if item_seq.size(1) < self.max_seq_len:
+            item_seq = torch.nn.functional.pad(item_seq, (0, self.max_seq_len - item_seq.size(1)))      # caser.py:39
+            batch = {k: v for k, v in batch.items() if k != '_seg'}
+            batch['in_' + self.fiid] = item_seq
+        rows = _history_rows(self.item_embedding, batch, self.fiid)
+        return caser_conv_torch(rows, *caser_pack(self.vertical_filter, self.horizontal_filter))
+
+    def forward(self, batch):
+        P_u = self.user_embedding(batch[self.fuid])
+        o = self.dropout(self.conv_features(batch))
+        z = torch.relu(self.fc(o))
+        return torch.cat((z, P_u), dim=1)

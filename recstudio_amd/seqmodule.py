@@ -43,6 +43,18 @@ fills with 0 -- there is no softmax --; ``b2`` reaches every live position.  ``q
 ONE launch of ``ops.ff_attention_pool`` (``rsa_ff_attention``, recstudio_amd/csrc/rsa_ffattn.hip), which never writes the
 ``[B, S, q_dim + k_dim]`` concatenation or the ``[B, S, M]`` hidden layer, and whose backward recomputes instead of saving.
 ``ff_attention_pool_torch`` is the twin: the reference's op sequence literally.
+
+THE CONVOLUTIONS OF CASER.  recstudio/model/seq/caser.py:36-56 runs, on the gathered history rows ``E`` [B, L, d] (right-padded
+with zero rows to ``L = max_seq_len``; there is no mask), one ``Conv2d(1, n_v, (L, 1))`` and L ``Conv2d(1, n_h, (h, d))``, h = 1 ..
+L, each of the latter under ``relu``, ``max_pool1d`` over its L - h + 1 windows and ``squeeze``, and two ``cat`` s:
+
+    o_v[b, c d + k] = b_v[c] + sum_t W_v[c, t] E[b, t, k]            o_h[b, (h - 1) n_h + c] = max(0, max_t conv_h[b, t, c])
+    conv_h[b, t, c] = b_h[c] + sum_{j < h} sum_k W_h[c, j, k] E[b, t + j, k]            o = cat(o_v, o_h)   [B, n_v d + L n_h]
+
+``caser_conv_torch`` is that op sequence on the filters PACKED: ``w_h`` = the L ``Conv2d.weight.reshape(-1)`` concatenated in
+height order (block h, [n_h, h, d], at element ``n_h d h (h - 1) / 2``), ``b_h`` [L, n_h] the biases alike -- one ``torch.cat`` each
+per call (``caser_pack``), whose own backward hands the slices of the gradient back to the L modules.  It is the operand layout a
+fused kernel would take; no such kernel ships, so the tower runs on torch ops.
 """
 import math
 
@@ -52,7 +64,7 @@ import torch.nn.functional as F
 from . import ops, rng
 
 __all__ = ['seq_attention', 'seq_attention_torch', 'FusedTransformerEncoder', 'gru_sequence', 'gru_sequence_torch', 'FusedGRU',
-           'ff_attention_pool', 'ff_attention_pool_torch', 'MLPModule', 'AttentionLayer']
+           'ff_attention_pool', 'ff_attention_pool_torch', 'MLPModule', 'AttentionLayer', 'caser_conv_torch', 'caser_pack']
 
 
 def allowed_keys(key_pad, causal, B, L, device):
@@ -348,6 +360,34 @@ def ff_attention_pool(query, key, w1, b1, w2, b2, key_pad=None):
             key_pad = key_pad.contiguous().view(torch.uint8)
         return _FfAttentionFn.apply(query, key, w1, b1, w2, b2, key_pad)
     return ff_attention_pool_torch(query, key, w1, b1, w2, b2, key_pad)
+
+
+def caser_pack(vertical_filter, horizontal_filter):
+    """``(w_v [n_v, L], b_v [n_v], w_h packed, b_h [L, n_h])`` of Caser's ``Conv2d`` modules: views for the vertical filter, ONE
+    ``torch.cat`` for the horizontal weights and one for their biases (``CatBackward`` hands the slices of the gradients back)."""
+    w_v = vertical_filter.weight.reshape(vertical_filter.weight.shape[0], -1)
+    w_h = torch.cat([conv.weight.reshape(-1) for conv in horizontal_filter])
+    b_h = torch.cat([conv.bias for conv in horizontal_filter]).view(len(horizontal_filter), -1)
+    return w_v, vertical_filter.bias, w_h, b_h
+
+
+def caser_conv_torch(rows, w_v, b_v, w_h, b_h):
+    """Caser's convolutions in the reference's own op sequence (recstudio/model/seq/caser.py:41-53) on the packed operands, any
+    float dtype: ``rows`` [B, L, d], ``w_v`` [n_v, L], ``b_v`` [n_v], ``w_h`` packed, ``b_h`` [L, n_h] -> ``o`` [B, n_v d + L n_h]."""
+    B, L, d = rows.shape
+    n_v, n_h = w_v.shape[0], b_h.shape[1]
+    x = rows.view(-1, 1, L, d)                                                   # caser.py:41
+    o_v = F.conv2d(x, w_v.view(n_v, 1, L, 1), b_v)                               # caser.py:43
+    o_v = o_v.reshape(o_v.size(0), -1)                                           # caser.py:44
+    o_h, at = [], 0
+    for i in range(L):                                                           # caser.py:47-50
+        h = i + 1
+        w = w_h[at:at + n_h * h * d].view(n_h, 1, h, d)
+        at += n_h * h * d
+        conv_out = torch.relu(F.conv2d(x, w, b_h[i]).squeeze(3))
+        pool_out = F.max_pool1d(conv_out, conv_out.size(2))
+        o_h.append(pool_out.squeeze(2))
+    return torch.cat((o_v, torch.cat(o_h, dim=1)), dim=1)                        # caser.py:51-53
 
 
 def get_act(activation, dim=None):
