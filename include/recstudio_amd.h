@@ -1090,6 +1090,55 @@ int64_t rsa_ff_attention_workspace_bytes(int64_t n_seq, int32_t seq_len, int32_t
 int rsa_ff_attention(const rsa_ff_attention_args* args, rsa_stream_t stream);
 int rsa_ff_attention_backward(const rsa_ff_attention_args* args, rsa_stream_t stream);
 
+/* Hierarchical gating of the sequence tower HGN, fused (recstudio/model/seq/hgn.py:31-43 between the gathers and `U +`):
+ *   f_bl = sigmoid(W1 s_bl + ug_b)   sf_bl = s_bl (.) f_bl   w_bl = sigmoid(w3 . sf_bl + ui_bl)   si_bl = sf_bl w_bl
+ *   mean: pooled_b = sum_l si_bl / sum_l w_bl     max: pooled_b[c] = max_l si_bl[c]     out_b = pooled_b + sum_l s_bl
+ * s fp32 [n_seq, seq_len, d] (padded positions are zero ROWS: there is no mask, they count in sum_l w and take part in the max
+ * with si = +0); ug fp32 [n_seq, d] = W_g_2 U + b_g and ui fp32 [n_seq, seq_len] = U W_g_4.weight[:seq_len]^T are the caller's
+ * GEMMs; w1 = W_g_1.weight [d, d], row c at w1 + c * w1_stride; w3 [d].  d is 32, 64 or 128; any seq_len >= 1; pooling 0 = mean,
+ * 1 = max.
+ * rsa_hgn_gating writes out [n_seq, d], w [n_seq, seq_len] and, for max pooling, arg int32 [n_seq, d] (the position of the
+ * maximum, the LOWEST one on exact ties) in one launch and nothing else.
+ * rsa_hgn_gating_backward takes the same inputs, g_out [n_seq, d] and the forward's w (and arg for max pooling), recomputes f and
+ * sf, and writes EVERY element of ds [n_seq, seq_len, d] (not zero at padded positions), dug [n_seq, d], dui [n_seq, seq_len],
+ * dw1 [d, d] (dense) and dw3 [d]:
+ *   mean: dsi = g_b / den_b, dw = -(g_b . pooled_b) / den_b     max: dsi[c] = l == arg_b[c] ? g_b[c] : 0, dw = 0
+ *   dw += dsi . sf   dz = dw w (1 - w)   dui = dz   dsf = dsi w + dz w3   dpre = (dsf (.) s) (.) f (1 - f)
+ *   ds = g_b + dsf (.) f + W1^T dpre   dug_b = sum_l dpre   dw1 = sum_bl dpre s^T   dw3 = sum_bl dz sf
+ * The sums over rows go through partial slots in `workspace` (rsa_hgn_gating_workspace_bytes) added in a fixed order by a last
+ * launch: no atomics, two runs are bit-equal.  64-bit element offsets.
+ * d outside {32, 64, 128}, seq_len < 1, negative n_seq, pooling outside {0, 1}, a null or misaligned (16 bytes: s, w1; w1_stride
+ * a multiple of 4, >= d) pointer, a workspace that is too small: RSA_ERR_ARG before the first HIP call.  n_seq == 0 returns 0 and
+ * launches nothing.  Nothing is allocated, nothing synchronises. */
+typedef struct rsa_hgn_gating_args {
+  int64_t size;                /* sizeof(rsa_hgn_gating_args) */
+  const float* s;              /* [n_seq, seq_len, d] */
+  const float* ug;             /* [n_seq, d] */
+  const float* ui;             /* [n_seq, seq_len] */
+  const float* w1;             /* [d, d], possibly a block of a wider buffer */
+  int64_t w1_stride;           /* floats between its rows */
+  const float* w3;             /* [d] */
+  int64_t n_seq;
+  int32_t seq_len;
+  int32_t d;
+  int32_t pooling;             /* 0 mean, 1 max */
+  int32_t reserved;            /* 0 */
+  float* out;                  /* forward: [n_seq, d] out */
+  float* w;                    /* [n_seq, seq_len]: forward out, backward in */
+  int32_t* arg;                /* max pooling, [n_seq, d]: forward out, backward in */
+  const float* g_out;          /* backward: [n_seq, d] */
+  float* ds;                   /* backward: [n_seq, seq_len, d] out */
+  float* dug;                  /* backward: [n_seq, d] out */
+  float* dui;                  /* backward: [n_seq, seq_len] out */
+  float* dw1;                  /* backward: [d, d] out */
+  float* dw3;                  /* backward: [d] out */
+  void* workspace;             /* backward */
+  int64_t workspace_bytes;     /* >= rsa_hgn_gating_workspace_bytes(n_seq, seq_len, d) */
+} rsa_hgn_gating_args;
+int64_t rsa_hgn_gating_workspace_bytes(int64_t n_seq, int32_t seq_len, int32_t d);
+int rsa_hgn_gating(const rsa_hgn_gating_args* args, rsa_stream_t stream);
+int rsa_hgn_gating_backward(const rsa_hgn_gating_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

@@ -307,6 +307,16 @@ class FfAttentionArgs(_Sized):
     ]
 
 
+class HgnGatingArgs(_Sized):
+    """struct rsa_hgn_gating_args."""
+    _fields_ = [
+        ('size', c_int64), ('s', c_void_p), ('ug', c_void_p), ('ui', c_void_p), ('w1', c_void_p), ('w1_stride', c_int64),
+        ('w3', c_void_p), ('n_seq', c_int64), ('seq_len', c_int32), ('d', c_int32), ('pooling', c_int32), ('reserved', c_int32),
+        ('out', c_void_p), ('w', c_void_p), ('arg', c_void_p), ('g_out', c_void_p), ('ds', c_void_p), ('dug', c_void_p),
+        ('dui', c_void_p), ('dw1', c_void_p), ('dw3', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -319,6 +329,7 @@ STRUCTS = {
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
     'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs, 'rsa_ff_attention_args': FfAttentionArgs,
+    'rsa_hgn_gating_args': HgnGatingArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -416,6 +427,9 @@ SIGNATURES = {
     'rsa_ff_attention_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32, c_int32]),
     'rsa_ff_attention': (c_int, [POINTER(FfAttentionArgs), c_void_p]),
     'rsa_ff_attention_backward': (c_int, [POINTER(FfAttentionArgs), c_void_p]),
+    'rsa_hgn_gating_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
+    'rsa_hgn_gating': (c_int, [POINTER(HgnGatingArgs), c_void_p]),
+    'rsa_hgn_gating_backward': (c_int, [POINTER(HgnGatingArgs), c_void_p]),
 }
 
 _lib = None

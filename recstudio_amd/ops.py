@@ -1877,3 +1877,85 @@ def ff_attention_pool_backward(key, qh, w_k, w2, b2, key_pad, g_out, *, scale):
     a.dkey, a.dqh, a.dw_k, a.dw2, a.db2 = ptr(dkey), ptr(dqh), ptr(dw_k), ptr(dw2[:M]), ptr(dw2[M:])
     _launch('rsa_ff_attention_backward', ctypes.byref(a))
     return dkey, dqh, dw_k, dw2[:M], dw2[M:]
+
+
+# ------------------------------------------------------------------ hierarchical gating (HGN)
+HGN_GATING_DIMS = (32, 64, 128)        # the embedding width: W_g_1 is kept in LDS (rsa_gating.hip)
+HGN_POOLING = {'mean': 0, 'max': 1}
+
+
+def _hgn_gating_args(who, S, ug, ui, w1, w3, pooling):
+    S, ug, ui = _need(S, torch.float32, 'S'), _need(ug, torch.float32, 'ug'), _need(ui, torch.float32, 'ui')
+    w1, w3 = _need_view(w1, torch.float32, 'w1'), _need(w3, torch.float32, 'w3')
+    if pooling not in HGN_POOLING:
+        raise ValueError(f'{who}: pooling must be one of {tuple(HGN_POOLING)}, got {pooling!r}')
+    if S.dim() != 3 or S.shape[1] < 1:
+        raise ValueError(f'{who}: S must be [B, L, D] with L >= 1, got {tuple(S.shape)}')
+    B, L, D = S.shape
+    if D not in HGN_GATING_DIMS:
+        raise ValueError(f'{who}: D must be one of {HGN_GATING_DIMS}, got {D}')
+    if tuple(w1.shape) != (D, D):
+        raise ValueError(f'{who}: w1 must be [{D}, {D}], got {tuple(w1.shape)}')
+    if w1.stride(1) != 1 or w1.stride(0) % 4 or w1.stride(0) < D or w1.data_ptr() % 16:
+        raise ValueError(f'{who}: w1 must be 16-byte aligned with unit column stride and a row stride that is a multiple of 4 '
+                         f'(got strides {w1.stride()}, offset {w1.storage_offset()})')
+    if tuple(ug.shape) != (B, D) or tuple(ui.shape) != (B, L) or w3.numel() != D:
+        raise ValueError(f'{who}: ug must be [{B}, {D}], ui [{B}, {L}] and w3 hold {D} elements, got {tuple(ug.shape)}, '
+                         f'{tuple(ui.shape)}, {tuple(w3.shape)}')
+    a = nat.HgnGatingArgs()
+    a.s, a.ug, a.ui, a.w1, a.w1_stride, a.w3 = ptr(S), ptr(ug), ptr(ui), ptr(w1), w1.stride(0), ptr(w3)
+    a.n_seq, a.seq_len, a.d, a.pooling = B, L, D, HGN_POOLING[pooling]
+    return a, (S, ug, ui, w1, w3), B, L, D
+
+
+@_on_device
+def hgn_gating(S, ug, ui, w1, w3, pooling='mean'):
+    """rsa_hgn_gating: HGN's feature gate, instance gate, pooling and item-item sum in one launch.  ``S`` fp32 [B, L, D] (padded
+    positions are zero rows: there is no mask); ``ug`` fp32 [B, D] = ``W_g_2(U) + b_g``; ``ui`` fp32 [B, L] =
+    ``U @ W_g_4.weight[:L].T``; ``w1`` fp32 [D, D] = ``W_g_1.weight``, read in place through its row stride; ``w3`` fp32 [D] (or
+    [1, D]); D in {32, 64, 128}, any L >= 1.  ``f = sigmoid(S w1^T + ug)``, ``sf = S * f``, ``w = sigmoid(sf . w3 + ui)``,
+    ``si = sf * w``; ``out = si.sum(1) / w.sum(1) + S.sum(1)`` ('mean') or ``si.max(1) + S.sum(1)`` ('max').
+    -> ``(out [B, D], w [B, L], arg)``: ``arg`` int32 [B, D], the position of the maximum (the lowest on exact ties), None for
+    'mean'.  Nothing of size B L D is written.  B = 0 returns empty tensors without a launch."""
+    a, keepalive, B, L, D = _hgn_gating_args('hgn_gating', S, ug, ui, w1, w3, pooling)
+    dev = keepalive[0].device
+    out = torch.empty(B, D, dtype=torch.float32, device=dev)
+    w = torch.empty(B, L, dtype=torch.float32, device=dev)
+    arg = torch.empty(B, D, dtype=torch.int32, device=dev) if pooling == 'max' else None
+    if B == 0:
+        return out, w, arg
+    a.out, a.w, a.arg = ptr(out), ptr(w), ptr(arg)
+    _launch('rsa_hgn_gating', ctypes.byref(a))
+    return out, w, arg
+
+
+@_on_device
+def hgn_gating_backward(S, ug, ui, w1, w3, w, arg, g_out, pooling='mean'):
+    """rsa_hgn_gating_backward: the gradients of ``hgn_gating`` from ``g_out`` (fp32 [B, D], the gradient of ``out``), the forward's
+    ``w`` [B, L] and, for 'max', its ``arg``.  The gates are recomputed from ``S`` and ``ug``.
+    -> ``(dS [B, L, D], dug [B, D], dui [B, L], dw1 [D, D], dw3 [D])``; every element is written; ``dS`` is NOT zero at padded
+    positions (the gather's backward drops them).  The gradients of ``W_g_2``, ``b_g``, ``W_g_4.weight[:L]`` and ``U`` follow from
+    ``dug`` and ``dui`` on the caller's side.  No atomics; bit-equal from run to run."""
+    a, keepalive, B, L, D = _hgn_gating_args('hgn_gating_backward', S, ug, ui, w1, w3, pooling)
+    g_out, w = _need(g_out, torch.float32, 'g_out'), _need(w, torch.float32, 'w')
+    if tuple(g_out.shape) != (B, D) or tuple(w.shape) != (B, L):
+        raise ValueError(f'hgn_gating_backward: g_out must be [{B}, {D}] and w [{B}, {L}], got {tuple(g_out.shape)}, {tuple(w.shape)}')
+    if pooling == 'max':
+        arg = _need(arg, torch.int32, 'arg')
+        if tuple(arg.shape) != (B, D):
+            raise ValueError(f'hgn_gating_backward: arg must be [{B}, {D}], got {tuple(arg.shape)}')
+    else:
+        arg = None
+    dev = keepalive[0].device
+    dS = torch.empty(B, L, D, dtype=torch.float32, device=dev)
+    dug = torch.empty(B, D, dtype=torch.float32, device=dev)
+    dui = torch.empty(B, L, dtype=torch.float32, device=dev)
+    if B == 0:
+        return dS, dug, dui, torch.zeros(D, D, dtype=torch.float32, device=dev), torch.zeros(D, dtype=torch.float32, device=dev)
+    dw1 = torch.empty(D, D, dtype=torch.float32, device=dev)
+    dw3 = torch.empty(D, dtype=torch.float32, device=dev)
+    ws, a.workspace_bytes = _workspace(dev, 'rsa_hgn_gating_workspace_bytes', B, L, D)
+    a.workspace, a.g_out, a.w, a.arg = ptr(ws), ptr(g_out), ptr(w), ptr(arg)
+    a.ds, a.dug, a.dui, a.dw1, a.dw3 = ptr(dS), ptr(dug), ptr(dui), ptr(dw1), ptr(dw3)
+    _launch('rsa_hgn_gating_backward', ctypes.byref(a))
+    return dS, dug, dui, dw1, dw3

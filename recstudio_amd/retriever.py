@@ -31,13 +31,17 @@ from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, Pairwise
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
 from .seqmodule import AttentionLayer, FusedGRU, FusedTransformerEncoder, MLPModule, caser_conv_torch, caser_pack
+from .seqmodule import hgn_gating, hgn_gating_torch
 
-__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'GRU4Rec', 'NARM', 'STAMP', 'LightGCN', 'SGL',
+__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'GRU4Rec', 'NARM', 'STAMP', 'HGN', 'LightGCN', 'SGL',
            'SimGCL', 'default_config', 'seed_everything']
 
 # ``model.fused_attention_pool`` of NARM and STAMP (the attention pooling as one HIP kernel): on where the kernel beat the
 # reference's op sequence in the same run, forward and forward + backward, at both models' shapes
 FUSED_ATTENTION_POOL_DEFAULT = True
+# ``model.fused_gating`` of HGN (both gates, the pooling and the item-item sum as one HIP kernel): on where the kernel beat the
+# reference's op sequence in the same run, forward and forward + backward, at both measured shapes
+FUSED_GATING_DEFAULT = True
 
 
 def default_config():
@@ -1839,3 +1843,72 @@ class CaserQueryEncoder(torch.nn.Module):
         o = self.dropout(self.conv_features(batch))
         z = torch.relu(self.fc(o))
         return torch.cat((z, P_u), dim=1)
+
+
+class HGNQueryEncoder(torch.nn.Module):
+    """recstudio/model/seq/hgn.py:16-44, same constructor arguments, same submodules (``user_embedding``, ``W_g_1``, ``W_g_2``,
+    ``b_g``, ``w_g_3``, ``W_g_4`` and the shared ``item_encoder``) and so the same ``state_dict``.  The history rows are gathered
+    through ``_history_rows``; ``ug = W_g_2(U) + b_g`` and ``ui = U @ W_g_4.weight[:L].T`` are torch GEMMs; everything per position
+    -- the feature gate, the instance gate, the pooling and ``S.sum(1)`` -- is ONE launch of ``seqmodule.hgn_gating`` with
+    ``fused_gating`` (a plain attribute, not a parameter), the reference's op sequence ``hgn_gating_torch`` without it or on CPU
+    tensors.  Two facts of the reference: ``b_g`` is ``torch.empty`` there and no initialiser touches a bare ``Parameter``, so it
+    trains from uninitialised memory -- here it starts at ZERO; ``W_g_4.bias`` exists, is saved and loaded, and
+    never receives a gradient.  No dropout: the generator is not consumed."""
+
+    def __init__(self, fuid, fiid, num_users, embed_dim, max_seq_len, item_encoder, pooling_type='mean', fused_gating=True) -> None:
+        super().__init__()
+        self.fuid = fuid
+        self.fiid = fiid
+        self.item_encoder = item_encoder
+        self.pooling_type = pooling_type
+        self.fused_gating = bool(fused_gating)
+        self.user_embedding = torch.nn.Embedding(num_users, embed_dim, 0)
+        self.W_g_1 = torch.nn.Linear(embed_dim, embed_dim, bias=False)
+        self.W_g_2 = torch.nn.Linear(embed_dim, embed_dim, bias=False)
+        self.b_g = torch.nn.Parameter(torch.zeros(embed_dim), requires_grad=True)
+        self.w_g_3 = torch.nn.Linear(embed_dim, 1, bias=False)
+        self.W_g_4 = torch.nn.Linear(embed_dim, max_seq_len)
+
+    def forward(self, batch):
+        if self.pooling_type not in ('mean', 'max'):
+            raise ValueError("`pooling_type` only support `avg` and `max`")                           # hgn.py:42
+        U = self.user_embedding(batch[self.fuid])                                                     # B x D
+        S = _history_rows(self.item_encoder, batch, self.fiid)                                        # B x L x D
+        ug = self.W_g_2(U) + self.b_g
+        ui = U @ self.W_g_4.weight[:S.size(1)].T                                                      # B x L
+        gate = hgn_gating if self.fused_gating else hgn_gating_torch
+        return U + gate(S, ug, ui, self.W_g_1.weight, self.w_g_3.weight.view(-1), self.pooling_type)
+
+
+class HGN(BaseRetriever):
+    """recstudio/model/seq/hgn.py:47-68 with the retriever tail on the fused BPR path."""
+
+    def __init__(self, config=None, **kwargs):
+        # recstudio/model/seq/config/hgn.yaml on top of basemodel.yaml; the caller's config wins
+        user = config or {}
+        super().__init__(config, **kwargs)
+        m = self.config['model']
+        for k, v in (('pooling_type', 'mean'), ('fused_gating', FUSED_GATING_DEFAULT)):
+            m.setdefault(k, v)
+        if 'negative_count' not in user.get('train', {}):
+            self.config['train']['negative_count'] = 1
+
+    def _get_dataset_class():
+        return SeqDataset
+
+    def _get_query_encoder(self, train_data):
+        m = self.config['model']
+        return HGNQueryEncoder(self.fuid, self.fiid, train_data.num_users, self.embed_dim, train_data.config['max_seq_len'],
+                               self.item_encoder, m['pooling_type'], fused_gating=m['fused_gating'])
+
+    def _get_query_feat(self, data):
+        return data if isinstance(data, dict) else super()._get_query_feat(data)
+
+    def _get_score_func(self):
+        return InnerProductScorer()
+
+    def _get_loss_func(self):
+        return BPRLoss()
+
+    def _get_sampler(self, train_data):
+        return UniformSampler(train_data.num_items)

@@ -55,6 +55,18 @@ L, each of the latter under ``relu``, ``max_pool1d`` over its L - h + 1 windows 
 height order (block h, [n_h, h, d], at element ``n_h d h (h - 1) / 2``), ``b_h`` [L, n_h] the biases alike -- one ``torch.cat`` each
 per call (``caser_pack``), whose own backward hands the slices of the gradient back to the L modules.  It is the operand layout a
 fused kernel would take; no such kernel ships, so the tower runs on torch ops.
+
+THE GATES OF HGN.  recstudio/model/seq/hgn.py:34-43 runs, on the gathered history rows ``S`` [B, L, d] (padded positions are the
+zero row; there is NO mask) and the user row ``U`` [B, d]:
+
+    f = sigmoid(W_g_1 s + ug)      sf = s * f      w = sigmoid(w_g_3 . sf + ui)      si = sf * w
+    mean: pooled = sum_l si / sum_l w        max: pooled[c] = max_l si[c]        out = pooled + sum_l s        query = U + out
+
+with ``ug = W_g_2 U + b_g`` [B, d] and ``ui = U W_g_4.weight[:L]^T`` [B, L] (``W_g_4.bias`` is never used).  Padded positions
+have ``si = 0`` but ``w = sigmoid(ui) > 0``: they count in the mean's denominator and take part in the max.  ``ug`` and ``ui``
+stay torch GEMMs; everything per position is ONE launch of ``ops.hgn_gating`` (``rsa_hgn_gating``,
+recstudio_amd/csrc/rsa_gating.hip), which writes ``out``, ``w`` [B, L] and the max's positions and none of the reference's eight
+``[B, L, d]`` temporaries; the backward recomputes the gates.  ``hgn_gating_torch`` is the twin: the reference's op sequence.
 """
 import math
 
@@ -64,7 +76,8 @@ import torch.nn.functional as F
 from . import ops, rng
 
 __all__ = ['seq_attention', 'seq_attention_torch', 'FusedTransformerEncoder', 'gru_sequence', 'gru_sequence_torch', 'FusedGRU',
-           'ff_attention_pool', 'ff_attention_pool_torch', 'MLPModule', 'AttentionLayer', 'caser_conv_torch', 'caser_pack']
+           'ff_attention_pool', 'ff_attention_pool_torch', 'MLPModule', 'AttentionLayer', 'caser_conv_torch', 'caser_pack',
+           'hgn_gating', 'hgn_gating_torch']
 
 
 def allowed_keys(key_pad, causal, B, L, device):
@@ -360,6 +373,58 @@ def ff_attention_pool(query, key, w1, b1, w2, b2, key_pad=None):
             key_pad = key_pad.contiguous().view(torch.uint8)
         return _FfAttentionFn.apply(query, key, w1, b1, w2, b2, key_pad)
     return ff_attention_pool_torch(query, key, w1, b1, w2, b2, key_pad)
+
+
+def hgn_gating_torch(S, ug, ui, w1, w3, pooling='mean'):
+    """HGN's gates, pooling and item-item sum in the reference's own op sequence (recstudio/model/seq/hgn.py:34-43), any float
+    dtype: ``S`` [B, L, d], ``ug`` [B, d] = ``W_g_2(U) + b_g``, ``ui`` [B, L] = ``U @ W_g_4.weight[:L].T``, ``w1`` [d, d], ``w3``
+    [1, d] -> ``out`` [B, d] = the query without its ``U +``."""
+    S_F = S * torch.sigmoid(F.linear(S, w1) + ug.view(ug.size(0), 1, -1))        # hgn.py:34
+    weight = torch.sigmoid(F.linear(S_F, w3.view(1, -1)) + ui.view(ui.size(0), -1, 1))   # hgn.py:35   B x L x 1
+    S_I = S_F * weight                                                           # hgn.py:36
+    if pooling == 'mean':
+        s = S_I.sum(1) / weight.sum(1)                                           # hgn.py:38
+    elif pooling == 'max':
+        s = torch.max(S_I, dim=1).values                                         # hgn.py:40
+    else:
+        raise ValueError("`pooling_type` only support `avg` and `max`")          # hgn.py:42
+    return s + S.sum(1)                                                          # hgn.py:43
+
+
+class _HgnGatingFn(torch.autograd.Function):
+    """``ops.hgn_gating`` / ``ops.hgn_gating_backward`` as one autograd node.  Saved: the inputs, ``w`` [B, L] and (max) ``arg``
+    [B, d] -- nothing of size B L d beyond ``S`` itself; the backward recomputes the gates."""
+
+    @staticmethod
+    def forward(ctx, S, ug, ui, w1, w3, pooling):
+        S, ug, ui = S.detach().contiguous(), ug.detach().contiguous(), ui.detach().contiguous()
+        w1, w3 = w1.detach(), w3.detach()
+        out, w, arg = ops.hgn_gating(S, ug, ui, w1, w3, pooling)
+        ctx.save_for_backward(S, ug, ui, w1, w3, w, arg)
+        ctx.pooling = pooling
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        S, ug, ui, w1, w3, w, arg = ctx.saved_tensors
+        dS, dug, dui, dw1, dw3 = ops.hgn_gating_backward(S, ug, ui, w1, w3, w, arg, g_out.contiguous(), ctx.pooling)
+        return dS, dug, dui, dw1, dw3.view_as(w3), None
+
+
+def hgn_gating_kernel_ok(S, ug, ui, w1, w3):
+    """Whether ``ops.hgn_gating`` takes these tensors: fp32 on the device, width in ``ops.HGN_GATING_DIMS``, ``L >= 1``."""
+    return (all(t.is_cuda and t.dtype == torch.float32 for t in (S, ug, ui, w1, w3)) and S.dim() == 3 and S.shape[1] >= 1
+            and S.shape[2] in ops.HGN_GATING_DIMS and w1.stride(1) == 1 and w1.stride(0) % 4 == 0 and w1.data_ptr() % 16 == 0)
+
+
+def hgn_gating(S, ug, ui, w1, w3, pooling='mean'):
+    """``out`` [B, d] of HGN's gating: the fused kernel where ``hgn_gating_kernel_ok``, ``hgn_gating_torch`` otherwise (CPU
+    tensors: the parity path; widths the kernel does not take)."""
+    if pooling not in ('mean', 'max'):
+        raise ValueError("`pooling_type` only support `avg` and `max`")
+    if hgn_gating_kernel_ok(S, ug, ui, w1, w3):
+        return _HgnGatingFn.apply(S, ug, ui, w1, w3, pooling)
+    return hgn_gating_torch(S, ug, ui, w1, w3, pooling)
 
 
 def caser_pack(vertical_filter, horizontal_filter):
