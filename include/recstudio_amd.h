@@ -1139,6 +1139,80 @@ int64_t rsa_hgn_gating_workspace_bytes(int64_t n_seq, int32_t seq_len, int32_t d
 int rsa_hgn_gating(const rsa_hgn_gating_args* args, rsa_stream_t stream);
 int rsa_hgn_gating_backward(const rsa_hgn_gating_args* args, rsa_stream_t stream);
 
+/* One augmented view of a batch of histories for the contrastive sequence retrievers (CL4SRec: recstudio/model/seq/cl4srec.py;
+ * Item_Crop / Item_Mask / Item_Reorder, recstudio/model/module/data_augmentation.py:22-87), one launch.  The random choices are
+ * the elements of ONE torch.rand([n_seq, seq_len + 1]) call for the given Philox state: U[b, 0] draws the start, U[b, 1 + p] is
+ * the key of position p (the same layout for all three kinds).
+ *   len   = clamp(seqlen[b], 0, seq_len)      n_sub = clamp(sub[len], 0, len)      sub int32 [seq_len + 1]: the caller's length
+ *           table (the reference's max(1, int(tau n)) / int(gamma n) / int(beta n), taken in float64 on the host; sub[0] = 0)
+ *   span  = max(len - n_sub + 1, 1)           start = min((int)(U[b, 0] * (float)span), span - 1)    (one fp32 product)
+ *   RSA_SEQAUG_CROP    out[b, p] = p < n_sub ? seq[b, start + p] : 0;                                          new_len = n_sub
+ *   RSA_SEQAUG_MASK    out[b, p] = mask_id where p < len and rank(p) < n_sub, else seq[b, p];                  new_len = len
+ *                      rank(p) = #{q < len : U[b, 1 + q] < U[b, 1 + p], or equal and q < p}
+ *   RSA_SEQAUG_REORDER out[b, start + rank(p)] = seq[b, p] for p in [start, start + n_sub), ranked among themselves the same way;
+ *                      every other position is copied;                                                         new_len = len
+ *   a row with len == 0 is copied and gets new_len = 0.
+ * seq int64 [n_seq, seq_len], row b at seq + b * seq_stride (right-padded with 0); seqlen / new_len [n_seq] are int32 or int64
+ * (seqlen_bytes 4 or 8); out int64 [n_seq, seq_len] dense, not aliasing seq.  seq_len <= RSA_SEQAUG_MAX_LEN: one lane per position
+ * and one wave per sequence; no atomics, no workspace, two runs are bit-equal; nothing outside [0, seq_len) of a row is read.
+ * seq_len outside [1, 64], an unknown kind, seqlen_bytes not 4 / 8, a negative n_seq, a null pointer, seq_stride < seq_len, out ==
+ * seq: RSA_ERR_ARG before the first HIP call.  n_seq == 0 returns 0 and launches nothing.  Nothing is allocated, nothing
+ * synchronises. */
+enum rsa_seqaug_kind { RSA_SEQAUG_CROP = 0, RSA_SEQAUG_MASK = 1, RSA_SEQAUG_REORDER = 2 };
+#define RSA_SEQAUG_MAX_LEN 64
+typedef struct rsa_seq_augment_args {
+  int64_t size;                /* sizeof(rsa_seq_augment_args) */
+  const int64_t* seq;          /* [n_seq, seq_len], possibly a block of a wider buffer */
+  int64_t seq_stride;          /* elements between its rows */
+  const void* seqlen;          /* [n_seq], int32 or int64 */
+  const int32_t* sub;          /* [seq_len + 1] */
+  int64_t n_seq;
+  int64_t mask_id;
+  int32_t seq_len;
+  int32_t kind;                /* rsa_seqaug_kind */
+  int32_t seqlen_bytes;        /* 4 or 8: the element size of seqlen and new_len */
+  uint32_t grid_threads;       /* Philox state of the torch.rand([n_seq, seq_len + 1]) call this stands for */
+  uint64_t seed;
+  uint64_t offset;
+  uint64_t elem_base;
+  int64_t* out;                /* [n_seq, seq_len] out */
+  void* new_len;               /* [n_seq] out, the element type of seqlen */
+} rsa_seq_augment_args;
+int rsa_seq_augment(const rsa_seq_augment_args* args, rsa_stream_t stream);
+
+/* In-batch InfoNCE of the contrastive sequence retrievers (InfoNCELoss neg_type 'batch_both' / 'batch_single',
+ * recstudio/model/module/data_augmentation.py:324-376) without anything of size n_rows^2.  zi, zj fp32 [n_rows, d] dense, 16-byte
+ * aligned (normalised by the caller for 'cosine'); d is 32, 64 or 128; any n_rows.  The logit set of row b:
+ *   s_ij[b, k] = <zi_b, zj_k> inv_t for every k except those with k != b and labels[k] == labels[b];
+ *   with `both` also s_ii[b, k] = <zi_b, zi_k> inv_t for every k != b whose label differs (labels null: every k != b).
+ * rsa_batch_infonce writes lse[b] = log sum exp over the set and pos[b] = s_ij[b, b]; the loss is mean(lse - pos), the caller's.
+ * rsa_batch_infonce_backward takes the same inputs, the forward's lse and g [n_rows] (the upstream of lse - pos), recomputes
+ * P = exp(s - lse_b) on the fp32 matrix cores and writes every element of
+ *   dzi_b = inv_t [ g_b (sum_k P_ij[b, k] zj_k + sum_k P_ii[b, k] zi_k - zj_b) + sum_r g_r P_ii[r, b] zi_r ]
+ *   dzj_k = inv_t [ sum_b g_b P_ij[b, k] zi_b - g_k zi_k ]
+ * in two launches (rows of zi stationary, then rows of zj stationary).  Nothing is saved but lse; no atomics, no workspace, two
+ * runs are bit-equal; rows past n_rows are never read.  d outside {32, 64, 128}, a negative n_rows, inv_t not positive and
+ * finite, a null or misaligned zi / zj, a null lse (/ pos / g / dzi / dzj), dzi or dzj aliasing an input or each other:
+ * RSA_ERR_ARG before the first HIP call.  n_rows == 0 returns 0 and launches nothing.  Nothing is allocated, nothing synchronises. */
+typedef struct rsa_batch_infonce_args {
+  int64_t size;                /* sizeof(rsa_batch_infonce_args) */
+  const float* zi;             /* [n_rows, d] */
+  const float* zj;             /* [n_rows, d] */
+  const int64_t* labels;       /* nullable [n_rows] */
+  int64_t n_rows;
+  int32_t d;
+  int32_t both;                /* non-zero: the s_ii block too ('batch_both') */
+  float inv_t;                 /* 1 / temperature */
+  int32_t reserved;            /* 0 */
+  float* lse;                  /* [n_rows]: forward out, backward in */
+  float* pos;                  /* forward: [n_rows] out */
+  const float* g;              /* backward: [n_rows] */
+  float* dzi;                  /* backward: [n_rows, d] out */
+  float* dzj;                  /* backward: [n_rows, d] out */
+} rsa_batch_infonce_args;
+int rsa_batch_infonce(const rsa_batch_infonce_args* args, rsa_stream_t stream);
+int rsa_batch_infonce_backward(const rsa_batch_infonce_args* args, rsa_stream_t stream);
+
 /* Backward of logsumexp over the full catalog (SoftmaxLoss, loss_func.py:39-47, when the forward was
  * rsa_fullscore(..., lse) and [B, N-1] was never written):  probs[b, i-1] = row_scale[b] * exp(<q_b, item_i> - lse[b])
  * = row_scale[b] * softmax_i, recomputed by the same MFMA kernel.  d lse/d query = probs @ items[1:],

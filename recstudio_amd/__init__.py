@@ -17,7 +17,7 @@ from .loss_func import (FullScoreLoss, PairwiseLoss, PointwiseLoss, BPRLoss,   #
 from .fused import retriever_scores                               # noqa: F401
 from .dataset import TripletDataset, SeqDataset, DataSampler, SortedDataSampler   # noqa: F401
 from .retriever import (BaseRetriever, TwoTowerRecommender, ItemTowerRecommender, BPR, SASRec, LightGCN,   # noqa: F401
-                        SGL, SimGCL, NGCF, GRU4Rec, NARM, STAMP, HGN, HGNQueryEncoder, default_config, seed_everything)
+                        SGL, SimGCL, NGCF, CL4SRec, GRU4Rec, NARM, STAMP, HGN, HGNQueryEncoder, default_config, seed_everything)
 from . import graphmodule                                         # noqa: F401
 from . import seqmodule                                           # noqa: F401
 from .seqmodule import FusedTransformerEncoder, seq_attention_torch, FusedGRU, gru_sequence_torch   # noqa: F401

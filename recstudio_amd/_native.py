@@ -317,6 +317,24 @@ class HgnGatingArgs(_Sized):
     ]
 
 
+class SeqAugmentArgs(_Sized):
+    """struct rsa_seq_augment_args."""
+    _fields_ = [
+        ('size', c_int64), ('seq', c_void_p), ('seq_stride', c_int64), ('seqlen', c_void_p), ('sub', c_void_p), ('n_seq', c_int64),
+        ('mask_id', c_int64), ('seq_len', c_int32), ('kind', c_int32), ('seqlen_bytes', c_int32), ('grid_threads', c_uint32),
+        ('seed', c_uint64), ('offset', c_uint64), ('elem_base', c_uint64), ('out', c_void_p), ('new_len', c_void_p),
+    ]
+
+
+class BatchInfoNceArgs(_Sized):
+    """struct rsa_batch_infonce_args."""
+    _fields_ = [
+        ('size', c_int64), ('zi', c_void_p), ('zj', c_void_p), ('labels', c_void_p), ('n_rows', c_int64), ('d', c_int32),
+        ('both', c_int32), ('inv_t', c_float), ('reserved', c_int32), ('lse', c_void_p), ('pos', c_void_p), ('g', c_void_p),
+        ('dzi', c_void_p), ('dzj', c_void_p),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -329,7 +347,8 @@ STRUCTS = {
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
     'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs, 'rsa_ff_attention_args': FfAttentionArgs,
-    'rsa_hgn_gating_args': HgnGatingArgs,
+    'rsa_hgn_gating_args': HgnGatingArgs, 'rsa_seq_augment_args': SeqAugmentArgs,
+    'rsa_batch_infonce_args': BatchInfoNceArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -430,6 +449,9 @@ SIGNATURES = {
     'rsa_hgn_gating_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
     'rsa_hgn_gating': (c_int, [POINTER(HgnGatingArgs), c_void_p]),
     'rsa_hgn_gating_backward': (c_int, [POINTER(HgnGatingArgs), c_void_p]),
+    'rsa_seq_augment': (c_int, [POINTER(SeqAugmentArgs), c_void_p]),
+    'rsa_batch_infonce': (c_int, [POINTER(BatchInfoNceArgs), c_void_p]),
+    'rsa_batch_infonce_backward': (c_int, [POINTER(BatchInfoNceArgs), c_void_p]),
 }
 
 _lib = None

@@ -1959,3 +1959,98 @@ def hgn_gating_backward(S, ug, ui, w1, w3, w, arg, g_out, pooling='mean'):
     a.ds, a.dug, a.dui, a.dw1, a.dw3 = ptr(dS), ptr(dug), ptr(dui), ptr(dw1), ptr(dw3)
     _launch('rsa_hgn_gating_backward', ctypes.byref(a))
     return dS, dug, dui, dw1, dw3
+
+
+# ------------------------------------------------------------------ sequence views (CL4SRec)
+SEQ_AUGMENT_MAX_LEN = 64          # one lane per position, one wave per sequence (rsa_seqaug.hip)
+SEQ_AUGMENT_KINDS = {'crop': 0, 'mask': 1, 'reorder': 2}
+
+
+def seq_augment(seq, seqlen, kind, sub, mask_id=0, generator=None):
+    """rsa_seq_augment: one augmented view of the histories ``seq`` (int64 [B, L], right-padded with 0, read in place through its
+    row stride; L <= 64) of lengths ``seqlen`` ([B] int32 / int64, clamped into [0, L] by the kernel) in one launch.  ``kind`` is
+    'crop', 'mask' or 'reorder'; ``sub`` (int32 [L + 1] on the device) is the table ``len -> n_sub``.  The random choices are
+    ``U = torch.rand([B, L + 1], device=...)`` on the device generator, which is advanced as that call would advance it: ``U[b, 0]``
+    draws the start, ``U[b, 1 + p]`` is the key of position p (``data_augmentation.seq_augment_torch`` is the rule in torch ops).
+    -> ``(out int64 [B, L], new_len [B] in seqlen's dtype)``.  No atomics; bit-equal from run to run."""
+    if kind not in SEQ_AUGMENT_KINDS:
+        raise ValueError(f"seq_augment: kind must be 'crop', 'mask' or 'reorder', got {kind!r}")
+    return _seq_augment(seq, seqlen, SEQ_AUGMENT_KINDS[kind], sub, int(mask_id), generator)
+
+
+@_on_device
+def _seq_augment(seq, seqlen, kind, sub, mask_id, generator):
+    seq = _need_view(seq, torch.int64, 'seq')
+    if seq.dim() != 2:
+        raise ValueError(f'seq_augment: seq must be [B, L], got {tuple(seq.shape)}')
+    B, L = seq.shape
+    if not 1 <= L <= SEQ_AUGMENT_MAX_LEN:
+        raise ValueError(f'seq_augment: L must lie in [1, {SEQ_AUGMENT_MAX_LEN}], got {L}')
+    if B and (seq.stride(1) != 1 or seq.stride(0) < L):
+        seq = seq.contiguous()
+    if seqlen.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f'seq_augment: seqlen must be int32 or int64, got {seqlen.dtype}')
+    seqlen = _need(seqlen, seqlen.dtype, 'seqlen')
+    sub = _need(sub, torch.int32, 'sub')
+    if seqlen.numel() != B or sub.numel() != L + 1:
+        raise ValueError(f'seq_augment: seqlen must hold {B} lengths and sub {L + 1} entries, got {seqlen.numel()} and {sub.numel()}')
+    out = torch.empty(B, L, dtype=torch.int64, device=seq.device)
+    new_len = torch.empty(B, dtype=seqlen.dtype, device=seq.device)
+    if B == 0:
+        return out, new_len
+    pc = rng.reserve(B * (L + 1), 4, seq.device, generator)
+    a = nat.SeqAugmentArgs()
+    a.seq, a.seq_stride, a.seqlen, a.sub, a.n_seq, a.mask_id = ptr(seq), seq.stride(0), ptr(seqlen), ptr(sub), B, int(mask_id)
+    a.seq_len, a.kind, a.seqlen_bytes = L, kind, seqlen.element_size()
+    a.seed, a.offset, a.grid_threads, a.elem_base = pc.seed, pc.offset, pc.grid_threads, pc.elem_base
+    a.out, a.new_len = ptr(out), ptr(new_len)
+    _launch('rsa_seq_augment', ctypes.byref(a))
+    return out, new_len
+
+
+# ------------------------------------------------------------------ in-batch InfoNCE (CL4SRec)
+BATCH_INFONCE_DIMS = (32, 64, 128)
+
+
+def _batch_infonce_args(who, zi, zj, inv_t, both, labels):
+    zi, zj = _need(zi, torch.float32, 'zi'), _need(zj, torch.float32, 'zj')
+    if zi.dim() != 2 or zi.shape != zj.shape:
+        raise ValueError(f'{who}: zi and zj must be [B, d] of one shape, got {tuple(zi.shape)} and {tuple(zj.shape)}')
+    B, d = zi.shape
+    if d not in BATCH_INFONCE_DIMS:
+        raise ValueError(f'{who}: d must be one of {BATCH_INFONCE_DIMS}, got {d}')
+    labels = _need_opt(labels, torch.int64, 'labels')
+    if labels is not None and tuple(labels.shape) != (B,):
+        raise ValueError(f'{who}: labels must hold one label per row')
+    a = nat.BatchInfoNceArgs()
+    a.zi, a.zj, a.labels, a.n_rows, a.d, a.both, a.inv_t = ptr(zi), ptr(zj), ptr(labels), B, d, int(bool(both)), float(inv_t)
+    return a, (zi, zj, labels), B, d
+
+
+@_on_device
+def batch_infonce(zi, zj, inv_t, both=True, labels=None):
+    """rsa_batch_infonce: ``lse`` [B] and ``pos`` [B] of the in-batch InfoNCE of ``zi``, ``zj`` (fp32 [B, d], d in 32 / 64 / 128;
+    normalised by the caller for 'cosine') without a [B, 2B] matrix.  Row b's logits are ``<zi_b, zj_k> inv_t`` for every k but those
+    with ``k != b`` and ``labels[k] == labels[b]`` and, with ``both``, ``<zi_b, zi_k> inv_t`` for every ``k != b`` whose label differs
+    (no ``labels``: every ``k != b``); ``pos_b = <zi_b, zj_b> inv_t``.  The loss is ``mean(lse - pos)``."""
+    a, keepalive, B, d = _batch_infonce_args('batch_infonce', zi, zj, inv_t, both, labels)
+    lse = torch.empty(B, dtype=torch.float32, device=keepalive[0].device)
+    pos = torch.empty(B, dtype=torch.float32, device=keepalive[0].device)
+    a.lse, a.pos = ptr(lse), ptr(pos)
+    _launch('rsa_batch_infonce', ctypes.byref(a))
+    return lse, pos
+
+
+@_on_device
+def batch_infonce_backward(zi, zj, inv_t, both, labels, lse, g):
+    """rsa_batch_infonce_backward: ``(dzi, dzj)`` from the forward's ``lse`` and ``g`` [B], the upstream of ``lse - pos``; the
+    softmax is recomputed from ``lse`` on the matrix cores (a row-stationary and a key-stationary pass).  No float atomics; two runs
+    are bit-equal."""
+    a, keepalive, B, d = _batch_infonce_args('batch_infonce_backward', zi, zj, inv_t, both, labels)
+    lse, g = _need(lse, torch.float32, 'lse'), _need(g, torch.float32, 'g')
+    if tuple(lse.shape) != (B,) or tuple(g.shape) != (B,):
+        raise ValueError(f'batch_infonce_backward: lse and g must be [{B}], got {tuple(lse.shape)} and {tuple(g.shape)}')
+    dzi, dzj = torch.empty_like(keepalive[0]), torch.empty_like(keepalive[1])
+    a.lse, a.g, a.dzi, a.dzj = ptr(lse), ptr(g), ptr(dzi), ptr(dzj)
+    _launch('rsa_batch_infonce_backward', ctypes.byref(a))
+    return dzi, dzj

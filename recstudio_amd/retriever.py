@@ -14,6 +14,7 @@ it is a minimal compatible one (the reference's Recommender loop is out of scope
 import copy
 import inspect
 import logging
+import math
 import os
 import time
 from typing import Dict
@@ -33,12 +34,17 @@ from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
 from .seqmodule import AttentionLayer, FusedGRU, FusedTransformerEncoder, MLPModule, caser_conv_torch, caser_pack
 from .seqmodule import hgn_gating, hgn_gating_torch
 
-__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'GRU4Rec', 'NARM', 'STAMP', 'HGN', 'LightGCN', 'SGL',
+__all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'CL4SRec', 'GRU4Rec', 'NARM', 'STAMP', 'HGN', 'LightGCN', 'SGL',
            'SimGCL', 'default_config', 'seed_everything']
 
 # ``model.fused_attention_pool`` of NARM and STAMP (the attention pooling as one HIP kernel): on where the kernel beat the
 # reference's op sequence in the same run, forward and forward + backward, at both models' shapes
 FUSED_ATTENTION_POOL_DEFAULT = True
+# ``model.fused_infonce`` of CL4SRec (the in-batch InfoNCE as HIP kernels without [B, 2B]): OFF.  The rule is on only where the kernels
+# are not slower than the reference's op sequence at every measured shape in both directions (tools/bench_cl4srec.py,
+# ``fused_infonce_wins_everywhere``); they win at B = 256 and lose at B = 8192 (2.11 against 1.19 ms forward, 6.07 against 2.30 ms
+# forward + backward at d = 64), where what they buy is memory: 1.7 GB less
+FUSED_INFONCE_DEFAULT = False
 # ``model.fused_gating`` of HGN (both gates, the pooling and the item-item sum as one HIP kernel): on where the kernel beat the
 # reference's op sequence in the same run, forward and forward + backward, at both measured shapes
 FUSED_GATING_DEFAULT = True
@@ -1506,12 +1512,22 @@ class SASRecQueryEncoder(torch.nn.Module):
     """recstudio/model/seq/sasrec.py:8-67: item-embedding gather of the history (HIP) + learned positions
     + nn.TransformerEncoder (causal unless ``bidirectional``) + last-position pooling.  The encoder is stock PyTorch-ROCm by
     default; with ``fused_attention`` its layers run through ``seqmodule.FusedTransformerEncoder`` (the attention core as one
-    HIP kernel) over the same parameters: ``state_dict`` is the same either way."""
+    HIP kernel) over the same parameters: ``state_dict`` is the same either way.
+
+    ``need_pooling=False`` returns the tower's ``[B, L, D]`` (what CL4SRec's views are mean-pooled from).  With ``mask_id`` (CL4SRec:
+    ``num_items``) the encoder owns ``mask_emb`` [1, D], the row of the mask token: the ids
+    equal to ``mask_id`` are gathered as row 0 (the zero padding row) through the same gather node and ``mask_emb`` is added at those
+    positions, while ``key_pad`` stays ``ids == 0`` on the ORIGINAL ids, so masked positions are attended.  The catalog table keeps
+    its ``num_items`` rows (the reference widens it by one, cl4srec.py:33-34): ``mask_id`` never reaches the gather, the sampler or
+    ``topk``."""
 
     def __init__(self, fiid, embed_dim, max_seq_len, n_head, hidden_size, dropout, activation, layer_norm_eps, n_layer,
-                 item_encoder, bidirectional=False, fused_attention=False):
+                 item_encoder, bidirectional=False, fused_attention=False, mask_id=None):
         super().__init__()
         self.fiid = fiid
+        self.mask_id = mask_id
+        if mask_id is not None:
+            self.mask_emb = torch.nn.Parameter(torch.zeros(1, embed_dim))
         self.item_encoder = item_encoder
         self.bidirectional = bool(bidirectional)
         self.fused_attention = bool(fused_attention)
@@ -1524,24 +1540,33 @@ class SASRecQueryEncoder(torch.nn.Module):
         # (no parameters of its own: it reads transformer_layer's at call time)
         self._fused = FusedTransformerEncoder(self.transformer_layer, max_seq_len) if self.fused_attention else None
 
-    def forward(self, batch):
+    def forward(self, batch, need_pooling=True):
         user_hist = batch['in_' + self.fiid]
         B, L = user_hist.shape
         positions = torch.arange(L, dtype=torch.long, device=user_hist.device).unsqueeze(0).expand(B, L)
         seg = batch.get('_seg')
+        masked = None
+        ids = user_hist
+        if self.mask_id is not None and seg is None:
+            # any ids handed over as a tensor (a view of CL4SRec): the mask token is no catalog row.  (The CSR view of the loader
+            # gathers from the dataset's own item column, which holds no mask token.)
+            masked = user_hist == self.mask_id
+            ids = torch.where(masked, torch.zeros_like(user_hist), user_hist)
         if not isinstance(self.item_encoder, torch.nn.Embedding):
             # the row-sharded catalog (shard.ShardedRows put here by BaseRetriever._setup_shard): ids out, rows back
-            rows = self.item_encoder(user_hist)
-        elif self._fused is not None and not user_hist.is_cuda:
+            rows = self.item_encoder(ids)
+        elif not user_hist.is_cuda and (self._fused is not None or self.mask_id is not None):
             # the torch-op twin of the fused tower (seqmodule.seq_attention_torch) on CPU tensors: parity checks without a device
-            rows = self.item_encoder(user_hist)
+            rows = self.item_encoder(ids)
         elif seg is not None and user_hist.is_cuda:
             # the device loader handed over the CSR view (flat item column, start, end): the fused segment gather emits
             # [B, L, d] directly; ``in_item_id`` only serves the padding mask and the backward
             flat, start, end = seg
             rows = _SegEmbedFn.apply(self.item_encoder.weight, flat, start, end, L, user_hist)
         else:
-            rows = _EmbedFn.apply(self.item_encoder.weight, user_hist)
+            rows = _EmbedFn.apply(self.item_encoder.weight, ids)
+        if masked is not None:
+            rows = rows + masked.unsqueeze(-1).to(rows.dtype) * self.mask_emb
         seq = rows + self.position_emb(positions)
         if self._fused is not None:
             out = self._fused(self.dropout(seq), key_pad=user_hist == 0, causal=not self.bidirectional)
@@ -1551,6 +1576,8 @@ class SASRecQueryEncoder(torch.nn.Module):
             else:
                 mask = torch.triu(torch.ones(L, L, dtype=torch.bool, device=user_hist.device), 1)
             out = self.transformer_layer(self.dropout(seq), mask=mask, src_key_padding_mask=user_hist == 0)
+        if not need_pooling:
+            return out
         last = (batch['seqlen'] - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, out.shape[-1])
         return out.gather(1, last).squeeze(1)
 
@@ -1587,6 +1614,80 @@ class SASRec(BaseRetriever):
 
     def _get_sampler(self, train_data):
         return UniformSampler(train_data.num_items)
+
+
+class CL4SRec(SASRec):
+    """recstudio/model/seq/cl4srec.py:13-53, recstudio/model/seq/config/cl4srec.yaml (hidden_size 64, layer_num 1, temperature 1.0,
+    augment_type 'item_crop', tau 0.2, cl_weight 0.1) on top of SASRec's: SASRec's step plus ``cl_weight`` times the in-batch InfoNCE
+    between two augmented views of every history, drawn afresh every step (``data_augmentation.CL4SRecAugmentation``).  The tower
+    runs three times per step: the main pass and one pass per view.  ``last_views`` holds the last step's two views.
+
+    A view is ONE launch of ``rsa_seq_augment`` with ``model.fused_augment`` (default on: faster than the twin at every measured shape), the same rule in batched torch ops
+    (``seq_augment_torch``) without it, on CPU tensors or above 64 positions -- the same view either way.  The in-batch InfoNCE is
+    ``rsa_batch_infonce`` / ``rsa_batch_infonce_backward`` with ``model.fused_infonce`` (nothing of size B^2, forward or backward;
+    off by default: slower than the op sequence at B = 8192, see ``FUSED_INFONCE_DEFAULT``), the reference's op sequence
+    (``batch_infonce_torch``, which holds [B, 2B]) without it, on CPU tensors or at other widths.
+
+    THE GENERATOR ORDER OF A STEP (device stream): the main pass (the tower's dropouts, then the negatives), ``rand([B, L + 1])`` for
+    view i, the same for view j, the tower's dropouts for view i, then those for view j.  ``item_random`` also takes one
+    ``random.randint(0, 2)`` per view from Python's generator.
+
+    Deliberate deviations from the reference.  (1) The views follow the device ``torch.rand`` stream, not the reference's three host
+    generators behind one ``.item()`` per sequence (2 B synchronisations per step).  (2) A cropped batch keeps its width L
+    (``pad_sequence`` narrows it); the encoder's output on the kept positions is the same.  (3) The mask token is not row
+    ``num_items`` of a widened item table (cl4srec.py:33-34, which the reference's evaluation then scores like an item) but the
+    query encoder's own ``mask_emb`` [1, d]: the catalog table keeps ``num_items`` rows, so the sampler, the fused tail, ``topk``
+    and ``evaluate`` run unchanged and never see ``num_items``; a reference checkpoint's trailing row is ``mask_emb``.  (4) The
+    training form is this tree's SASRec's (``SeqDataset``, last-position pooling, BCE with one negative); the reference's uses
+    ``SeqToSeqDataset`` with a loss at every position."""
+
+    def __init__(self, config=None, **kwargs):
+        user = (config or {}).get('model', {})
+        super().__init__(config, **kwargs)
+        m = self.config['model']
+        for k, v in (('hidden_size', 64), ('layer_num', 1)):
+            if k not in user:
+                m[k] = v
+        for k, v in (('temperature', 1.0), ('augment_type', 'item_crop'), ('tau', 0.2), ('cl_weight', 0.1), ('fused_augment', True),
+                     ('fused_infonce', FUSED_INFONCE_DEFAULT)):
+            m.setdefault(k, v)
+
+    def _init_model(self, train_data, drop_unused_field=True):
+        from . import data_augmentation
+        super()._init_model(train_data, drop_unused_field)
+        self.augmentation_model = data_augmentation.CL4SRecAugmentation(self.config['model'], train_data)
+
+    def _get_query_encoder(self, train_data):
+        m = self.config['model']
+        return SASRecQueryEncoder(self.fiid, self.embed_dim, train_data.config['max_seq_len'], m['head_num'],
+                                  m['hidden_size'], m['dropout_rate'], m['activation'], m['layer_norm_eps'],
+                                  m['layer_num'], self.item_encoder, fused_attention=m['fused_attention'],
+                                  mask_id=train_data.num_items)
+
+    def _init_parameter(self):
+        super()._init_parameter()
+        # the mask token like a row of the item table (recstudio/model/init.py on the reference's [num_items + 1, d] table); drawn
+        # last, so every other parameter is SASRec's at the same seed
+        w = self.query_encoder.mask_emb.data
+        method, (n, d) = self.config['train']['init_method'], self.item_encoder.weight.shape
+        if method == 'xavier_normal':
+            w.normal_(mean=0.0, std=math.sqrt(2.0 / (n + 1 + d)))
+        elif method == 'xavier_uniform':
+            bound = math.sqrt(6.0 / (n + 1 + d))
+            w.uniform_(-bound, bound)
+        else:
+            w.normal_(mean=0.0, std=0.02)
+
+    @property
+    def last_views(self):
+        return self.augmentation_model.last_views
+
+    def training_step(self, batch):
+        loss = super().training_step(batch)
+        if not self.config['model']['cl_weight']:
+            return loss
+        cl_output = self.augmentation_model(batch, self.query_encoder)
+        return loss + self.config['model']['cl_weight'] * cl_output['cl_loss']
 
 
 class GRU4RecQueryEncoder(torch.nn.Module):
