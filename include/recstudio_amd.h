@@ -1139,6 +1139,49 @@ int64_t rsa_hgn_gating_workspace_bytes(int64_t n_seq, int32_t seq_len, int32_t d
 int rsa_hgn_gating(const rsa_hgn_gating_args* args, rsa_stream_t stream);
 int rsa_hgn_gating_backward(const rsa_hgn_gating_args* args, rsa_stream_t stream);
 
+/* Bag sum of table rows straight from a padded id matrix, and its backward (MultiDAE / MultiVAE: recstudio/model/ae/multidae.py:21-23
+ * `item_embedding(ids).sum(1) / count_nonzero(ids, 1) ** 0.5`, and the per-user mean of the positives' rows in the softmax loss):
+ *   cnt[b] = live ids of row b     out[b] = s_b * sum_{l live} table[ids[b, l]]     s_b = 1 (RSA_BAG_SUM), 1 / sqrt(cnt[b])
+ *   (RSA_BAG_RSQRT) or 1 / cnt[b] (RSA_BAG_MEAN); an empty bag gives 0 under RSA_BAG_SUM and NaN under the other two (0 * inf).
+ * An id is live when it is > 0: id 0 is padding and may stand anywhere in a row; padding is skipped, not read (equal to the
+ * reference whenever row 0 of the table is zero).  A live id >= n_rows reads row n_rows - 1.  table fp32 [n_rows, d], ids int64
+ * [n_bags, bag_len] with ids_stride elements between rows, d a multiple of 4 in [4, 1024], any n_bags, bag_len >= 0 with
+ * n_bags * bag_len < 2^31, n_rows < 2^31 - 1; element offsets are 64-bit.
+ * rsa_bag_pool writes out [n_bags, d] and cnt [n_bags].  bag_len <= 256: one launch, no workspace.  Longer rows: chunks of 256
+ * positions are summed by a workgroup each into `workspace` and a second launch adds a bag's non-empty chunks in chunk order.  No
+ * atomics; the order of the additions depends on d and on that row of ids only (the same bag gives the same bits anywhere).
+ * rsa_bag_pool_backward takes ids, the forward's cnt, g [n_bags, d] and writes dw[i] = sum_{(b, l) : ids[b, l] = i} s_b g[b] into
+ * the rows i it touches of dw [n_rows, d], which the CALLER has zeroed (row 0 is never written): a stable radix sort of the
+ * (row, bag) pairs in `workspace`, then a wave per touched row adds in (bag, position) order and stores the row once.  No atomics,
+ * bit-equal from run to run.
+ * A d, scale or size outside the above, a null or misaligned (16 bytes: table, out, g, dw) pointer, an ids_stride below bag_len, a
+ * workspace that is too small: RSA_ERR_ARG before the first HIP call.  n_bags == 0 returns 0 and launches nothing.  Nothing is
+ * allocated, nothing synchronises. */
+#define RSA_BAG_SUM 0
+#define RSA_BAG_RSQRT 1
+#define RSA_BAG_MEAN 2
+typedef struct rsa_bag_args {
+  int64_t size;                /* sizeof(rsa_bag_args) */
+  const float* table;          /* forward: [n_rows, d] */
+  const int64_t* ids;          /* [n_bags, bag_len], row b at ids + b * ids_stride */
+  int64_t ids_stride;          /* elements between the rows of ids, >= bag_len */
+  int64_t n_rows;
+  int64_t n_bags;
+  int32_t bag_len;
+  int32_t d;
+  int32_t scale;               /* RSA_BAG_* */
+  int32_t reserved;            /* 0 */
+  float* out;                  /* forward: [n_bags, d] out */
+  int32_t* cnt;                /* [n_bags]: forward out, backward in */
+  const float* g;              /* backward: [n_bags, d] */
+  float* dw;                   /* backward: [n_rows, d], zeroed by the caller */
+  void* workspace;             /* forward with bag_len > 256, backward */
+  int64_t workspace_bytes;     /* >= rsa_bag_pool_workspace_bytes(n_bags, bag_len, n_rows) */
+} rsa_bag_args;
+int64_t rsa_bag_pool_workspace_bytes(int64_t n_bags, int32_t bag_len, int64_t n_rows);
+int rsa_bag_pool(const rsa_bag_args* args, rsa_stream_t stream);
+int rsa_bag_pool_backward(const rsa_bag_args* args, rsa_stream_t stream);
+
 /* One augmented view of a batch of histories for the contrastive sequence retrievers (CL4SRec: recstudio/model/seq/cl4srec.py;
  * Item_Crop / Item_Mask / Item_Reorder, recstudio/model/module/data_augmentation.py:22-87), one launch.  The random choices are
  * the elements of ONE torch.rand([n_seq, seq_len + 1]) call for the given Philox state: U[b, 0] draws the start, U[b, 1 + p] is

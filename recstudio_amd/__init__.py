@@ -15,15 +15,17 @@ from .loss_func import (FullScoreLoss, PairwiseLoss, PointwiseLoss, BPRLoss,   #
                         SampledSoftmaxLoss, SoftmaxLoss, BinaryCrossEntropyLoss, WeightedBPRLoss,
                         WeightedBinaryCrossEntropyLoss, HingeLoss, NCELoss, CCLLoss, InfoNCELoss)
 from .fused import retriever_scores                               # noqa: F401
-from .dataset import TripletDataset, SeqDataset, DataSampler, SortedDataSampler   # noqa: F401
+from .dataset import TripletDataset, SeqDataset, UserDataset, DataSampler, SortedDataSampler   # noqa: F401
 from .retriever import (BaseRetriever, TwoTowerRecommender, ItemTowerRecommender, BPR, SASRec, LightGCN,   # noqa: F401
-                        SGL, SimGCL, NGCF, CL4SRec, GRU4Rec, NARM, STAMP, HGN, HGNQueryEncoder, default_config, seed_everything)
+                        SGL, SimGCL, NGCF, CL4SRec, GRU4Rec, NARM, STAMP, HGN, HGNQueryEncoder, MultiDAE, MultiVAE, MultiDAEQueryEncoder,
+                        MultiVAEQueryEncoder, default_config, seed_everything)
 from . import graphmodule                                         # noqa: F401
 from . import seqmodule                                           # noqa: F401
 from .seqmodule import FusedTransformerEncoder, seq_attention_torch, FusedGRU, gru_sequence_torch   # noqa: F401
 from .seqmodule import AttentionLayer, MLPModule, ff_attention_pool, ff_attention_pool_torch   # noqa: F401
 from .seqmodule import caser_conv_torch   # noqa: F401
 from .seqmodule import hgn_gating, hgn_gating_torch   # noqa: F401
+from .seqmodule import bag_pool, bag_pool_torch   # noqa: F401
 from . import data_augmentation                                   # noqa: F401
 from . import eval                                                # noqa: F401
 from . import fused                                               # noqa: F401

@@ -335,6 +335,16 @@ class BatchInfoNceArgs(_Sized):
     ]
 
 
+class BagArgs(_Sized):
+    """struct rsa_bag_args."""
+    _fields_ = [
+        ('size', c_int64), ('table', c_void_p), ('ids', c_void_p), ('ids_stride', c_int64), ('n_rows', c_int64),
+        ('n_bags', c_int64), ('bag_len', c_int32), ('d', c_int32), ('scale', c_int32), ('reserved', c_int32),
+        ('out', c_void_p), ('cnt', c_void_p), ('g', c_void_p), ('dw', c_void_p), ('workspace', c_void_p),
+        ('workspace_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -348,7 +358,7 @@ STRUCTS = {
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
     'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs, 'rsa_ff_attention_args': FfAttentionArgs,
     'rsa_hgn_gating_args': HgnGatingArgs, 'rsa_seq_augment_args': SeqAugmentArgs,
-    'rsa_batch_infonce_args': BatchInfoNceArgs,
+    'rsa_batch_infonce_args': BatchInfoNceArgs, 'rsa_bag_args': BagArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -452,6 +462,9 @@ SIGNATURES = {
     'rsa_seq_augment': (c_int, [POINTER(SeqAugmentArgs), c_void_p]),
     'rsa_batch_infonce': (c_int, [POINTER(BatchInfoNceArgs), c_void_p]),
     'rsa_batch_infonce_backward': (c_int, [POINTER(BatchInfoNceArgs), c_void_p]),
+    'rsa_bag_pool_workspace_bytes': (c_int64, [c_int64, c_int32, c_int64]),
+    'rsa_bag_pool': (c_int, [POINTER(BagArgs), c_void_p]),
+    'rsa_bag_pool_backward': (c_int, [POINTER(BagArgs), c_void_p]),
 }
 
 _lib = None

@@ -698,6 +698,58 @@ class SeqDataset(TripletDataset):
         return self.inter_feat[self.fiid], idx[:, 1].contiguous(), idx[:, 2].contiguous()
 
 
+class UserDataset(TripletDataset):
+    """recstudio/data/dataset.py:1278-1366: ONE sample per user, ``[user, start, end, user, start', end')``.  The first segment
+    is the user's train cut (the model's input, ``in_*``), the second the split's own cut (the targets): the train cut again for
+    the training split, the valid / test cut for the others.  Users whose valid cut is empty are dropped from all three splits
+    (:1319-1321).  Batches are right-padded with 0: ``in_item_id``, ``in_rating``, ``item_id``, ``rating`` [B, L] each with its own
+    L; evaluation batches carry ``user_hist = in_item_id`` (:1354-1355).  Host loader only: ``device_train_loader`` is not
+    offered for this class (a training epoch is a few hundred batches of one user per sample)."""
+
+    def build(self, binarized_rating_thres=None, fmeval=False, neg_count=None, sampler=None, shuffle=True,
+              split_mode='user_entry', split_ratio=(0.8, 0.1, 0.1), **kwargs):
+        if split_mode != 'user_entry':
+            # the reference's `entry` branch (:1328-1332) only serves a split by counts [n_trn, n_val, n_tst], which _build
+            # regroups per user first (:1030-1051); with ratios its torch.hstack of numpy arrays raises, and `user` leaves
+            # _get_data_idx without a result
+            raise NotImplementedError("UserDataset: only split_mode='user_entry' is implemented (the reference's 'entry' branch "
+                                      "needs a split by counts regrouped per user and fails on ratios; 'user' returns nothing)")
+        if isinstance(split_ratio, int):
+            raise NotImplementedError('UserDataset: split_ratio must be a list of ratios')
+        return self._build(list(split_ratio), shuffle, False)
+
+    def _get_data_idx(self, splits, uids):
+        keep = splits[:, 1] < splits[:, 2]
+        splits, uids = splits[keep], np.asarray(uids)[keep]
+        cuts = [torch.from_numpy(np.stack([uids, splits[:, i - 1], splits[:, i]], axis=1).astype(np.int64))
+                for i in range(1, splits.shape[1])]
+        return [torch.cat((cuts[0], c), dim=-1) for c in cuts]
+
+    @property
+    def inter_feat_subset(self):
+        return torch.cat([torch.arange(s, e) for s, e in zip(self.data_index[:, -2].tolist(), self.data_index[:, -1].tolist())])
+
+    def _get_pos_data(self, index):
+        idx = self.data_index[index]
+        data = {self.fuid: idx[:, 0]}
+        for i, prefix in enumerate(('in_', '')):
+            start, end = idx[:, i * 3 + 1], idx[:, i * 3 + 2]
+            lens = (end - start).tolist()
+            rows = torch.cat([torch.arange(s, e) for s, e in zip(start.tolist(), end.tolist())])
+            for k in (self.fiid, self.frating):
+                data[prefix + k] = pad_sequence(self.inter_feat[k][rows].split(lens), batch_first=True)
+        return data
+
+    def __getitem__(self, index):
+        data = self._get_pos_data(index)
+        if self.eval_mode and 'user_hist' not in data:
+            data['user_hist'] = data['in_' + self.fiid]
+        return data
+
+    def device_train_loader(self, *args, **kwargs):
+        raise NotImplementedError('UserDataset batches are assembled on the host: use train_loader(..., device=...)')
+
+
 def synthetic_interactions(n_users, n_items, n_inter, alpha=1.0, seed=1):
     """Seeded synthetic interaction stream: users uniform, items Zipf(alpha) over a permuted id space
     (SURVEY.md section 8d).  Returns (user_ids, item_ids) int64 arrays with ids starting at 1."""

@@ -2054,3 +2054,80 @@ def batch_infonce_backward(zi, zj, inv_t, both, labels, lse, g):
     a.lse, a.g, a.dzi, a.dzj = ptr(lse), ptr(g), ptr(dzi), ptr(dzj)
     _launch('rsa_batch_infonce_backward', ctypes.byref(a))
     return dzi, dzj
+
+
+# ------------------------------------------------------------------ user-history bags (MultiDAE / MultiVAE)
+BAG_MAX_DIM = 1024                # one thread per 16-byte column of a row (rsa_bag.hip)
+BAG_SCALES = {'sum': 0, 'rsqrt': 1, 'mean': 2}
+
+
+def _bag_args(who, ids, N, d, scale):
+    ids = _need_view(ids, torch.int64, 'ids')
+    if scale not in BAG_SCALES:
+        raise ValueError(f'{who}: scale must be one of {tuple(BAG_SCALES)}, got {scale!r}')
+    if ids.dim() != 2:
+        raise ValueError(f'{who}: ids must be [B, L], got {tuple(ids.shape)}')
+    if d % 4 or not 4 <= d <= BAG_MAX_DIM:
+        raise ValueError(f'{who}: the row width must be a multiple of 4 in [4, {BAG_MAX_DIM}], got {d}')
+    B, L = ids.shape
+    if B > 0 and L > 0 and (ids.stride(1) != 1 or ids.stride(0) < L):
+        ids = ids.contiguous()
+    a = nat.BagArgs()
+    a.ids, a.ids_stride = ptr(ids), (ids.stride(0) if B > 0 and L > 0 else L)
+    a.n_rows, a.n_bags, a.bag_len, a.d, a.scale = N, B, L, d, BAG_SCALES[scale]
+    return a, ids, B, L
+
+
+@_on_device
+def bag_pool(table, ids, scale='sum'):
+    """rsa_bag_pool: ``out[b] = s_b * table[ids[b, live]].sum(0)`` straight from the padded id matrix.  ``table`` fp32 [N, d], d
+    a multiple of 4 up to 1024; ``ids`` int64 [B, L], read in place through its row stride; an id is live when it is > 0 (0 is
+    padding, anywhere in the row; it is skipped, not read).  ``scale``: 'sum' (s = 1), 'rsqrt' (s = cnt ** -0.5) or 'mean'
+    (s = 1 / cnt); an empty bag gives 0 under 'sum' and NaN under the other two.
+    -> ``(out [B, d], cnt int32 [B])``.  Nothing of size B L d is read, written or allocated; no atomics; the same bag gives the
+    same bits at any batch position."""
+    table = _need(table, torch.float32, 'table')
+    if table.dim() != 2:
+        raise ValueError(f'bag_pool: table must be [N, d], got {tuple(table.shape)}')
+    N, d = table.shape
+    a, ids, B, L = _bag_args('bag_pool', ids, N, d, scale)
+    dev = table.device
+    out = torch.empty(B, d, dtype=torch.float32, device=dev)
+    cnt = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return out, cnt
+    ws = None
+    if L > 256:
+        ws, a.workspace_bytes = _workspace(dev, 'rsa_bag_pool_workspace_bytes', B, L, N)
+    a.table, a.out, a.cnt, a.workspace = ptr(table), ptr(out), ptr(cnt), ptr(ws)
+    _launch('rsa_bag_pool', ctypes.byref(a))
+    return out, cnt
+
+
+@_on_device
+def bag_pool_backward(ids, cnt, g, n_rows, scale='sum', out=None):
+    """rsa_bag_pool_backward: the gradient of ``bag_pool`` to its table, ``dW[i] = sum over the occurrences (b, l) of item i of
+    s_b * g[b]`` (an item twice in one bag counts twice; row 0 and padding receive nothing), from ``ids``, the forward's ``cnt``
+    and ``g`` fp32 [B, d].  -> dense ``dW`` fp32 [n_rows, d] (``out``: a ZEROED tensor to write into).  The (item, bag) pairs
+    are sorted by the in-tree radix sort and every touched row is written once: no atomics, two runs are bit-equal."""
+    g = _need(g, torch.float32, 'g')
+    cnt = _need(cnt, torch.int32, 'cnt')
+    if g.dim() != 2:
+        raise ValueError(f'bag_pool_backward: g must be [B, d], got {tuple(g.shape)}')
+    d = g.shape[1]
+    a, ids, B, L = _bag_args('bag_pool_backward', ids, int(n_rows), d, scale)
+    if g.shape[0] != B or tuple(cnt.shape) != (B,):
+        raise ValueError(f'bag_pool_backward: g must be [{B}, {d}] and cnt [{B}], got {tuple(g.shape)}, {tuple(cnt.shape)}')
+    dev = g.device
+    if out is None:
+        out = torch.zeros(int(n_rows), d, dtype=torch.float32, device=dev)
+    else:
+        out = _need_view(out, torch.float32, 'out')
+        if tuple(out.shape) != (int(n_rows), d) or not out.is_contiguous():
+            raise ValueError(f'bag_pool_backward: out must be a contiguous [{int(n_rows)}, {d}] tensor, got {tuple(out.shape)}')
+    if B == 0 or L == 0:
+        return out
+    ws, a.workspace_bytes = _workspace(dev, 'rsa_bag_pool_workspace_bytes', B, L, int(n_rows))
+    a.cnt, a.g, a.dw, a.workspace = ptr(cnt), ptr(g), ptr(out), ptr(ws)
+    _launch('rsa_bag_pool_backward', ctypes.byref(a))
+    return out

@@ -67,6 +67,16 @@ have ``si = 0`` but ``w = sigmoid(ui) > 0``: they count in the mean's denominato
 stay torch GEMMs; everything per position is ONE launch of ``ops.hgn_gating`` (``rsa_hgn_gating``,
 recstudio_amd/csrc/rsa_gating.hip), which writes ``out``, ``w`` [B, L] and the max's positions and none of the reference's eight
 ``[B, L, d]`` temporaries; the backward recomputes the gates.  ``hgn_gating_torch`` is the twin: the reference's op sequence.
+
+USER-HISTORY BAGS.  The autoencoder retrievers (recstudio/model/ae/multidae.py:29-31, multivae.py:33-35) start from
+
+    seq_emb = item_embedding(ids).sum(1) / ids.count_nonzero(1) ** 0.5          ids [B, L], 0 = padding
+
+and their softmax loss needs, per user, the mean of the positives' rows.  ``bag_pool(weight, ids, scale)`` is both: ONE bag sum
+straight from the padded id matrix (``ops.bag_pool``, ``rsa_bag_pool``, recstudio_amd/csrc/rsa_bag.hip) with the scale 'sum',
+'rsqrt' or 'mean', and a sorted, atomic-free backward into the dense table gradient; no ``[B, L, d]`` tensor exists in either
+direction.  Deviation: padding is skipped, not read -- equal to the reference whenever row 0 of the table is zero, which
+``padding_idx=0`` guarantees.  ``bag_pool_torch`` is the twin: the reference's op sequence (it DOES read row 0).
 """
 import math
 
@@ -77,7 +87,7 @@ from . import ops, rng
 
 __all__ = ['seq_attention', 'seq_attention_torch', 'FusedTransformerEncoder', 'gru_sequence', 'gru_sequence_torch', 'FusedGRU',
            'ff_attention_pool', 'ff_attention_pool_torch', 'MLPModule', 'AttentionLayer', 'caser_conv_torch', 'caser_pack',
-           'hgn_gating', 'hgn_gating_torch']
+           'hgn_gating', 'hgn_gating_torch', 'bag_pool', 'bag_pool_torch']
 
 
 def allowed_keys(key_pad, causal, B, L, device):
@@ -425,6 +435,56 @@ def hgn_gating(S, ug, ui, w1, w3, pooling='mean'):
     if hgn_gating_kernel_ok(S, ug, ui, w1, w3):
         return _HgnGatingFn.apply(S, ug, ui, w1, w3, pooling)
     return hgn_gating_torch(S, ug, ui, w1, w3, pooling)
+
+
+BAG_SCALES = ('sum', 'rsqrt', 'mean')
+
+
+def bag_pool_torch(weight, ids, scale='sum'):
+    """The bag sum in the reference's own op sequence (recstudio/model/ae/multidae.py:29-31), any float dtype: gather
+    ``[B, L, d]``, sum over L, divide by ``count_nonzero ** 0.5`` ('rsqrt') or ``count_nonzero`` ('mean').  An empty bag divides
+    0 by 0 (NaN), as the reference does."""
+    if scale not in BAG_SCALES:
+        raise ValueError(f'scale must be one of {BAG_SCALES}, got {scale!r}')
+    out = F.embedding(ids, weight, padding_idx=0).sum(1)        # nn.Embedding(.., padding_idx=0): row 0 is read, and gets no gradient
+    if scale == 'sum':
+        return out
+    non_zero_num = ids.count_nonzero(dim=1).unsqueeze(-1).to(out.dtype)      # (the reference's int64 .pow(0.5) is fp32: the same in fp32)
+    return out / (non_zero_num.pow(0.5) if scale == 'rsqrt' else non_zero_num)
+
+
+class _BagPoolFn(torch.autograd.Function):
+    """``ops.bag_pool`` / ``ops.bag_pool_backward`` as one autograd node: linear in ``weight``, no gradient to ``ids``.  Saved:
+    ``ids`` and ``cnt`` [B]."""
+
+    @staticmethod
+    def forward(ctx, weight, ids, scale):
+        out, cnt = ops.bag_pool(weight.detach(), ids, scale)
+        ctx.save_for_backward(ids, cnt)
+        ctx.scale, ctx.n_rows = scale, weight.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        ids, cnt = ctx.saved_tensors
+        return ops.bag_pool_backward(ids, cnt, g_out.contiguous(), ctx.n_rows, ctx.scale), None, None
+
+
+def bag_pool_kernel_ok(weight, ids):
+    """Whether ``ops.bag_pool`` takes these tensors: an fp32 table and int64 ids on the device, a width that is a multiple of 4
+    up to ``ops.BAG_MAX_DIM``."""
+    return (weight.is_cuda and ids.is_cuda and weight.dtype == torch.float32 and ids.dtype == torch.int64 and weight.dim() == 2
+            and ids.dim() == 2 and weight.shape[1] % 4 == 0 and 4 <= weight.shape[1] <= ops.BAG_MAX_DIM)
+
+
+def bag_pool(weight, ids, scale='sum', fused=True):
+    """``[B, d]`` bag sums of the rows ``weight[ids]`` (see the module docstring): the kernel pair where ``fused`` and
+    ``bag_pool_kernel_ok``, ``bag_pool_torch`` otherwise (CPU tensors: the parity path; widths the kernel does not take)."""
+    if scale not in BAG_SCALES:
+        raise ValueError(f'scale must be one of {BAG_SCALES}, got {scale!r}')
+    if fused and bag_pool_kernel_ok(weight, ids):
+        return _BagPoolFn.apply(weight, ids, scale)
+    return bag_pool_torch(weight, ids, scale)
 
 
 def caser_pack(vertical_filter, horizontal_filter):

@@ -1,0 +1,179 @@
+"""GPU: MultiDAE and MultiVAE on a synthetic UserDataset (60 users, 40 items): one training step + backward with model.fused_bag
+on and off, the same step in float64 on the CPU, evaluation top-k next to the torch-op model, a five-epoch fit, and the KL
+weight's annealing.
+
+HOW THE STEP IS JUDGED.  The two settings differ in two places only: the encoder's input h (the 'rsqrt' bag) and the positives'
+term (the 'mean' bag dotted with the query, against the mean of the [B, L] scores).  Both are checked at the source against the
+referee's own bounds (tests/bag_referee.py): two fp32 evaluations of one bag are at most two bounds apart.  Everything after is the
+same sequence of fp32 torch ops on inputs that differ by those few ulps, so the loss and the gradients are held to the suite's
+tolerances for towers on torch ops (tests/test_caser_twin.py: 1e-4 on outputs, 3e-4 on gradients, the latter relative to a
+gradient's largest element); the float64 step is held to the same."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import bag_referee as br
+from recstudio_amd.dataset import synthetic_interactions
+
+pytestmark = pytest.mark.gpu
+
+DEV = 'cuda'
+MODELS = {'MultiDAE': dict(embed_dim=32, dropout=0.0, encoder_dims=[16, 8], decoder_dims=[8, 16]),
+          'MultiVAE': dict(embed_dim=32, dropout_rate=0.0, encoder_dims=[16, 8], decoder_dims=[8, 16])}
+
+
+@pytest.fixture(scope='module')
+def ra():
+    import recstudio_amd
+    recstudio_amd._native.lib()
+    torch.cuda.init()
+    return recstudio_amd
+
+
+@pytest.fixture(scope='module')
+def splits(ra):
+    users, items = synthetic_interactions(60, 40, 1500, seed=3)
+    np.random.seed(5)
+    return ra.UserDataset.from_interactions(users.astype(str), items.astype(str)).build(split_ratio=[0.8, 0.1, 0.1])
+
+
+def make_model(ra, name, trn, fused, **train):
+    cfg = {'model': dict(MODELS[name], fused_bag=fused), 'train': dict({'batch_size': 32, 'anneal_total_step': 4, 'anneal_max': 0.5}, **train),
+           'eval': {'batch_size': 32}}
+    model = getattr(ra, name)(cfg)
+    model._init_model(trn)
+    model._init_parameter()
+    with torch.no_grad():                      # (the 'xavier_normal' start leaves scores near 0: widen them so the step has a slope)
+        for p in model.parameters():
+            p.mul_(3.0)
+        model.item_encoder.weight[0] = 0
+        model.query_encoder.item_embedding.weight[0] = 0
+    return model.to(DEV)
+
+
+def train_batch(trn, n=24):
+    trn.eval_mode = False
+    return {k: v.to(DEV) for k, v in trn[torch.arange(n)].items()}
+
+
+def step(model, batch, seed=11):
+    model.train()
+    model.anneal = 0.25                         # (MultiVAE: a KL weight that is neither 0 nor the cap)
+    for p in model.parameters():
+        p.grad = None
+    torch.manual_seed(seed)
+    loss = model.training_step(batch)
+    loss.backward()
+    return loss.detach(), {k: p.grad.detach().clone() for k, p in model.named_parameters()}
+
+
+def close_grads(got, want, rtol=3e-4):
+    assert set(got) == set(want)
+    for k in want:
+        a, b = got[k].cpu().double(), want[k].cpu().double()
+        assert float((a - b).abs().max()) <= rtol * max(float(b.abs().max()), 1e-6), k
+
+
+@pytest.mark.parametrize('name', sorted(MODELS))
+def test_step_with_the_flag_on_and_off(ra, splits, name):
+    trn = splits[0]
+    on = make_model(ra, name, trn, True)
+    off = make_model(ra, name, trn, False)
+    off.load_state_dict(on.state_dict())
+    assert on.query_encoder.fused_bag and not off.query_encoder.fused_bag
+    batch = train_batch(trn)
+    ids_in, ids_pos = batch['in_item_id'], batch['item_id']
+    assert ids_pos.dim() == 2 and bool((ids_in == 0).any())
+    # the two places the settings differ, against the referee's bounds
+    from recstudio_amd import seqmodule
+    for w, ids, scale in ((on.query_encoder.item_embedding.weight, ids_in, 'rsqrt'), (on.item_encoder.weight, ids_pos, 'mean')):
+        a, b = seqmodule.bag_pool(w, ids, scale, fused=True), seqmodule.bag_pool(w, ids, scale, fused=False)
+        judged = br.forward(w.detach().cpu(), ids.cpu(), scale)
+        assert br.worst_ratio(a, judged['out'], judged['tol']) <= 1.0 and br.worst_ratio(b, judged['out'], judged['tol']) <= 1.0
+    loss_on, g_on = step(on, batch)
+    loss_off, g_off = step(off, batch)
+    print(name, 'loss on / off', float(loss_on), float(loss_off))
+    assert abs(float(loss_on) - float(loss_off)) <= 1e-4 * abs(float(loss_off))
+    close_grads(g_on, g_off)
+    assert not bool(g_on['item_encoder.weight'][0].any()) and not bool(g_on['query_encoder.item_embedding.weight'][0].any())
+
+
+@pytest.mark.parametrize('name', sorted(MODELS))
+def test_float64_step_on_the_cpu_agrees(ra, splits, name, monkeypatch):
+    trn = splits[0]
+    model = make_model(ra, name, trn, True)
+    batch = train_batch(trn)
+    eps = torch.randn(batch['item_id'].shape[0], 8, generator=torch.Generator().manual_seed(3), dtype=torch.float64)
+    monkeypatch.setattr(torch, 'randn_like', lambda t: eps.to(t.device, t.dtype))
+    loss, grads = step(model, batch)
+    # the same step from the rule, in float64: twin encoder, dense scores, the mean over every user's live positives
+    model.query_encoder.kl_loss = 0.0           # (MultiVAE leaves a graph tensor there: deepcopy refuses it)
+    enc = copy.deepcopy(model.query_encoder).cpu().double().train()
+    enc.fused_bag = False
+    w = model.item_encoder.weight.detach().cpu().double().requires_grad_(True)
+    cpu = {k: v.cpu() for k, v in batch.items()}
+    q = enc(cpu)
+    lse = torch.logsumexp(q @ w[1:].t(), dim=-1)
+    pos = (w[cpu['item_id']] * q.unsqueeze(1)).sum(-1)
+    live = cpu['item_id'] != 0
+    want = ((lse.unsqueeze(1) - pos) * live).sum(1) / live.sum(1)
+    want = want.mean()
+    if name == 'MultiVAE':
+        want = want + 0.25 * enc.kl_loss
+    want.backward()
+    assert abs(float(loss) - float(want)) <= 1e-4 * abs(float(want))
+    ref = {'query_encoder.' + k: p.grad for k, p in enc.named_parameters()}
+    ref['item_encoder.weight'] = w.grad
+    close_grads(grads, ref)
+
+
+@pytest.mark.parametrize('name', sorted(MODELS))
+def test_eval_topk_equals_the_twin_s(ra, splits, name):
+    trn, val, _ = splits
+    on = make_model(ra, name, trn, True)
+    off = make_model(ra, name, trn, False)
+    off.load_state_dict(on.state_dict())
+    on.eval(), off.eval()
+    batch = {k: v.to(DEV) for k, v in next(iter(val.eval_loader(batch_size=32))).items()}
+    assert 'user_hist' in batch
+    with torch.no_grad():
+        on._update_item_vector(), off._update_item_vector()
+        s_on, i_on, q_on = on.topk(batch, 10, batch['user_hist'], return_query=True)
+        s_off, i_off = off.topk(batch, 10, batch['user_hist'])
+    torch.testing.assert_close(s_on, s_off, rtol=1e-4, atol=1e-5)
+    dense = q_on.double() @ on.item_encoder.weight.double().t()
+    torch.testing.assert_close(dense.gather(1, i_on), s_on.double(), rtol=1e-4, atol=1e-5)
+    swapped = i_on != i_off                    # only exact or near ties may come out in another order
+    assert not bool(swapped.any()) or float((dense.gather(1, i_on) - dense.gather(1, i_off)).abs()[swapped].max()) <= 1e-5
+    assert not bool((i_on.unsqueeze(2) == batch['user_hist'].unsqueeze(1)).any())
+
+
+@pytest.mark.parametrize('name', sorted(MODELS))
+def test_five_epoch_fit_lowers_the_training_loss(ra, splits, name):
+    trn, val, _ = splits
+    cfg = {'model': dict(MODELS[name], fused_bag=True), 'train': {'epochs': 5, 'batch_size': 32, 'learning_rate': 0.01},
+           'eval': {'batch_size': 32}}
+    model = getattr(ra, name)(cfg)
+    model.fit(trn, val)
+    losses = [h['train_loss'] for h in model.history]
+    print(name, losses)
+    assert len(losses) == 5 and all(np.isfinite(losses)) and losses[-1] < losses[0]
+
+
+def test_kl_weight_follows_the_annealing_schedule(ra, splits):
+    trn = splits[0]
+    model = make_model(ra, 'MultiVAE', trn, True)       # anneal_total_step 4, anneal_max 0.5
+    batch = train_batch(trn)
+    model.train()
+    seen = []
+    for _ in range(4):
+        torch.manual_seed(1)
+        before = getattr(model, 'anneal', 0)
+        loss = model.training_step(batch)
+        torch.manual_seed(1)
+        base = model._softmax_step(batch)
+        seen.append(before)
+        torch.testing.assert_close(loss - base, min(0.5, before) * model.query_encoder.kl_loss, rtol=1e-4, atol=1e-6)
+    assert seen == [0, 0.25, 0.5, 0.5] and model.anneal == 0.5
