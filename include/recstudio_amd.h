@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define RSA_ABI_VERSION 13  /* 13: rsa_scatter_rows_sorted_pairs_offset / rsa_bpr_sgd_pairs_offset / rsa_shard_backward_workspace_offsets (read-only: where the sorts leave their pairs, runs and flags inside the caller's workspaces);
+#define RSA_ABI_VERSION 13  /* (added without a bump, as the later entry points were: rsa_fullscore_plan, read-only: the plan of rsa_fullscore's top-k and where its select leaves thr / flags / seg_cnt / ovf_cnt in the workspace);
+                               13: rsa_scatter_rows_sorted_pairs_offset / rsa_bpr_sgd_pairs_offset / rsa_shard_backward_workspace_offsets (read-only: where the sorts leave their pairs, runs and flags inside the caller's workspaces);
                                12: rsa_rows_update_args.lr / beta1 / beta2 / eps are DOUBLES (the caller's own values: 1 - beta and the bias corrections are derived from them in double and rounded to fp32 once; as floats, 1 - float(0.999) was 1.29e-5 short of 0.001 on every touched row);
                                11: rsa_bpr_sgd_prepare / _apply sort the step's user rows WITH its item rows (one radix sort; item_workspace = rsa_scatter_rows_sorted_workspace_bytes(n_queries, num_neg + 1, n_items), user_workspace unused) and draw the negatives inside that sort's first launch; sampler RSA_SAMPLER_GIVEN accepted (neg_ids is an input);
                                10: rsa_fullscore_lse_grad (flash forward: logsumexp + d/d query in one pass); rsa_fullscore_softmax_dw (d/d items of the full softmax with the softmax tile recomputed on the matrix cores: no
@@ -728,6 +729,45 @@ typedef struct rsa_fullscore_args {
   int64_t workspace_bytes;
 } rsa_fullscore_args;
 int rsa_fullscore(const rsa_fullscore_args* args, rsa_stream_t stream);
+
+/* What rsa_fullscore(n_query, n_items, k) will do, read-only and host-only (no device call): filled from the very code the
+ * launch runs.  `k` as for rsa_fullscore_workspace_bytes (0: no top-k, or the caller's `scores` hold the rows).  The caller sets
+ * out->size = sizeof(rsa_fullscore_plan_info); at most that many bytes are written.
+ *   filter            1: sample GEMM + threshold + filter epilogue + candidate select; 0: dense select over materialised rows
+ *   groups, j         the threshold of a query is the j-th largest (value descending, group index ascending) of `groups` group
+ *                     maxima; a group is group_tiles consecutive sampled tiles and sample tile s covers catalog items
+ *                     1 + s * tile_stride * 32 + [0, 32).  On a dense plan: what the planner had worked out when it turned the
+ *                     filter down (all zero below the smallest filtered catalog)
+ *   expect            catalog items the planner expects above the threshold
+ *   splits, items_per_split   the item ranges of the full GEMM's launch: range x = items [1 + x * items_per_split, ...)
+ *   n_seg             candidate segments per query = 2 * splits (one per range and lane half; a lane half owns rows 4..7, 12..15,
+ *                     20..23, 28..31 of every 32-item tile when it is the upper one); 0 on a dense plan
+ *   seg, ovf, cand_max        slots of a segment, of a query's overflow list, and the most candidates the select takes
+ *   *_offset          byte offsets, from the workspace pointer rounded up to 256 bytes, of thr [n_query] (float), flags [n_query]
+ *                     (int32, 1 = the row went to the exact recompute), seg_cnt [n_query, n_seg] (int32) and ovf_cnt [n_query]
+ *                     (int32, appends to the overflow list, may exceed ovf); -1 on a dense plan. */
+typedef struct rsa_fullscore_plan_info {
+  int64_t size;                /* sizeof(rsa_fullscore_plan_info) */
+  int32_t filter;
+  int32_t j;
+  int64_t groups;
+  int64_t sample_tiles;
+  int64_t tile_stride;
+  int64_t group_tiles;
+  double expect;
+  int64_t splits;
+  int64_t items_per_split;
+  int64_t n_seg;
+  int32_t seg;
+  int32_t ovf;
+  int32_t cand_max;
+  int32_t _pad;
+  int64_t thr_offset;
+  int64_t flags_offset;
+  int64_t seg_cnt_offset;
+  int64_t ovf_cnt_offset;
+} rsa_fullscore_plan_info;
+int rsa_fullscore_plan(int64_t n_query, int64_t n_items, int32_t k, rsa_fullscore_plan_info* out);
 
 /* BaseRetriever.sampling(method='brute') -- baseretriever.py:299-328 -- and RetrieverSampler (recstudio/ann/sampler.py:61-78)
  * without the [B, N] matrix: num_neg ids per query, with replacement, from softmax(score(q, .) * inv_t) over item rows

@@ -181,6 +181,17 @@ class FullscoreArgs(_Sized):
     ]
 
 
+class FullscorePlanInfo(_Sized):
+    """struct rsa_fullscore_plan_info (filled by rsa_fullscore_plan)."""
+    _fields_ = [
+        ('size', c_int64), ('filter', c_int32), ('j', c_int32), ('groups', c_int64), ('sample_tiles', c_int64),
+        ('tile_stride', c_int64), ('group_tiles', c_int64), ('expect', c_double), ('splits', c_int64),
+        ('items_per_split', c_int64), ('n_seg', c_int64), ('seg', c_int32), ('ovf', c_int32), ('cand_max', c_int32),
+        ('_pad', c_int32), ('thr_offset', c_int64), ('flags_offset', c_int64), ('seg_cnt_offset', c_int64),
+        ('ovf_cnt_offset', c_int64),
+    ]
+
+
 class MidxArgs(_Sized):
     """struct rsa_midx_args."""
     _fields_ = [
@@ -352,7 +363,7 @@ STRUCTS = {
     'rsa_shard_home_args': ShardHomeArgs, 'rsa_shard_backward_args': ShardBackwardArgs,
     'rsa_shard_owner_bpr_args': ShardOwnerBprArgs, 'rsa_popular_args': PopularArgs, 'rsa_loss_args': LossArgs,
     'rsa_rows_update_args': RowsUpdateArgs, 'rsa_bpr_sgd_args': BprSgdArgs, 'rsa_seg_gather_args': SegGatherArgs,
-    'rsa_fullscore_args': FullscoreArgs, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
+    'rsa_fullscore_args': FullscoreArgs, 'rsa_fullscore_plan_info': FullscorePlanInfo, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
@@ -439,6 +450,7 @@ SIGNATURES = {
     'rsa_gather_f32': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     'rsa_fullscore_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32]),
     'rsa_fullscore': (c_int, [POINTER(FullscoreArgs), c_void_p]),
+    'rsa_fullscore_plan': (c_int, [c_int64, c_int64, c_int32, POINTER(FullscorePlanInfo)]),
     'rsa_row_sqnorm': (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     'rsa_softmax_sample_workspace_bytes': (c_int64, [c_int64, c_int64]),
     'rsa_softmax_sample_block': (c_int32, []),

@@ -962,7 +962,9 @@ static TopkPlan plan_topk(int64_t n_items, int32_t k, bool scores_given) {
 // follow from, and the regions.
 struct FullscoreLayout {
   TopkPlan pl;
-  int64_t splits;
+  int64_t splits;         // item-range splits the regions are sized for
+  int64_t per;            // items per split of the launch (whole tiles)
+  int64_t splits_used;    // splits the launch uses (<= splits): ranges of `per` items that are not empty; n_seg = 2 * splits_used
   float2* part;           // lse partials
   float2* gmax;           // filter: group maxima of the sample pass
   float* thr;             //   thresholds
@@ -979,6 +981,8 @@ static FullscoreLayout carve_fullscore(Carver& ws, int64_t n_query, int64_t n_it
   FullscoreLayout L{};
   L.pl = plan_topk(n_items, k, k <= 0);
   L.splits = fullscore_splits(n_query, n_items - 1, L.pl.filter ? L.pl.min_splits : 1);
+  L.per = ((n_items - 1 + L.splits - 1) / L.splits + TI - 1) / TI * TI;
+  L.splits_used = (n_items - 1 + L.per - 1) / L.per;
   L.part = ws.take<float2>(n_query * L.splits);
   if (k <= 0) return L;
   if (!L.pl.filter) {
@@ -1002,6 +1006,42 @@ extern "C" int64_t rsa_fullscore_workspace_bytes(int64_t n_query, int64_t n_item
   Carver sizing(nullptr);
   carve_fullscore(sizing, n_query, n_items, k);
   return align256(sizing.bytes()) + 256;
+}
+
+// What rsa_fullscore would do for this shape, from the same carve_fullscore / plan_topk it runs (host only, no device call):
+// the plan, the launch's item ranges, the caps of the candidate lists and where the select's bookkeeping lies in the workspace
+// (offsets from the workspace pointer rounded up to 256 bytes, as Carver places the regions).
+extern "C" int rsa_fullscore_plan(int64_t n_query, int64_t n_items, int32_t k, rsa_fullscore_plan_info* out) {
+  RSA_CHECK_ARG(out != nullptr, "rsa_fullscore_plan: out is null");
+  const int64_t sz = out->size;
+  RSA_CHECK_ARG(sz >= 16 && sz <= (1 << 16), "rsa_fullscore_plan: out->size = %lld (set it to sizeof the struct)", (long long)sz);
+  RSA_CHECK_ARG(n_query >= 1 && n_items >= 2 && k >= 0, "rsa_fullscore_plan: need n_query >= 1, n_items >= 2, k >= 0");
+  char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);     // never dereferenced: only the distances are used
+  Carver ws(base);
+  const FullscoreLayout L = carve_fullscore(ws, n_query, n_items, k);
+  auto off = [&](const void* p) -> int64_t { return p ? (int64_t)(reinterpret_cast<const char*>(p) - base) : -1; };
+  rsa_fullscore_plan_info o{};
+  o.size = (int64_t)sizeof(o);
+  o.filter = L.pl.filter ? 1 : 0;
+  o.j = L.pl.j;                        // (a dense plan keeps what plan_topk had worked out when it turned the filter down:
+  o.groups = L.pl.groups;              //  all zero below FILTER_MIN_ITEMS)
+  o.sample_tiles = L.pl.sample_tiles;
+  o.tile_stride = L.pl.tile_stride;
+  o.group_tiles = GROUP_TILES;
+  o.expect = L.pl.expect;
+  o.splits = L.splits_used;
+  o.items_per_split = L.per;
+  o.n_seg = L.pl.filter ? 2 * L.splits_used : 0;
+  o.seg = SEG;
+  o.ovf = OVF;
+  o.cand_max = CAND_MAX;
+  o.thr_offset = off(L.thr);
+  o.flags_offset = off(L.flags);
+  o.seg_cnt_offset = off(L.seg_cnt);
+  o.ovf_cnt_offset = off(L.ovf_cnt);
+  __builtin_memcpy(out, &o, (size_t)sz < sizeof(o) ? (size_t)sz : sizeof(o));
+  out->size = sz;
+  return RSA_OK;
 }
 
 template <int D, int MODE>
@@ -1057,8 +1097,7 @@ extern "C" int rsa_fullscore(const rsa_fullscore_args* args, rsa_stream_t stream
   Carver ws(a.workspace);
   const FullscoreLayout W = carve_fullscore(ws, n_query, a.n_items, ws_k);
   const TopkPlan& pl = W.pl;
-  const int64_t per = ((n_cols + W.splits - 1) / W.splits + TI - 1) / TI * TI;
-  const int64_t splits_used = (n_cols + per - 1) / per;
+  const int64_t per = W.per, splits_used = W.splits_used;
   float2* lp = a.lse ? W.part : nullptr;
   const FilterArgs no_filter{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a.item_aux, a.query_aux, nullptr};
 

@@ -246,10 +246,12 @@ def test_topk_filter_path_adversarial_catalogs(ra):
 
 
 def test_topk_large_k_large_batch_trending_scores(ra):
-    """B = 2048, k = 500 on a catalog whose scores trend along the id axis (ids sorted by popularity, say):
-    most of a query's candidates fall into a few item ranges.  The per-segment lists overflow into the
-    query's overflow list instead of sending every row to the exact single-workgroup recompute (which used
-    to turn this call from milliseconds into tens of seconds)."""
+    """B = 2048, k = 500 on a catalog whose scores trend along the id axis (ids sorted by popularity, say): most of a
+    query's best items fall into a few item ranges.  Written for the overflow list of the filter plan; at this shape the
+    planner now turns the filter down (rsa_fullscore_plan: rank j = 84 of 128 group maxima, more than half), so the call runs
+    the DENSE plan: materialised score rows (B x N floats of workspace) and the dense radix select.  What it still holds: the
+    exact top-k, the logsumexp, and that the call stays in the milliseconds.  The overflow list and the exact recompute are
+    asserted taken, row by row, in tests/test_gpu_topk_paths.py."""
     import time
     torch.manual_seed(5)
     N, d, B, k = 300_001, 128, 2048, 500
@@ -272,8 +274,9 @@ def test_topk_large_k_large_batch_trending_scores(ra):
 
 
 def test_fullscore_topk_fuzz(ra):
-    """18 random (B, N, d, k) around the dense / filter switch-over (32 768 items) and the tile sizes: logsumexp and
-    exact top-k (values; ids wherever fp32 near-ties do not swap neighbours) against a float64 matmul on the device."""
+    """18 random (B, N, d, k) around FILTER_MIN_ITEMS (32 768 items) and the tile sizes: logsumexp and exact top-k (values;
+    ids wherever fp32 near-ties do not swap neighbours) against a float64 matmul on the device.  By rsa_fullscore_plan every
+    draw below N = 200 003 runs the dense plan, and N = 200 003 the filter plan for k <= 100 (dense at k = 300)."""
     rs = np.random.RandomState(7)
     for it in range(18):
         d = int(rs.choice([32, 64, 128, 100]))

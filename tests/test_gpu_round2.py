@@ -248,9 +248,11 @@ def test_full_catalog_scorers_golden(ra, golden, d, name):
 @pytest.mark.parametrize('mode', ['cos', 'euc'])
 @pytest.mark.parametrize('d,N,B,k', [(128, 40_000, 200, 100), (64, 5_000, 33, 10), (100, 70_001, 130, 50)])
 def test_full_catalog_cos_euc_scores_lse_topk(ra, mode, d, N, B, k):
-    """rsa_fullscore with the cosine / Euclidean tile epilogue: materialised scores, logsumexp and exact top-k (the
-    filter path for large catalogs, the dense select for small ones) against the oracle's formulas; gradients of the
-    materialised path against torch autograd."""
+    """rsa_fullscore with the cosine / Euclidean tile epilogue: materialised scores, logsumexp and exact top-k against the
+    oracle's formulas; gradients of the materialised path against torch autograd.  All three shapes run the DENSE plan
+    (rsa_fullscore_plan: N = 5 000 is below the smallest filtered catalog, and at 40 000 / 70 001 the threshold rank would pass
+    half of the group maxima); the filter epilogue and the exact recompute in these two score modes are covered by
+    tests/test_gpu_topk_paths.py."""
     g = torch.Generator().manual_seed(d + N)
     iw = torch.randn(N, d, generator=g) * (0.5 + torch.rand(N, 1, generator=g) * 2)
     iw[0] = 0
