@@ -18,6 +18,7 @@ import random
 import torch
 import torch.nn.functional as F
 
+from .gather import _EmbedFn
 from .scorer import full_lse
 
 __all__ = ['EdgeDropout', 'NodeDropout', 'InfoNCELoss', 'SGLAugmentation', 'SimGCLAugmentation', 'Item_Crop', 'Item_Mask',
@@ -93,7 +94,6 @@ class InfoNCELoss(torch.nn.Module):
 def _contrast(loss_fn, view1, view2, uid, iid):
     """``view1`` / ``view2``: the (user table, item table) of the two propagations -> the InfoNCE of the rows ``uid`` of the
     user tables plus that of the rows ``iid`` of the item tables, each against the whole second table (its row 0 is skipped)."""
-    from .retriever import _EmbedFn
     # the batch rows through the gather / sorted-scatter node, not index_add
     user_cl_loss, item_cl_loss = (loss_fn(_EmbedFn.apply(t1, idx), _EmbedFn.apply(t2, idx), all_reps=t2)
                                   for t1, t2, idx in zip(view1, view2, (uid, iid)))

@@ -14,7 +14,6 @@ it is a minimal compatible one (the reference's Recommender loop is out of scope
 import copy
 import inspect
 import logging
-import math
 import os
 import time
 from typing import Dict
@@ -25,33 +24,14 @@ import torch
 from . import _native as nat
 from . import eval as rs_eval
 from . import ops
-from .dataset import SeqDataset, TripletDataset, UserDataset
+from .dataset import SeqDataset, TripletDataset
 from .fused import BPRAdagradStep, BPRAdamStep, BPRSGDStep, fused_bpr_loss, fused_ssm_loss, retriever_scores
-from .loss_func import (BinaryCrossEntropyLoss, BPRLoss, FullScoreLoss, PairwiseLoss, PointwiseLoss, SampledSoftmaxLoss,
-                        SoftmaxLoss)
+from .loss_func import BPRLoss, FullScoreLoss, PairwiseLoss, PointwiseLoss, SampledSoftmaxLoss, SoftmaxLoss
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
 from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
-from .seqmodule import AttentionLayer, FusedGRU, FusedTransformerEncoder, MLPModule, caser_conv_torch, caser_pack
-from .seqmodule import hgn_gating, hgn_gating_torch
-from .seqmodule import bag_pool
 
 __all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'CL4SRec', 'GRU4Rec', 'NARM', 'STAMP', 'HGN', 'MultiDAE', 'MultiVAE', 'LightGCN', 'SGL',
            'SimGCL', 'default_config', 'seed_everything']
-
-# ``model.fused_attention_pool`` of NARM and STAMP (the attention pooling as one HIP kernel): on where the kernel beat the
-# reference's op sequence in the same run, forward and forward + backward, at both models' shapes
-FUSED_ATTENTION_POOL_DEFAULT = True
-# ``model.fused_infonce`` of CL4SRec (the in-batch InfoNCE as HIP kernels without [B, 2B]): OFF.  The rule is on only where the kernels
-# are not slower than the reference's op sequence at every measured shape in both directions (tools/bench_cl4srec.py,
-# ``fused_infonce_wins_everywhere``); they win at B = 256 and lose at B = 8192 (2.11 against 1.19 ms forward, 6.07 against 2.30 ms
-# forward + backward at d = 64), where what they buy is memory: 1.7 GB less
-FUSED_INFONCE_DEFAULT = False
-# ``model.fused_gating`` of HGN (both gates, the pooling and the item-item sum as one HIP kernel): on where the kernel beat the
-# reference's op sequence in the same run, forward and forward + backward, at both measured shapes
-FUSED_GATING_DEFAULT = True
-# MultiDAE / MultiVAE: the bag kernel pair (rsa_bag.hip) for the encoder input and the positives' mean -- see DESIGN.md 4.19 for the
-# measurement this default follows from
-FUSED_BAG_DEFAULT = True
 
 
 def default_config():
@@ -191,12 +171,55 @@ def _one_ahead(batches, step, prepare=None):
     return out
 
 
+def _with_next(it):
+    """(x0, x1), (x1, x2), ..., (x_last, None)"""
+    it = iter(it)
+    cur = next(it, None)
+    while cur is not None:
+        nxt = next(it, None)
+        yield cur, nxt
+        cur = nxt
+
+
+class _above_second_stream:
+    """``with`` block whose work runs on a HIGH-priority stream (entered after, left before, the stream that was current):
+    the look-ahead's second stream then sits below the steps it runs under and fills their gaps instead of competing with
+    them (sharded training step one batch ahead, in process: 1.166 ms with both at the default priority, 1.136 ms so)."""
+
+    def __init__(self, on, device, cache):
+        self.on, self.device, self.cache = bool(on), device, cache
+
+    def __enter__(self):
+        if self.on:
+            self.prev = torch.cuda.current_stream(self.device)
+            hi = self.cache.get('hi_stream')
+            if hi is None:
+                hi = self.cache['hi_stream'] = torch.cuda.Stream(device=self.device, priority=-1)
+            hi.wait_stream(self.prev)
+            torch.cuda.set_stream(hi)
+            self.hi = hi
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.prev.wait_stream(self.hi)
+            torch.cuda.set_stream(self.prev)
+        return False
+
+
 class BaseRetriever(torch.nn.Module):
+    # A model's own defaults, ``{'model': {...}, 'train': {...}, 'eval': {...}}`` (its yaml in the reference).  The resolved config is
+    # ``default_config()``, then the ``config_defaults`` of every class in the MRO, base first, then the caller's config: a derived
+    # class's default beats its parent's and the caller beats both.
+    config_defaults = {}
+
     def __init__(self, config: Dict = None, **kwargs):
         super().__init__()
         self.config = default_config()
-        if config is not None:
-            for group, values in config.items():
+        defaults = [copy.deepcopy(vars(klass)['config_defaults']) for klass in reversed(type(self).__mro__)
+                    if 'config_defaults' in vars(klass)]
+        for layer in defaults + [config or {}]:
+            for group, values in layer.items():
                 if isinstance(values, dict) and group in self.config:
                     self.config[group].update(values)
                 else:
@@ -1145,1039 +1168,28 @@ TwoTowerRecommender = BaseRetriever      # README.md:29-31 names
 ItemTowerRecommender = BaseRetriever
 
 
+class _BatchQueryFeat:
+    """Mixin for a retriever whose query tower takes the whole batch dict (the sequence and the autoencoder families)."""
+
+    def _get_query_feat(self, data):
+        return data if isinstance(data, dict) else super()._get_query_feat(data)
+
+
 class BPR(BaseRetriever):
     """recstudio/model/mf/bpr.py:7-25, recstudio/model/mf/config/bpr.yaml (negative_count: 1)."""
 
-    def __init__(self, config=None, **kwargs):
-        super().__init__(config, **kwargs)
-        if 'negative_count' not in (config or {}).get('train', {}):
-            self.config['train']['negative_count'] = 1
-
-    def _get_dataset_class():
-        return TripletDataset
-
-    def _get_item_encoder(self, train_data):
-        return torch.nn.Embedding(train_data.num_items, self.embed_dim, padding_idx=0)
+    config_defaults = {'train': {'negative_count': 1}}
 
     def _get_query_encoder(self, train_data):
         return torch.nn.Embedding(train_data.num_users, self.embed_dim, padding_idx=0)
 
-    def _get_score_func(self):
-        return InnerProductScorer()
-
     def _get_loss_func(self):
         return BPRLoss()
 
-    def _get_sampler(self, train_data):
-        return UniformSampler(train_data.num_items)
 
-
-class LightGCN(BaseRetriever):
-    """recstudio/model/graph/lightgcn.py:14-84, recstudio/model/graph/config/{all,lightgcn}.yaml (n_layers 3, l2_reg_weight 1e-4,
-    negative_count 1).  The base tables ``user_emb`` / ``item_emb`` are propagated over the normalised interaction graph
-    (``graphmodule.NormAdj``, ``rsa_spmm_csr``); everything behind the propagation is the fused path: the propagated item table is
-    the ``item_weight`` of ``fused.retriever_scores``, the propagated user table its ``query_src`` with the batch's user ids as
-    ``query_index`` -- the negatives are drawn in the kernel (the ids ``UniformSampler`` gives for the seed), no [B, n, d] tensor
-    exists, and the dense table gradients flow back into the propagation's backward.  The towers are not nn.Embedding modules,
-    so ``train.fused_optimizer``, multi-GPU ``fit`` and ``train.ann`` refuse this model as they refuse any such tower."""
-
-    def __init__(self, config=None, **kwargs):
-        super().__init__(config, **kwargs)
-        self.config['model'].setdefault('n_layers', 3)
-        self.config['model'].setdefault('l2_reg_weight', 1e-4)
-        given = config or {}
-        for group, key, value in (('train', 'negative_count', 1), ('train', 'early_stop_patience', 100), ('eval', 'cutoff', [20, 10, 5])):
-            if key not in given.get(group, {}):
-                self.config[group][key] = value
-
-    def _init_model(self, train_data, drop_unused_field=True):
-        from . import graphmodule
-        super()._init_model(train_data, drop_unused_field)
-        self.num_users, self.num_items = train_data.num_users, train_data.num_items
-        self.user_emb = torch.nn.Embedding(self.num_users, self.embed_dim, padding_idx=0)
-        self.item_emb = torch.nn.Embedding(self.num_items, self.embed_dim, padding_idx=0)
-        net = self._get_gnn_net()
-        setattr(self, type(net).__name__, net)
-        self.adj_mat = self._get_graph(train_data)
-
-    def _get_gnn_net(self):
-        """The propagation module; ``_init_model`` registers it under its class name."""
-        from . import graphmodule
-        return graphmodule.LightGCNNet(self.config['model']['n_layers'])
-
-    def _get_graph(self, train_data):
-        """The normalised adjacency of the training interactions (``model.spmm_chunk``: the chunk size of its plan, default
-        ``ops.SPMM_CHUNK``)."""
-        from . import graphmodule
-        return graphmodule.NormAdj.from_dataset(train_data, chunk=self.config['model'].get('spmm_chunk'))
-
-    def _get_dataset_class():
-        return TripletDataset
-
-    def _get_loss_func(self):
-        return BPRLoss()
-
-    def _get_score_func(self):
-        return InnerProductScorer()
-
-    def _get_sampler(self, train_data):
-        return UniformSampler(train_data.num_items)
-
-    def _get_query_encoder(self, train_data):
-        from . import graphmodule
-        return graphmodule.GraphUserEncoder()
-
-    def _get_item_encoder(self, train_data):
-        from . import graphmodule
-        return graphmodule.GraphItemEncoder()
-
-    def _propagate(self, embeddings):
-        return self.LightGCNNet.propagate(self.adj_mat, embeddings)
-
-    def update_encoders(self):
-        embeddings = torch.cat([self.user_emb.weight, self.item_emb.weight], dim=0)
-        all_embeddings = self._propagate(embeddings)
-        self.query_encoder.user_embeddings, self.item_encoder.item_embeddings = \
-            all_embeddings[:self.num_users], all_embeddings[self.num_users:]
-
-    def forward(self, batch, full_score=False, return_query=True, return_item=True, return_neg_item=False, return_neg_id=True):
-        self.update_encoders()
-        users, items = self.query_encoder.user_embeddings, self.item_encoder.item_embeddings
-        pos_items, uid = self._get_item_feat(batch), batch[self.fuid]
-        if self.neg_count is None or isinstance(self.neg_count, (list, tuple)) or type(self.score_func) is not InnerProductScorer \
-                or self.config['train'].get('sampling_method', 'none') != 'none' or pos_items.dim() != 1:
-            return self._forward_plugins(batch, full_score, return_query, return_item, return_neg_item, return_neg_id)
-        n = self.neg_count
-        score, neg_ids = retriever_scores(items, users, n, query_index=uid, pos_ids=pos_items, sampler=self.sampler)
-        output = {'score': {'pos_score': score['pos_score'], 'log_pos_prob': score['log_pos_prob'].detach(),
-                            'neg_score': score['neg_score'].view(-1, n), 'log_neg_prob': score['log_neg_prob'].view(-1, n).detach()}}
-        if return_neg_id:
-            output['neg_id'] = neg_ids.view(-1, n)
-        if return_neg_item:
-            output['neg_item'] = self.item_encoder(neg_ids.view(-1, n))
-        if return_query:
-            output['query'] = self.query_encoder(uid)
-        if return_item:
-            output['item'] = self.item_encoder(pos_items)
-        return output
-
-    def training_step(self, batch):
-        from .loss_func import l2_reg_loss_fn
-        output = self.forward(batch, isinstance(self.loss_fn, FullScoreLoss), return_query=False, return_item=False, return_neg_id=True)
-        score = dict(output['score'], label=batch[self.frating])
-        # the regulariser sees the BASE rows of the batch (lightgcn.py:72-73), through the gather / sorted-scatter autograd node
-        reg = l2_reg_loss_fn(_EmbedFn.apply(self.user_emb.weight, batch[self.fuid]),
-                             _EmbedFn.apply(self.item_emb.weight, batch[self.fiid]),
-                             _EmbedFn.apply(self.item_emb.weight, output['neg_id'].reshape(-1)))
-        return self.loss_fn(**score) + self.config['model']['l2_reg_weight'] * reg
-
-    def _get_item_vector(self):
-        if self.item_encoder.item_embeddings is None:
-            return self.item_emb.weight[1:].detach().clone()
-        return self.item_encoder.item_embeddings[1:].detach().clone()
-
-    @torch.no_grad()
-    def _update_item_vector(self):
-        self.update_encoders()
-        super()._update_item_vector()
-
-    def _fullscore_catalog(self):
-        # ``item_vector`` is a plain fp32 table (the propagated item rows): the MFMA top-k reads it as it reads an nn.Embedding's
-        return self.num_items if type(self.score_func) in (InnerProductScorer, CosineScorer, EuclideanScorer) else None
-
-
-class SGL(LightGCN):
-    """recstudio/model/graph/sgl.py:34-114, recstudio/model/graph/config/sgl.yaml (aug_type 'ED', n_layers 3, l2_reg_weight 1e-4,
-    ssl_ratio 0.1, ssl_reg 0.1, temperature 0.2, negative_count 1, batch_size 2048): LightGCN's step plus ``ssl_reg`` times the
-    InfoNCE contrast (users and items) between two randomly thinned views of the graph, drawn afresh every step
-    (``data_augmentation.SGLAugmentation`` on ``rsa_graph_dropout``).  ``last_views`` holds the last step's two views (their
-    masks and degrees; ``ssl_reg: 0`` draws none and is LightGCN's step).  Evaluation propagates over the full graph and is
-    LightGCN's.
-
-    Two deliberate deviations from the reference.  (1) sgl.py:101-103 ends a line with a stray comma, so ``training_step``
-    returns a tuple and ``Recommender.training_epoch`` (recommender.py:615-639) runs no backward at all; here the loss is the sum
-    those three lines plainly intend.  (2) Which edges fall is defined by the device ``torch.rand`` stream in CSR edge order, not
-    by ``dgl.DropEdge``'s stream, which cannot be reproduced without dgl; the distribution is the same."""
-
-    def __init__(self, config=None, **kwargs):
-        super().__init__(config, **kwargs)
-        for key, value in (('aug_type', 'ED'), ('ssl_ratio', 0.1), ('ssl_reg', 0.1), ('temperature', 0.2)):
-            self.config['model'].setdefault(key, value)
-        if 'batch_size' not in (config or {}).get('train', {}):
-            self.config['train']['batch_size'] = 2048
-
-    def _init_model(self, train_data, drop_unused_field=True):
-        from . import data_augmentation
-        super()._init_model(train_data, drop_unused_field)
-        self.augmentaion_model = data_augmentation.SGLAugmentation(self.config['model'], train_data)
-
-    @property
-    def last_views(self):
-        return self.augmentaion_model.last_views
-
-    def training_step(self, batch):
-        loss = super().training_step(batch)
-        if not self.config['model']['ssl_reg']:
-            return loss
-        cl_output = self.augmentaion_model(batch, self.user_emb, self.item_emb, self.adj_mat, self.LightGCNNet)
-        return loss + self.config['model']['ssl_reg'] * cl_output['cl_loss']
-
-
-class SimGCL(LightGCN):
-    """recstudio/model/graph/simgcl.py:35-110, recstudio/model/graph/config/simgcl.yaml (eps 0.1, n_layers 3, l2_reg_weight 1e-4,
-    cl_neg_type 'all', temperature 0.2, batch_size 2048, learning_rate 0.001, negative_count 1): LightGCN's step -- BPR on
-    uniform negatives plus the l2 regulariser of the base rows -- over ``graphmodule.SimGCLNet``, whose layer mean SKIPS the
-    input (mean(E_1 .. E_L), which ``evaluate`` / ``topk`` use as well), plus the InfoNCE contrast between two noise-perturbed
-    propagations of the same graph (``data_augmentation.SimGCLAugmentation``; the noise is added inside ``rsa_spmm_csr``).  The
-    device stream of a step: the negatives first, then the L ``rand_like`` calls of view 1, then those of view 2.
-
-    ``model.cl_weight`` (0.5 in simgcl.yaml) is accepted and NOT applied: nothing in the reference reads it, simgcl.py:98 adds
-    ``cl_loss`` with weight 1, and so does this class."""
-
-    def __init__(self, config=None, **kwargs):
-        super().__init__(config, **kwargs)
-        for key, value in (('eps', 0.1), ('cl_weight', 0.5), ('cl_neg_type', 'all'), ('temperature', 0.2)):
-            self.config['model'].setdefault(key, value)
-        given = (config or {}).get('train', {})
-        for key, value in (('batch_size', 2048), ('learning_rate', 0.001)):
-            if key not in given:
-                self.config['train'][key] = value
-
-    def _init_model(self, train_data, drop_unused_field=True):
-        from . import data_augmentation
-        super()._init_model(train_data, drop_unused_field)
-        self.augmentation_model = data_augmentation.SimGCLAugmentation(self.config['model'], train_data)
-
-    def _get_gnn_net(self):
-        from . import graphmodule
-        return graphmodule.SimGCLNet(self.config['model']['n_layers'], self.config['model']['eps'])
-
-    def _propagate(self, embeddings):
-        return self.SimGCLNet.propagate(self.adj_mat, embeddings)
-
-    def training_step(self, batch):
-        loss = super().training_step(batch)                    # the negatives are drawn here, before the noise
-        cl_output = self.augmentation_model(batch, self.user_emb, self.item_emb, self.adj_mat, self.SimGCLNet)
-        return loss + cl_output['cl_loss']
-
-
-class NGCF(LightGCN):
-    """recstudio/model/graph/ngcf.py:14-96, recstudio/model/graph/config/ngcf.yaml (layer_size [64, 64, 64, 64], mess_dropout
-    [0.1, 0.1, 0.1], node_dropout 0.1 -- ``None`` switches it off --, l2_reg_weight 1e-5, batch_size 2048, learning_rate 1e-4,
-    negative_count 1).  The base tables are propagated by ``graphmodule.NGCFNet``: per layer one ``rsa_spmm_csr`` over the
-    left-normalised graph (``graphmodule.LeftAdj``) and one fused ``BiCombiner`` (``rsa_bi_combine``); the result is
-    ``cat(x_0, normalize(h_1), ..., normalize(h_L))``, sum(layer_size) wide (at most 256, the widest table the fused BPR tail and
-    the MFMA top-k take), and everything behind it -- the fused forward, ``training_step`` (BPR plus the l2 regulariser of the BASE
-    rows), ``evaluate`` / ``topk`` -- is LightGCN's.  ``embed_dim`` must equal ``layer_size[0]``.  Evaluation propagates over
-    the full graph without any dropout.
-
-    The device generator of a training step is consumed in this order: the edge mask (``torch.rand(nnz)``, with ``node_dropout``),
-    then the L message-dropout calls in layer order (``torch.rand(n_nodes, layer_size[k])``), then the negatives.
-
-    Two deliberate deviations from the reference, both in WHICH elements fall, neither in how many.  (1) ``node_dropout`` is an
-    edge dropout in the reference too (``EdgeDropout`` -> ``dgl.DropEdge``); here the kept edges are defined by the device
-    ``torch.rand`` stream in CSR edge order (``rsa_graph_dropout``), as for SGL.  (2) The message dropout keeps element (r, c)
-    iff ``torch.rand_like(h)[r, c] < fp32(1 - p)`` and divides by that; ``nn.Dropout``'s kernel walks the same Philox stream in
-    another layout (``graphmodule.BiCombiner``)."""
-
-    MAX_WIDTH = 256
-
-    def __init__(self, config=None, **kwargs):
-        super().__init__(config, **kwargs)
-        model, given = self.config['model'], config or {}
-        for key, value in (('layer_size', [64, 64, 64, 64]), ('node_dropout', 0.1)):
-            model.setdefault(key, value)
-        model['n_layers'] = len(model['layer_size']) - 1
-        model.setdefault('mess_dropout', [0.1] * (len(model['layer_size']) - 1))
-        if 'l2_reg_weight' not in given.get('model', {}):
-            model['l2_reg_weight'] = 1e-5
-        for key, value in (('batch_size', 2048), ('learning_rate', 1e-4)):
-            if key not in given.get('train', {}):
-                self.config['train'][key] = value
-        layers = [int(v) for v in model['layer_size']]
-        if len(layers) < 2 or len(model['mess_dropout']) != len(layers) - 1:
-            raise ValueError(f'NGCF: layer_size {layers} needs at least one layer and one mess_dropout per layer, got '
-                             f'{model["mess_dropout"]}')
-        if self.embed_dim != layers[0]:
-            raise ValueError(f'NGCF: embed_dim ({self.embed_dim}) must equal layer_size[0] ({layers[0]})')
-        if sum(layers) > self.MAX_WIDTH:
-            raise ValueError(f'NGCF: the concatenated table is sum(layer_size) = {sum(layers)} wide; the fused BPR tail and the '
-                             f'top-k kernels take tables of at most {self.MAX_WIDTH} columns')
-        drop = model['node_dropout']
-        if drop is not None and not 0.0 <= float(drop) < 1.0:
-            raise ValueError(f'NGCF: node_dropout must be None or lie in [0, 1), got {drop}')
-
-    def _init_model(self, train_data, drop_unused_field=True):
-        from . import graphmodule
-        super()._init_model(train_data, drop_unused_field)
-        self.left_adj = graphmodule.LeftAdj(self.adj_mat)
-        self.last_view = None
-
-    def _get_gnn_net(self):
-        from . import graphmodule
-        model = self.config['model']
-        layers = [int(v) for v in model['layer_size']]
-        self.combiners = torch.nn.ModuleList(graphmodule.BiCombiner(a, b, dropout=float(p))
-                                             for a, b, p in zip(layers[:-1], layers[1:], model['mess_dropout']))
-        return graphmodule.NGCFNet(self.combiners, len(layers) - 1)
-
-    def _propagate(self, embeddings):
-        from . import graphmodule
-        drop = self.config['model']['node_dropout']
-        adj = self.left_adj
-        if self.training and drop:
-            self.adj_mat.to(embeddings.device)
-            adj = self.last_view = graphmodule.LeftAdj.thinned(self.adj_mat, 1.0 - float(drop))
-        return self.NGCFNet.propagate(adj, embeddings)
-
-
-class _EmbedFn(torch.autograd.Function):
-    """item_encoder(ids) with the HIP gather forward and the HIP row scatter-add backward."""
-
-    @staticmethod
-    def forward(ctx, weight, ids):
-        ctx.save_for_backward(ids)
-        ctx.n_rows = weight.shape[0]
-        return ops.embedding_gather(weight, ids)
-
-    @staticmethod
-    def backward(ctx, g):
-        (ids,) = ctx.saved_tensors
-        return _embedding_grad(g, ids, ctx.n_rows), None
-
-
-class _above_second_stream:
-    """``with`` block whose work runs on a HIGH-priority stream (entered after, left before, the stream that was current):
-    the look-ahead's second stream then sits below the steps it runs under and fills their gaps instead of competing with
-    them (sharded training step one batch ahead, in process: 1.166 ms with both at the default priority, 1.136 ms so)."""
-
-    def __init__(self, on, device, cache):
-        self.on, self.device, self.cache = bool(on), device, cache
-
-    def __enter__(self):
-        if self.on:
-            self.prev = torch.cuda.current_stream(self.device)
-            hi = self.cache.get('hi_stream')
-            if hi is None:
-                hi = self.cache['hi_stream'] = torch.cuda.Stream(device=self.device, priority=-1)
-            hi.wait_stream(self.prev)
-            torch.cuda.set_stream(hi)
-            self.hi = hi
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.prev.wait_stream(self.hi)
-            torch.cuda.set_stream(self.prev)
-        return False
-
-
-def _with_next(it):
-    """(x0, x1), (x1, x2), ..., (x_last, None)"""
-    it = iter(it)
-    cur = next(it, None)
-    while cur is not None:
-        nxt = next(it, None)
-        yield cur, nxt
-        cur = nxt
-
-
-def _embedding_grad(g, ids, n_rows):
-    """Dense ``weight.grad`` of an item-row gather (embedding_dense_backward with padding_idx = 0): rows sorted by item id
-    and summed run by run without atomics (``rsa_rows_update_sorted``; bit-reproducible) for the stock dims, the
-    float-atomic scatter otherwise."""
-    d = g.shape[-1]
-    rows = g.reshape(-1, d).contiguous()
-    flat_ids = ids.reshape(-1, 1).contiguous()
-    if d in (64, 128, 256) and rows.shape[0] > 0:
-        ones = torch.ones(rows.shape[0], 1, dtype=torch.float32, device=g.device)
-        return ops.scatter_rows_sorted(torch.zeros(n_rows, d, dtype=torch.float32, device=g.device), rows, flat_ids, ones, pad_row=0)
-    return ops.scatter_add_rows(rows, flat_ids.view(-1), n_rows)
-
-
-class _SegEmbedFn(torch.autograd.Function):
-    """item_encoder(in_item_id) straight from the CSR view of the interaction column (dataset.py:1418-1439 +
-    seq/sasrec.py:42): ``rsa_seg_gather`` reads ``[start, end)`` of the flat item column and writes the right-padded
-    ``[B, L, d]`` rows -- no ``[B, L]`` id tensor is re-read; the backward is the sorted, atomics-free row scatter."""
-
-    @staticmethod
-    def forward(ctx, weight, flat, start, end, max_len, ids):
-        ctx.save_for_backward(ids)
-        ctx.n_rows = weight.shape[0]
-        return ops.seg_gather(weight, flat, start, end, int(max_len), want_rows=True, want_ids=False)[1]
-
-    @staticmethod
-    def backward(ctx, g):
-        (ids,) = ctx.saved_tensors
-        return _embedding_grad(g, ids, ctx.n_rows), None, None, None, None, None
-
-
-class SASRecQueryEncoder(torch.nn.Module):
-    """recstudio/model/seq/sasrec.py:8-67: item-embedding gather of the history (HIP) + learned positions
-    + nn.TransformerEncoder (causal unless ``bidirectional``) + last-position pooling.  The encoder is stock PyTorch-ROCm by
-    default; with ``fused_attention`` its layers run through ``seqmodule.FusedTransformerEncoder`` (the attention core as one
-    HIP kernel) over the same parameters: ``state_dict`` is the same either way.
-
-    ``need_pooling=False`` returns the tower's ``[B, L, D]`` (what CL4SRec's views are mean-pooled from).  With ``mask_id`` (CL4SRec:
-    ``num_items``) the encoder owns ``mask_emb`` [1, D], the row of the mask token: the ids
-    equal to ``mask_id`` are gathered as row 0 (the zero padding row) through the same gather node and ``mask_emb`` is added at those
-    positions, while ``key_pad`` stays ``ids == 0`` on the ORIGINAL ids, so masked positions are attended.  The catalog table keeps
-    its ``num_items`` rows (the reference widens it by one, cl4srec.py:33-34): ``mask_id`` never reaches the gather, the sampler or
-    ``topk``."""
-
-    def __init__(self, fiid, embed_dim, max_seq_len, n_head, hidden_size, dropout, activation, layer_norm_eps, n_layer,
-                 item_encoder, bidirectional=False, fused_attention=False, mask_id=None):
-        super().__init__()
-        self.fiid = fiid
-        self.mask_id = mask_id
-        if mask_id is not None:
-            self.mask_emb = torch.nn.Parameter(torch.zeros(1, embed_dim))
-        self.item_encoder = item_encoder
-        self.bidirectional = bool(bidirectional)
-        self.fused_attention = bool(fused_attention)
-        self.position_emb = torch.nn.Embedding(max_seq_len, embed_dim)
-        layer = torch.nn.TransformerEncoderLayer(d_model=embed_dim, nhead=n_head, dim_feedforward=hidden_size,
-                                                 dropout=dropout, activation=activation, layer_norm_eps=layer_norm_eps,
-                                                 batch_first=True, norm_first=False)
-        self.transformer_layer = torch.nn.TransformerEncoder(layer, num_layers=n_layer)
-        self.dropout = torch.nn.Dropout(p=dropout)
-        # (no parameters of its own: it reads transformer_layer's at call time)
-        self._fused = FusedTransformerEncoder(self.transformer_layer, max_seq_len) if self.fused_attention else None
-
-    def forward(self, batch, need_pooling=True):
-        user_hist = batch['in_' + self.fiid]
-        B, L = user_hist.shape
-        positions = torch.arange(L, dtype=torch.long, device=user_hist.device).unsqueeze(0).expand(B, L)
-        seg = batch.get('_seg')
-        masked = None
-        ids = user_hist
-        if self.mask_id is not None and seg is None:
-            # any ids handed over as a tensor (a view of CL4SRec): the mask token is no catalog row.  (The CSR view of the loader
-            # gathers from the dataset's own item column, which holds no mask token.)
-            masked = user_hist == self.mask_id
-            ids = torch.where(masked, torch.zeros_like(user_hist), user_hist)
-        if not isinstance(self.item_encoder, torch.nn.Embedding):
-            # the row-sharded catalog (shard.ShardedRows put here by BaseRetriever._setup_shard): ids out, rows back
-            rows = self.item_encoder(ids)
-        elif not user_hist.is_cuda and (self._fused is not None or self.mask_id is not None):
-            # the torch-op twin of the fused tower (seqmodule.seq_attention_torch) on CPU tensors: parity checks without a device
-            rows = self.item_encoder(ids)
-        elif seg is not None and user_hist.is_cuda:
-            # the device loader handed over the CSR view (flat item column, start, end): the fused segment gather emits
-            # [B, L, d] directly (SURVEY.md 8a D2); ``in_item_id`` only serves the padding mask and the backward
-            flat, start, end = seg
-            rows = _SegEmbedFn.apply(self.item_encoder.weight, flat, start, end, L, user_hist)
-        else:
-            rows = _EmbedFn.apply(self.item_encoder.weight, ids)
-        if masked is not None:
-            rows = rows + masked.unsqueeze(-1).to(rows.dtype) * self.mask_emb
-        seq = rows + self.position_emb(positions)
-        if self._fused is not None:
-            out = self._fused(self.dropout(seq), key_pad=user_hist == 0, causal=not self.bidirectional)
-        else:
-            if self.bidirectional:
-                mask = torch.zeros(L, L, dtype=torch.bool, device=user_hist.device)
-            else:
-                mask = torch.triu(torch.ones(L, L, dtype=torch.bool, device=user_hist.device), 1)
-            out = self.transformer_layer(self.dropout(seq), mask=mask, src_key_padding_mask=user_hist == 0)
-        if not need_pooling:
-            return out
-        last = (batch['seqlen'] - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, out.shape[-1])
-        return out.gather(1, last).squeeze(1)
-
-
-class SASRec(BaseRetriever):
-    """recstudio/model/seq/sasrec.py:70-123 with the retriever tail on the fused path."""
-
-    def __init__(self, config=None, **kwargs):
-        # recstudio/model/seq/config/sasrec.yaml on top of basemodel.yaml; the caller's config wins
-        user = config or {}
-        super().__init__(config, **kwargs)
-        m = self.config['model']
-        for k, v in (('hidden_size', 128), ('layer_num', 2), ('head_num', 2), ('dropout_rate', 0.5),
-                     ('activation', 'gelu'), ('layer_norm_eps', 1e-12), ('fused_attention', False)):
-            m.setdefault(k, v)
-        for k, v in (('negative_count', 1), ('init_method', 'normal')):
-            if k not in user.get('train', {}):
-                self.config['train'][k] = v
-
-    def _get_dataset_class():
-        return SeqDataset
-
-    def _get_query_encoder(self, train_data):
-        m = self.config['model']
-        return SASRecQueryEncoder(self.fiid, self.embed_dim, train_data.config['max_seq_len'], m['head_num'],
-                                  m['hidden_size'], m['dropout_rate'], m['activation'], m['layer_norm_eps'],
-                                  m['layer_num'], self.item_encoder, fused_attention=m['fused_attention'])
-
-    def _get_query_feat(self, data):
-        return data if isinstance(data, dict) else super()._get_query_feat(data)
-
-    def _get_loss_func(self):
-        return BinaryCrossEntropyLoss()         # sasrec.py:117-119
-
-    def _get_sampler(self, train_data):
-        return UniformSampler(train_data.num_items)
-
-
-class CL4SRec(SASRec):
-    """recstudio/model/seq/cl4srec.py:13-53, recstudio/model/seq/config/cl4srec.yaml (hidden_size 64, layer_num 1, temperature 1.0,
-    augment_type 'item_crop', tau 0.2, cl_weight 0.1) on top of SASRec's: SASRec's step plus ``cl_weight`` times the in-batch InfoNCE
-    between two augmented views of every history, drawn afresh every step (``data_augmentation.CL4SRecAugmentation``).  The tower
-    runs three times per step: the main pass and one pass per view.  ``last_views`` holds the last step's two views.
-
-    A view is ONE launch of ``rsa_seq_augment`` with ``model.fused_augment`` (default on: faster than the twin at every measured shape), the same rule in batched torch ops
-    (``seq_augment_torch``) without it, on CPU tensors or above 64 positions -- the same view either way.  The in-batch InfoNCE is
-    ``rsa_batch_infonce`` / ``rsa_batch_infonce_backward`` with ``model.fused_infonce`` (nothing of size B^2, forward or backward;
-    off by default: slower than the op sequence at B = 8192, see ``FUSED_INFONCE_DEFAULT``), the reference's op sequence
-    (``batch_infonce_torch``, which holds [B, 2B]) without it, on CPU tensors or at other widths.
-
-    THE GENERATOR ORDER OF A STEP (device stream): the main pass (the tower's dropouts, then the negatives), ``rand([B, L + 1])`` for
-    view i, the same for view j, the tower's dropouts for view i, then those for view j.  ``item_random`` also takes one
-    ``random.randint(0, 2)`` per view from Python's generator.
-
-    Deliberate deviations from the reference.  (1) The views follow the device ``torch.rand`` stream, not the reference's three host
-    generators behind one ``.item()`` per sequence (2 B synchronisations per step).  (2) A cropped batch keeps its width L
-    (``pad_sequence`` narrows it); the encoder's output on the kept positions is the same.  (3) The mask token is not row
-    ``num_items`` of a widened item table (cl4srec.py:33-34, which the reference's evaluation then scores like an item) but the
-    query encoder's own ``mask_emb`` [1, d]: the catalog table keeps ``num_items`` rows, so the sampler, the fused tail, ``topk``
-    and ``evaluate`` run unchanged and never see ``num_items``; a reference checkpoint's trailing row is ``mask_emb``.  (4) The
-    training form is this tree's SASRec's (``SeqDataset``, last-position pooling, BCE with one negative); the reference's uses
-    ``SeqToSeqDataset`` with a loss at every position."""
-
-    def __init__(self, config=None, **kwargs):
-        user = (config or {}).get('model', {})
-        super().__init__(config, **kwargs)
-        m = self.config['model']
-        for k, v in (('hidden_size', 64), ('layer_num', 1)):
-            if k not in user:
-                m[k] = v
-        for k, v in (('temperature', 1.0), ('augment_type', 'item_crop'), ('tau', 0.2), ('cl_weight', 0.1), ('fused_augment', True),
-                     ('fused_infonce', FUSED_INFONCE_DEFAULT)):
-            m.setdefault(k, v)
-
-    def _init_model(self, train_data, drop_unused_field=True):
-        from . import data_augmentation
-        super()._init_model(train_data, drop_unused_field)
-        self.augmentation_model = data_augmentation.CL4SRecAugmentation(self.config['model'], train_data)
-
-    def _get_query_encoder(self, train_data):
-        m = self.config['model']
-        return SASRecQueryEncoder(self.fiid, self.embed_dim, train_data.config['max_seq_len'], m['head_num'],
-                                  m['hidden_size'], m['dropout_rate'], m['activation'], m['layer_norm_eps'],
-                                  m['layer_num'], self.item_encoder, fused_attention=m['fused_attention'],
-                                  mask_id=train_data.num_items)
-
-    def _init_parameter(self):
-        super()._init_parameter()
-        # the mask token like a row of the item table (recstudio/model/init.py on the reference's [num_items + 1, d] table); drawn
-        # last, so every other parameter is SASRec's at the same seed
-        w = self.query_encoder.mask_emb.data
-        method, (n, d) = self.config['train']['init_method'], self.item_encoder.weight.shape
-        if method == 'xavier_normal':
-            w.normal_(mean=0.0, std=math.sqrt(2.0 / (n + 1 + d)))
-        elif method == 'xavier_uniform':
-            bound = math.sqrt(6.0 / (n + 1 + d))
-            w.uniform_(-bound, bound)
-        else:
-            w.normal_(mean=0.0, std=0.02)
-
-    @property
-    def last_views(self):
-        return self.augmentation_model.last_views
-
-    def training_step(self, batch):
-        loss = super().training_step(batch)
-        if not self.config['model']['cl_weight']:
-            return loss
-        cl_output = self.augmentation_model(batch, self.query_encoder)
-        return loss + self.config['model']['cl_weight'] * cl_output['cl_loss']
-
-
-class GRU4RecQueryEncoder(torch.nn.Module):
-    """recstudio/model/seq/gru4rec.py:36-53: item-embedding gather of the history (HIP) + nn.Dropout + module.GRULayer (an
-    ``nn.GRU`` with ``bias=False``, ``batch_first=True``) + last-position pooling + nn.Linear(hidden_size, embed_dim).  With
-    ``fused_gru`` the GRU runs through ``seqmodule.FusedGRU`` (the recurrence as one HIP kernel, stopped at ``seqlen``) over the
-    same parameters: ``state_dict`` is the same either way.  In train mode the device generator is consumed once per call, by
-    the ``nn.Dropout`` on the gathered rows."""
-
-    def __init__(self, fiid, embed_dim, hidden_size, dropout, n_layer, item_encoder, fused_gru=True):
-        super().__init__()
-        self.fiid = fiid
-        self.item_encoder = item_encoder
-        self.fused_gru = bool(fused_gru)
-        self.dropout = torch.nn.Dropout(p=dropout)
-        self.gru = torch.nn.GRU(input_size=embed_dim, hidden_size=hidden_size, num_layers=n_layer, bias=False, batch_first=True,
-                                bidirectional=False)
-        self.dense = torch.nn.Linear(hidden_size, embed_dim)
-        # (no parameters of its own: it reads gru's at call time)
-        self._fused = FusedGRU(self.gru) if self.fused_gru else None
-
-    def forward(self, batch):
-        user_hist = batch['in_' + self.fiid]
-        L = user_hist.shape[1]
-        seg = batch.get('_seg')
-        if not isinstance(self.item_encoder, torch.nn.Embedding) or not user_hist.is_cuda:
-            # the row-sharded catalog (shard.ShardedRows put here by BaseRetriever._setup_shard): ids out, rows back; or CPU
-            # tensors (the torch-op twin of the fused recurrence: parity checks without a device)
-            rows = self.item_encoder(user_hist)
-        elif seg is not None:
-            flat, start, end = seg
-            rows = _SegEmbedFn.apply(self.item_encoder.weight, flat, start, end, L, user_hist)
-        else:
-            rows = _EmbedFn.apply(self.item_encoder.weight, user_hist)
-        seqlen = batch['seqlen']
-        if self._fused is not None:
-            out, _ = self._fused(self.dropout(rows), lengths=seqlen, want_state=False)
-        else:
-            out, _ = self.gru(self.dropout(rows))
-        last = (seqlen - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, out.shape[-1])
-        return self.dense(out.gather(1, last).squeeze(1))
-
-
-class GRU4Rec(BaseRetriever):
-    """recstudio/model/seq/gru4rec.py:17-63 with the retriever tail on the fused BPR path."""
-
-    def __init__(self, config=None, **kwargs):
-        # recstudio/model/seq/config/gru4rec.yaml on top of basemodel.yaml; the caller's config wins
-        user = config or {}
-        super().__init__(config, **kwargs)
-        m = self.config['model']
-        for k, v in (('hidden_size', 128), ('dropout_rate', 0.3), ('layer_num', 1), ('fused_gru', True)):
-            m.setdefault(k, v)
-        if 'negative_count' not in user.get('train', {}):
-            self.config['train']['negative_count'] = 1
-
-    def _get_dataset_class():
-        return SeqDataset
-
-    def _get_query_encoder(self, train_data):
-        m = self.config['model']
-        return GRU4RecQueryEncoder(self.fiid, self.embed_dim, m['hidden_size'], m['dropout_rate'], m['layer_num'],
-                                   self.item_encoder, fused_gru=m['fused_gru'])
-
-    def _get_query_feat(self, data):
-        return data if isinstance(data, dict) else super()._get_query_feat(data)
-
-    def _get_score_func(self):
-        return InnerProductScorer()
-
-    def _get_loss_func(self):
-        return BPRLoss()
-
-    def _get_sampler(self, train_data):
-        return UniformSampler(train_data.num_items)
-
-
-def _history_rows(item_encoder, batch, fiid):
-    """``item_encoder(in_item_id)`` [B, L, d] of a sequence tower: the HIP gather (from the device loader's CSR view when the
-    batch carries one) for an ``nn.Embedding`` on device tensors, the module itself otherwise (a sharded catalog; CPU tensors)."""
-    user_hist = batch['in_' + fiid]
-    seg = batch.get('_seg')
-    if not isinstance(item_encoder, torch.nn.Embedding) or not user_hist.is_cuda:
-        return item_encoder(user_hist)
-    if seg is not None:
-        flat, start, end = seg
-        return _SegEmbedFn.apply(item_encoder.weight, flat, start, end, user_hist.shape[1], user_hist)
-    return _EmbedFn.apply(item_encoder.weight, user_hist)
-
-
-def _last_position(out, seqlen):
-    """SeqPoolingLayer(pooling_type='last'): ``out[b, seqlen[b] - 1]``."""
-    last = (seqlen - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, out.shape[-1])
-    return out.gather(1, last).squeeze(1)
-
-
-class NARMQueryEncoder(torch.nn.Module):
-    """recstudio/model/seq/narm.py:15-47: item-embedding gather of the history (HIP) + nn.Dropout + module.GRULayer (an ``nn.GRU``
-    with ``bias=False``) -> ``c_global`` = the state at the last position; ``c_local`` = ``AttentionLayer(q_dim=hidden_size,
-    mlp_layers=[hidden_size], bias=False)`` of that state over every GRU state (``seqmodule.AttentionLayer``: the pooling as one
-    HIP kernel with ``fused_attention_pool``); ``fc`` = nn.Dropout + nn.Linear(2 hidden_size, embed_dim, bias=False) of their
-    concatenation.  The GRU sits under ``gru_layer.2.gru`` as in the reference; with ``fused_gru`` it runs through
-    ``seqmodule.FusedGRU``.  ``state_dict`` is the same whichever flags are set.
-    In train mode the device generator is consumed TWICE per call, in this order: the ``nn.Dropout`` on the gathered rows
-    (``gru_layer.1``), then the ``nn.Dropout`` on ``cat(c_global, c_local)`` (``fc.0``).
-    The fused GRU writes zeros at ``t >= seqlen`` where ``nn.GRU`` runs on; the padding mask gives those positions weight 0 and
-    gradient 0 either way, so the query is the same."""
-
-    def __init__(self, fiid, embed_dim, hidden_size, layer_num, dropout_rate, item_encoder=None, fused_gru=True,
-                 fused_attention_pool=True):
-        super().__init__()
-        self.fiid = fiid
-        self.item_encoder = item_encoder
-        self.fused_gru = bool(fused_gru)
-        gru_layer = torch.nn.Module()
-        gru_layer.gru = torch.nn.GRU(input_size=embed_dim, hidden_size=hidden_size, num_layers=layer_num, bias=False,
-                                     batch_first=True, bidirectional=False)
-        # (the reference's Sequential(item_encoder, Dropout, GRULayer): the item encoder is registered once, above)
-        self.gru_layer = torch.nn.ModuleDict({'1': torch.nn.Dropout(dropout_rate[0]), '2': gru_layer})
-        self.attn_layer = AttentionLayer(q_dim=hidden_size, mlp_layers=[hidden_size], bias=False)
-        self.attn_layer.fused = bool(fused_attention_pool)
-        self.fc = torch.nn.Sequential(torch.nn.Dropout(dropout_rate[1]), torch.nn.Linear(hidden_size * 2, embed_dim, bias=False))
-        self._fused = FusedGRU(gru_layer.gru) if self.fused_gru else None
-
-    def forward(self, batch):
-        user_hist = batch['in_' + self.fiid]
-        rows = self.gru_layer['1'](_history_rows(self.item_encoder, batch, self.fiid))
-        seqlen = batch['seqlen']
-        if self._fused is not None:
-            gru_vec, _ = self._fused(rows, lengths=seqlen, want_state=False)
-        else:
-            gru_vec, _ = self.gru_layer['2'].gru(rows)
-        c_global = h_t = _last_position(gru_vec, seqlen)                                           # B x H
-        c_local = self.attn_layer(query=h_t.unsqueeze(1), key=gru_vec, value=gru_vec, key_padding_mask=user_hist == 0,
-                                  need_weight=False).squeeze(1)                                    # B x H
-        return self.fc(torch.cat((c_global, c_local), dim=1))                                      # B x D
-
-
-class _SeqSoftmaxRetriever(BaseRetriever):
-    """What NARM and STAMP share: SeqDataset, InnerProductScorer, SoftmaxLoss and no sampler -- ``training_step`` takes the
-    'full_softmax' path, which never holds [B, N]."""
-
-    def _get_dataset_class():
-        return SeqDataset
-
-    def _get_query_feat(self, data):
-        return data if isinstance(data, dict) else super()._get_query_feat(data)
-
-    def _get_score_func(self):
-        return InnerProductScorer()
-
-    def _get_loss_func(self):
-        return SoftmaxLoss()
-
-    def _get_sampler(self, train_data):
-        return None
-
-
-class NARM(_SeqSoftmaxRetriever):
-    """recstudio/model/seq/narm.py:50-88 with the retriever tail on the fused full-softmax path."""
-
-    def __init__(self, config=None, **kwargs):
-        # recstudio/model/seq/config/narm.yaml on top of basemodel.yaml; the caller's config wins
-        super().__init__(config, **kwargs)
-        m = self.config['model']
-        for k, v in (('hidden_size', 128), ('dropout_rate', [0.25, 0.5]), ('layer_num', 1), ('fused_gru', True),
-                     ('fused_attention_pool', FUSED_ATTENTION_POOL_DEFAULT)):
-            m.setdefault(k, v)
-
-    def _get_dataset_class():
-        return SeqDataset
-
-    def _get_query_encoder(self, train_data):
-        m = self.config['model']
-        return NARMQueryEncoder(self.fiid, self.embed_dim, m['hidden_size'], m['layer_num'], m['dropout_rate'], self.item_encoder,
-                                fused_gru=m['fused_gru'], fused_attention_pool=m['fused_attention_pool'])
-
-
-class STAMPQueryEncoder(torch.nn.Module):
-    """recstudio/model/seq/stamp.py:6-32: ``m_t`` = the last item's embedding, ``m_s`` = the mean of the history's, ``m_a`` =
-    ``AttentionLayer(q_dim=2 embed_dim, k_dim=embed_dim, mlp_layers=[embed_dim])`` of ``cat(m_t, m_s)`` over the history rows
-    (``seqmodule.AttentionLayer``: one HIP kernel with ``fused_attention_pool``), query = ``mlpA(m_a) * mlpB(m_t)`` (two
-    ``MLPModule([embed_dim, embed_dim], Tanh)``).  No dropout is active: the generator is not consumed."""
-
-    def __init__(self, fiid, embed_dim, item_encoder, fused_attention_pool=True):
-        super().__init__()
-        self.fiid = fiid
-        self.item_encoder = item_encoder
-        self.attention_layer = AttentionLayer(q_dim=2 * embed_dim, k_dim=embed_dim, mlp_layers=[embed_dim])
-        self.attention_layer.fused = bool(fused_attention_pool)
-        self.mlpA = MLPModule([embed_dim, embed_dim], torch.nn.Tanh())
-        self.mlpB = MLPModule([embed_dim, embed_dim], torch.nn.Tanh())
-
-    def forward(self, batch):
-        user_hist = batch['in_' + self.fiid]
-        seq_emb = _history_rows(self.item_encoder, batch, self.fiid)
-        m_t = _last_position(seq_emb, batch['seqlen'])
-        m_s = seq_emb.sum(dim=1) / batch['seqlen'].unsqueeze(1).float()                            # B x D
-        query = torch.cat((m_t, m_s), dim=1)                                                       # B x 2D
-        m_a = self.attention_layer(query.unsqueeze(1), seq_emb, seq_emb, key_padding_mask=(user_hist == 0)).squeeze(1)
-        return self.mlpA(m_a) * self.mlpB(m_t)
-
-
-class STAMP(_SeqSoftmaxRetriever):
-    """recstudio/model/seq/stamp.py:35-61 with the retriever tail on the fused full-softmax path."""
-
-    def __init__(self, config=None, **kwargs):
-        # recstudio/model/seq/config/stamp.yaml (embed_dim 64) on top of basemodel.yaml; the caller's config wins
-        super().__init__(config, **kwargs)
-        self.config['model'].setdefault('fused_attention_pool', FUSED_ATTENTION_POOL_DEFAULT)
-
-    def _get_dataset_class():
-        return SeqDataset
-
-    def _get_query_encoder(self, train_data):
-        return STAMPQueryEncoder(self.fiid, self.embed_dim, self.item_encoder,
-                                 fused_attention_pool=self.config['model']['fused_attention_pool'])
-
-
-class CaserQueryEncoder(torch.nn.Module):
-    """recstudio/model/seq/caser.py:16-56, same constructor arguments, same submodules (``user_embedding``, ``item_embedding`` --
-    the tower's OWN [num_items, embed_dim] table, not the item encoder --, ``vertical_filter``, ``horizontal_filter.{i}``, ``fc``)
-    and so the same ``state_dict``.  The history ids are padded to ``max_seq_len`` (:39) and gathered through ``_history_rows``;
-    everything between that gather and the dropout in front of ``fc`` is ``seqmodule.caser_conv_torch``, the reference's op
-    sequence over the ``Conv2d`` modules' own parameters; then ``nn.Dropout``, ``relu(fc(.))`` and ``cat((z, P_u))``: a query of
-    width 2 embed_dim.  In train mode the generator is consumed ONCE per call, by that ``nn.Dropout`` on ``o`` [B, n_v d + L n_h].
-    The tower only: no retriever is built on it while its convolutions have no kernel."""
-
-    def __init__(self, fiid, fuid, num_users, num_items, embed_dim, max_seq_len, n_v, n_h, dropout=0.2) -> None:
-        super().__init__()
-        self.fiid = fiid
-        self.fuid = fuid
-        self.max_seq_len = max_seq_len
-        self.user_embedding = torch.nn.Embedding(num_users, embed_dim, 0)
-        self.item_embedding = torch.nn.Embedding(num_items, embed_dim, 0)
-        self.dropout = torch.nn.Dropout(p=dropout)
-        self.vertical_filter = torch.nn.Conv2d(in_channels=1, out_channels=n_v, kernel_size=(self.max_seq_len, 1))
-        self.horizontal_filter = torch.nn.ModuleList([
-            torch.nn.Conv2d(in_channels=1, out_channels=n_h, kernel_size=(h, embed_dim)) for h in range(1, max_seq_len + 1)])
-        self.fc = torch.nn.Linear(n_v * embed_dim + n_h * max_seq_len, embed_dim, bias=True)
-
-    def conv_features(self, batch):
-        """``o`` [B, n_v d + L n_h]: what goes into the dropout."""
-        item_seq = batch['in_' + self.fiid]
-        if item_seq.size(1) < self.max_seq_len:
-            item_seq = torch.nn.functional.pad(item_seq, (0, self.max_seq_len - item_seq.size(1)))      # caser.py:39
-            batch = {k: v for k, v in batch.items() if k != '_seg'}
-            batch['in_' + self.fiid] = item_seq
-        rows = _history_rows(self.item_embedding, batch, self.fiid)
-        return caser_conv_torch(rows, *caser_pack(self.vertical_filter, self.horizontal_filter))
-
-    def forward(self, batch):
-        P_u = self.user_embedding(batch[self.fuid])
-        o = self.dropout(self.conv_features(batch))
-        z = torch.relu(self.fc(o))
-        return torch.cat((z, P_u), dim=1)
-
-
-class HGNQueryEncoder(torch.nn.Module):
-    """recstudio/model/seq/hgn.py:16-44, same constructor arguments, same submodules (``user_embedding``, ``W_g_1``, ``W_g_2``,
-    ``b_g``, ``w_g_3``, ``W_g_4`` and the shared ``item_encoder``) and so the same ``state_dict``.  The history rows are gathered
-    through ``_history_rows``; ``ug = W_g_2(U) + b_g`` and ``ui = U @ W_g_4.weight[:L].T`` are torch GEMMs; everything per position
-    -- the feature gate, the instance gate, the pooling and ``S.sum(1)`` -- is ONE launch of ``seqmodule.hgn_gating`` with
-    ``fused_gating`` (a plain attribute, not a parameter), the reference's op sequence ``hgn_gating_torch`` without it or on CPU
-    tensors.  Two facts of the reference: ``b_g`` is ``torch.empty`` there and no initialiser touches a bare ``Parameter``, so it
-    trains from uninitialised memory -- here it starts at ZERO; ``W_g_4.bias`` exists, is saved and loaded, and
-    never receives a gradient.  No dropout: the generator is not consumed."""
-
-    def __init__(self, fuid, fiid, num_users, embed_dim, max_seq_len, item_encoder, pooling_type='mean', fused_gating=True) -> None:
-        super().__init__()
-        self.fuid = fuid
-        self.fiid = fiid
-        self.item_encoder = item_encoder
-        self.pooling_type = pooling_type
-        self.fused_gating = bool(fused_gating)
-        self.user_embedding = torch.nn.Embedding(num_users, embed_dim, 0)
-        self.W_g_1 = torch.nn.Linear(embed_dim, embed_dim, bias=False)
-        self.W_g_2 = torch.nn.Linear(embed_dim, embed_dim, bias=False)
-        self.b_g = torch.nn.Parameter(torch.zeros(embed_dim), requires_grad=True)
-        self.w_g_3 = torch.nn.Linear(embed_dim, 1, bias=False)
-        self.W_g_4 = torch.nn.Linear(embed_dim, max_seq_len)
-
-    def forward(self, batch):
-        if self.pooling_type not in ('mean', 'max'):
-            raise ValueError("`pooling_type` only support `avg` and `max`")                           # hgn.py:42
-        U = self.user_embedding(batch[self.fuid])                                                     # B x D
-        S = _history_rows(self.item_encoder, batch, self.fiid)                                        # B x L x D
-        ug = self.W_g_2(U) + self.b_g
-        ui = U @ self.W_g_4.weight[:S.size(1)].T                                                      # B x L
-        gate = hgn_gating if self.fused_gating else hgn_gating_torch
-        return U + gate(S, ug, ui, self.W_g_1.weight, self.w_g_3.weight.view(-1), self.pooling_type)
-
-
-class HGN(BaseRetriever):
-    """recstudio/model/seq/hgn.py:47-68 with the retriever tail on the fused BPR path."""
-
-    def __init__(self, config=None, **kwargs):
-        # recstudio/model/seq/config/hgn.yaml on top of basemodel.yaml; the caller's config wins
-        user = config or {}
-        super().__init__(config, **kwargs)
-        m = self.config['model']
-        for k, v in (('pooling_type', 'mean'), ('fused_gating', FUSED_GATING_DEFAULT)):
-            m.setdefault(k, v)
-        if 'negative_count' not in user.get('train', {}):
-            self.config['train']['negative_count'] = 1
-
-    def _get_dataset_class():
-        return SeqDataset
-
-    def _get_query_encoder(self, train_data):
-        m = self.config['model']
-        return HGNQueryEncoder(self.fuid, self.fiid, train_data.num_users, self.embed_dim, train_data.config['max_seq_len'],
-                               self.item_encoder, m['pooling_type'], fused_gating=m['fused_gating'])
-
-    def _get_query_feat(self, data):
-        return data if isinstance(data, dict) else super()._get_query_feat(data)
-
-    def _get_score_func(self):
-        return InnerProductScorer()
-
-    def _get_loss_func(self):
-        return BPRLoss()
-
-    def _get_sampler(self, train_data):
-        return UniformSampler(train_data.num_items)
-
-
-class _BagQueryEncoder(torch.nn.Module):
-    """What the two autoencoder towers share (recstudio/model/ae/multidae.py:10-32, multivae.py:10-36): the item table, the
-    dropout and ``h = dropout(item_embedding(ids).sum(1) / count_nonzero(ids, 1) ** 0.5)`` -- one ``seqmodule.bag_pool`` call
-    (``fused_bag``: the kernel pair on the device; off, or on CPU tensors: the reference's op sequence)."""
-
-    def __init__(self, fiid, num_items, embed_dim, dropout_rate, encoder_dims, decoder_dims, fused_bag):
-        super().__init__()
-        assert encoder_dims[-1] == decoder_dims[0], 'expecting the output size of' \
-            'encoder is equal to the input size of decoder.'
-        assert encoder_dims[0] == decoder_dims[-1], 'expecting the output size of' \
-            'decoder is equal to the input size of encoder.'
-        self.fiid = fiid
-        self.fused_bag = fused_bag
-        self.item_embedding = torch.nn.Embedding(num_items, embed_dim, 0)
-        self.dropout = torch.nn.Dropout(p=dropout_rate)
-
-    def pooled(self, batch):
-        return self.dropout(bag_pool(self.item_embedding.weight, batch['in_' + self.fiid], 'rsqrt', fused=self.fused_bag))
-
-
-class MultiDAEQueryEncoder(_BagQueryEncoder):
-    """recstudio/model/ae/multidae.py:9-34, same constructor arguments (plus ``fused_bag``), submodules and ``state_dict`` keys
-    (``item_embedding``, ``encoder_decoder``)."""
-
-    def __init__(self, fiid, num_items, embed_dim, dropout_rate, encoder_dims, decoder_dims, activation='relu',
-                 fused_bag=FUSED_BAG_DEFAULT):
-        super().__init__(fiid, num_items, embed_dim, dropout_rate, encoder_dims, decoder_dims, fused_bag)
-        self.encoder_decoder = torch.nn.Sequential(
-            MLPModule([embed_dim] + encoder_dims + decoder_dims[1:], activation),
-            torch.nn.Linear(decoder_dims[-1], embed_dim))
-
-    def forward(self, batch):
-        return self.encoder_decoder(self.pooled(batch))
-
-
-class MultiVAEQueryEncoder(_BagQueryEncoder):
-    """recstudio/model/ae/multivae.py:9-60, same constructor arguments (plus ``fused_bag``), submodules and ``state_dict`` keys
-    (``item_embedding``, ``encoders``, ``decoders``).  ``kl_loss`` is set by every training-mode forward."""
-
-    def __init__(self, fiid, num_items, embed_dim, dropout_rate, encoder_dims, decoder_dims, activation='relu',
-                 fused_bag=FUSED_BAG_DEFAULT):
-        super().__init__(fiid, num_items, embed_dim, dropout_rate, encoder_dims, decoder_dims, fused_bag)
-        self.encoders = torch.nn.Sequential(
-            MLPModule([embed_dim] + encoder_dims[:-1], activation),
-            torch.nn.Linear(([embed_dim] + encoder_dims[:-1])[-1], encoder_dims[-1] * 2))
-        self.decoders = torch.nn.Sequential(
-            MLPModule(decoder_dims, activation),
-            torch.nn.Linear(decoder_dims[-1], embed_dim))
-        self.kl_loss = 0.0
-
-    def forward(self, batch):
-        encoder_h = self.encoders(self.pooled(batch))
-        mu, logvar = encoder_h.tensor_split(2, dim=-1)
-        z = self.reparameterize(mu, logvar)
-        decoder_z = self.decoders(z)
-        if self.training:
-            self.kl_loss = self.kl_loss_func(mu, logvar)
-        return decoder_z
-
-    def reparameterize(self, mu, logvar):
-        if self.training:
-            std = torch.exp(0.5 * logvar)
-            eps = torch.randn_like(std)
-            return eps.mul(std).add_(mu)
-        return mu
-
-    def kl_loss_func(self, mu, logvar):
-        return -0.5 * torch.mean(torch.sum(1 + logvar - mu.pow(2) - logvar.exp(), dim=1))
-
-
-class MultiDAE(BaseRetriever):
-    """recstudio/model/ae/multidae.py:37-67: one sample per user (``UserDataset``), no sampler, full softmax over the catalog.
-    With ``model.fused_bag`` the training step is ``mean_b(lse_b - <q_b, mean_l item[pos_bl]>)`` -- the reference's second
-    ``SoftmaxLoss`` branch (loss_func.py:39-47) reduced per user -- with the positives' mean one ``bag_pool`` over the item table:
-    no ``[B, L, d]`` gather of the positives, no ``[B, L]`` scores.  ``lse`` comes from ``scorer.full_lse`` (no ``[B, N]`` scores)
-    where the fused full softmax applies (an nn.Embedding catalog up to 128 wide), else from ``torch.logsumexp`` over the
-    scorer's full scores.  With the flag off the step is the stock plugin path over the torch twin."""
-
-    _model_defaults = (('dropout', 0.5), ('encoder_dims', [64, 32]), ('decoder_dims', [32, 64]), ('activation', 'relu'))
-    _train_defaults = (('batch_size', 256), ('learning_rate', 0.01), ('weight_decay', 1e-5))
-
-    def __init__(self, config=None, **kwargs):
-        # recstudio/model/ae/config/multidae.yaml (multivae.yaml) on top of basemodel.yaml; the caller's config wins
-        user = config or {}
-        super().__init__(config, **kwargs)
-        m = self.config['model']
-        if 'embed_dim' not in user.get('model', {}):
-            m['embed_dim'] = self.embed_dim = self._embed_dim_default
-        for k, v in self._model_defaults + (('fused_bag', FUSED_BAG_DEFAULT),):
-            m.setdefault(k, v)
-        for k, v in self._train_defaults + (('device_loader', False),):        # UserDataset batches are assembled on the host
-            if k not in user.get('train', {}):
-                self.config['train'][k] = v
-
-    _embed_dim_default = 200
-
-    def _get_dataset_class():
-        return UserDataset
-
-    def _get_item_encoder(self, train_data):
-        return torch.nn.Embedding(train_data.num_items, self.embed_dim, 0)
-
-    def _get_query_encoder(self, train_data):
-        m = self.config['model']
-        return MultiDAEQueryEncoder(train_data.fiid, train_data.num_items, self.embed_dim, m['dropout'], m['encoder_dims'],
-                                    m['decoder_dims'], m['activation'], fused_bag=m['fused_bag'])
-
-    def _get_query_feat(self, data):
-        return data if isinstance(data, dict) else super()._get_query_feat(data)
-
-    def _get_score_func(self):
-        return InnerProductScorer()
-
-    def _get_sampler(self, train_data):
-        return None
-
-    def _get_loss_func(self):
-        return SoftmaxLoss()
-
-    def _bag_step_ok(self, batch):
-        return (self.config['model'].get('fused_bag', False) and type(self.loss_fn) is SoftmaxLoss and self.sampler is None
-                and type(self.score_func) is InnerProductScorer and isinstance(self.item_encoder, torch.nn.Embedding)
-                and batch[self.fiid].dim() == 2 and batch[self.fiid].is_cuda)
-
-    def _softmax_step(self, batch):
-        if not self._bag_step_ok(batch):
-            return BaseRetriever.training_step(self, batch)
-        query = self.query_encoder(self._get_query_feat(batch))
-        weight = self.item_encoder.weight
-        pos = (bag_pool(weight, batch[self.fiid], 'mean') * query).sum(-1)
-        if weight.shape[1] <= 128 and self.config['train'].get('fused_full_softmax', True):
-            lse = full_lse(query, weight)
-        else:
-            lse = torch.logsumexp(self.score_func(query, self._get_item_vector()), dim=-1)
-        return (lse - pos).mean()
-
-    def training_step(self, batch):
-        return self._softmax_step(batch)
-
-
-class MultiVAE(MultiDAE):
-    """recstudio/model/ae/multivae.py:63-105: MultiDAE's step plus ``anneal * kl_loss``, the weight rising by
-    ``1 / train.anneal_total_step`` per step up to ``train.anneal_max`` (:97-105)."""
-
-    _model_defaults = (('dropout_rate', 0.5), ('encoder_dims', [200]), ('decoder_dims', [200]), ('activation', 'tanh'))
-    _train_defaults = (('batch_size', 500), ('learning_rate', 0.001), ('weight_decay', 1e-5), ('anneal_max', 0.2),
-                       ('anneal_total_step', 2000000), ('early_stop_patience', 100))
-    _embed_dim_default = 600
-
-    def _get_query_encoder(self, train_data):
-        m = self.config['model']
-        return MultiVAEQueryEncoder(train_data.fiid, train_data.num_items, self.embed_dim, m['dropout_rate'], m['encoder_dims'],
-                                    m['decoder_dims'], m['activation'], fused_bag=m['fused_bag'])
-
-    def training_step(self, batch):
-        loss = self._softmax_step(batch)
-        if not hasattr(self, 'anneal'):
-            setattr(self, 'anneal', 0)
-        tr = self.config['train']
-        anneal = min(tr['anneal_max'], self.anneal)
-        self.anneal = min(tr['anneal_max'], self.anneal + (1.0 / tr['anneal_total_step']))
-        return loss + anneal * self.query_encoder.kl_loss
+# The model families live in their own modules, which import BaseRetriever from here; their names keep resolving from this one.
+from .models_graph import LightGCN, NGCF, SGL, SimGCL                                                    # noqa: E402, F401
+from .models_seq import (CL4SRec, CaserQueryEncoder, GRU4Rec, GRU4RecQueryEncoder, HGN, HGNQueryEncoder, NARM,   # noqa: E402, F401
+                         NARMQueryEncoder, SASRec, SASRecQueryEncoder, STAMP, STAMPQueryEncoder, FUSED_ATTENTION_POOL_DEFAULT,
+                         FUSED_GATING_DEFAULT, FUSED_INFONCE_DEFAULT)
+from .models_ae import MultiDAE, MultiDAEQueryEncoder, MultiVAE, MultiVAEQueryEncoder, FUSED_BAG_DEFAULT   # noqa: E402, F401

@@ -451,7 +451,7 @@ def test_config2_sasrec_d128_L50_ssm_n256_training_step(ra, golden):
     rel_close(l2.detach().cpu(), loss.detach().cpu(), rtol=1e-6)
     rel_close(grads[0].cpu(), grads[1].cpu(), rtol=1e-5, atol=1e-6 * scale)         # (the stock Transformer's backward sits in between)
     rel_close(grads[0].cpu(), gi, rtol=1e-4, atol=1e-5 * scale)
-    from recstudio_amd.retriever import _embedding_grad
+    from recstudio_amd.gather import _embedding_grad
     gseq = torch.randn(*db['in_item_id'].shape, 128, device=DEV)
     ga, gb = (_embedding_grad(gseq, db['in_item_id'], model.item_encoder.weight.shape[0]) for _ in range(2))
     assert torch.equal(ga, gb) and not ga[0].any()                                  # the gather's own backward: bit-reproducible

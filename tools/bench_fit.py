@@ -185,7 +185,7 @@ def fit_c3(ra, dev, n_users=40_000, n_items=1_000_001, B=8192, n=256, d=128, L=5
     """configs[2] through ``fit`` (the reference's loop: recommender.py:560-650; the tower: model/seq/sasrec.py:37-67) and the
     split of one step.  The pieces are timed one by one on ONE batch of the epoch's loader, each alone on the stream (their sum
     is close to, not equal to, the step: the loop also pays the loader and the host side)."""
-    from recstudio_amd.retriever import _embedding_grad
+    from recstudio_amd.gather import _embedding_grad
     ds = synthetic_seq_dataset(ra, dev, n_users, n_items, max_seq_len=L)
     conf = {'model': {'embed_dim': d}, 'train': {'negative_count': n, 'batch_size': B, 'epochs': epochs, 'learning_rate': 1e-3,
                                                  'early_stop_patience': 10 ** 6}}
