@@ -995,6 +995,61 @@ int64_t rsa_bi_combine_workspace_bytes(int64_t n_rows, int32_t d_in, int32_t d_o
 int rsa_bi_combine(const rsa_bi_combine_args* args, rsa_stream_t stream);
 int rsa_bi_combine_backward(const rsa_bi_combine_args* args, rsa_stream_t stream);
 
+/* NCF's pair scorers, fused (recstudio/model/scorer.py:37-56 MLPScorer, :92-113 FusionMFMLPScorer over MLPModule): one score per
+ * (query b, slot) pair, the item row gathered by id.  Pair m = b * n_slots + slot, id = ids[m] (ids given) or c0 + slot (ids
+ * null: RANGE mode, the evaluation walk over [c0, c0 + n_slots)), u = query[b], x = table[id]:
+ *   in = [u | x] * keep0 / q;  h1 = relu(W1 in + b1);  h2 = relu(W2 (h1 * keep1 / q) + b2)        (h2 == 0: one hidden layer)
+ *   mode 0 (fusion): s = relu(w_mf . (u * x) + w_h . h_K)       mode 1 (mlp): s = relu(w_h . (h_K * keep_K / q) + b_out)
+ * W1 fp32 [h1, 2 d], W2 fp32 [h2, h1] (nn.Linear); d, h1, h2 in {32, 64, 128} with the padded matrices in the 160 KB of LDS.
+ * mask_slot0 != 0: a pair of slot 0 whose id is 0 scores -inf and passes no gradient.  An id outside the table is clamped into it.
+ * THE DROPOUT.  q = (float)(1.0 - p); element (m, c) is kept iff u[m * C + c] < q and then divided by q, u = element elem_base +
+ * m * C + c of ONE torch.rand([M, C]) call ("Philox state"); C = the masked columns in layer order: 2 d, then h1 when a layer
+ * follows it or mode is 1, then h2 when mode is 1.  p == 0 draws nothing.  Not the stream nn.Dropout's kernel consumes.
+ * rsa_pair_mlp_backward takes the same inputs and state and g (the gradient of the scores, [M]); it recomputes every layer and the
+ * mask and writes dq [n_query, d] (the slots of a query added in ascending order), drows [M, d] (the gradient of each pair's item
+ * row, whatever its id: the row scatter that follows drops the padding row) and dparams: dW1 [h1, 2 d], dW2 [h2, h1], db1 [h1], db2 [h2], dw_h [h_K], then dw_mf [d] (mode 0) or
+ * db_out [1] (mode 1), contiguous in this order.  Sums over pairs are per-wave partials in `workspace` added in a fixed order: no
+ * float atomics, two runs are bit-equal.  Four launches.
+ * Bad widths / mode / p / Philox state / range, null or misaligned pointers (query, table, w1, w2, dq, drows: 16 bytes), a
+ * workspace that is too small: RSA_ERR_ARG before the first HIP call.  No pairs: the forward returns 0 and launches nothing. */
+typedef struct rsa_pair_mlp_args {
+  int64_t size;                /* sizeof(rsa_pair_mlp_args) */
+  const float* query;          /* [n_query, d] */
+  const float* table;          /* [n_items, d], read in place */
+  const int64_t* ids;          /* [n_query, n_slots], or null: RANGE mode */
+  int64_t n_query;
+  int64_t n_slots;
+  int64_t n_items;
+  int64_t c0;                  /* RANGE mode: id of slot 0 */
+  int32_t d;
+  int32_t h1;
+  int32_t h2;                  /* 0: one hidden layer */
+  int32_t mode;                /* 0 fusion, 1 mlp */
+  int32_t mask_slot0;
+  uint32_t grid_threads;       /* "Philox state" of the torch.rand([M, C]) call the dropout stands for (p != 0) */
+  const float* w1;
+  const float* b1;
+  const float* w2;             /* null when h2 == 0 */
+  const float* b2;
+  const float* w_mf;           /* mode 0: [d] */
+  const float* w_h;            /* [h_K] */
+  const float* b_out;          /* mode 1: [1] */
+  double p;                    /* dropout probability in [0, 1) */
+  uint64_t seed;
+  uint64_t offset;
+  uint64_t elem_base;
+  float* scores;               /* forward: [M] out */
+  const float* g;              /* backward: [M] */
+  float* dq;                   /* backward: [n_query, d] out */
+  float* drows;                /* backward: [M, d] out */
+  float* dparams;              /* backward: out, layout above */
+  void* workspace;             /* backward */
+  int64_t workspace_bytes;     /* >= rsa_pair_mlp_workspace_bytes(M, d, h1, h2) */
+} rsa_pair_mlp_args;
+int64_t rsa_pair_mlp_workspace_bytes(int64_t n_pairs, int32_t d, int32_t h1, int32_t h2);
+int rsa_pair_mlp(const rsa_pair_mlp_args* args, rsa_stream_t stream);
+int rsa_pair_mlp_backward(const rsa_pair_mlp_args* args, rsa_stream_t stream);
+
 /* The attention core of the sequence towers, fused: what nn.MultiheadAttention computes between in_proj and out_proj as the
  * reference's nn.TransformerEncoder calls it (recstudio/model/seq/sasrec.py:25-36, :60-63).  qkv fp32 [n_seq, seq_len, 3 D],
  * D = n_head * head_dim, exactly what F.linear(x, in_proj_weight, in_proj_bias) returns: columns [0, D) are q, [D, 2 D) k,

@@ -11,12 +11,13 @@ from .sampler import (Sampler, UniformSampler, MaskedUniformSampler, PopularSamp
                       RetrieverSampler, MIDXSamplerUniform, ClusterSamplerUniform,
                       MIDXSamplerPop, ClusterSamplerPop, LSHSampler)
 from .scorer import InnerProductScorer, CosineScorer, EuclideanScorer, NormScorer, GMFScorer   # noqa: F401
+from .scorer import MLPScorer, FusionMFMLPScorer, pair_mlp_torch   # noqa: F401
 from .loss_func import (FullScoreLoss, PairwiseLoss, PointwiseLoss, BPRLoss,   # noqa: F401
                         SampledSoftmaxLoss, SoftmaxLoss, BinaryCrossEntropyLoss, WeightedBPRLoss,
                         WeightedBinaryCrossEntropyLoss, HingeLoss, NCELoss, CCLLoss, InfoNCELoss)
 from .fused import retriever_scores                               # noqa: F401
 from .dataset import TripletDataset, SeqDataset, UserDataset, DataSampler, SortedDataSampler   # noqa: F401
-from .retriever import (BaseRetriever, TwoTowerRecommender, ItemTowerRecommender, BPR, SASRec, LightGCN,   # noqa: F401
+from .retriever import (BaseRetriever, TwoTowerRecommender, ItemTowerRecommender, BPR, NCF, SASRec, LightGCN,   # noqa: F401
                         SGL, SimGCL, NGCF, CL4SRec, GRU4Rec, NARM, STAMP, HGN, HGNQueryEncoder, MultiDAE, MultiVAE, MultiDAEQueryEncoder,
                         MultiVAEQueryEncoder, default_config, seed_everything)
 from . import graphmodule                                         # noqa: F401

@@ -289,6 +289,18 @@ class BiCombineArgs(_Sized):
     ]
 
 
+class PairMlpArgs(_Sized):
+    """struct rsa_pair_mlp_args."""
+    _fields_ = [
+        ('size', c_int64), ('query', c_void_p), ('table', c_void_p), ('ids', c_void_p), ('n_query', c_int64),
+        ('n_slots', c_int64), ('n_items', c_int64), ('c0', c_int64), ('d', c_int32), ('h1', c_int32), ('h2', c_int32),
+        ('mode', c_int32), ('mask_slot0', c_int32), ('grid_threads', c_uint32), ('w1', c_void_p), ('b1', c_void_p),
+        ('w2', c_void_p), ('b2', c_void_p), ('w_mf', c_void_p), ('w_h', c_void_p), ('b_out', c_void_p), ('p', c_double),
+        ('seed', c_uint64), ('offset', c_uint64), ('elem_base', c_uint64), ('scores', c_void_p), ('g', c_void_p),
+        ('dq', c_void_p), ('drows', c_void_p), ('dparams', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
 class AttentionArgs(_Sized):
     """struct rsa_attention_args."""
     _fields_ = [
@@ -366,7 +378,7 @@ STRUCTS = {
     'rsa_fullscore_args': FullscoreArgs, 'rsa_fullscore_plan_info': FullscorePlanInfo, 'rsa_midx_args': MidxArgs, 'rsa_kmeans_args': KmeansArgs,
     'rsa_midx_weights_args': MidxWeightsArgs, 'rsa_lsh_hash_args': LshHashArgs, 'rsa_lsh_args': LshArgs,
     'rsa_softmax_sample_args': SoftmaxSampleArgs, 'rsa_spmm_args': SpmmArgs,
-    'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs,
+    'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs, 'rsa_pair_mlp_args': PairMlpArgs,
     'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs, 'rsa_ff_attention_args': FfAttentionArgs,
     'rsa_hgn_gating_args': HgnGatingArgs, 'rsa_seq_augment_args': SeqAugmentArgs,
     'rsa_batch_infonce_args': BatchInfoNceArgs, 'rsa_bag_args': BagArgs,
@@ -461,6 +473,9 @@ SIGNATURES = {
     'rsa_bi_combine_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32]),
     'rsa_bi_combine': (c_int, [POINTER(BiCombineArgs), c_void_p]),
     'rsa_bi_combine_backward': (c_int, [POINTER(BiCombineArgs), c_void_p]),
+    'rsa_pair_mlp_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    'rsa_pair_mlp': (c_int, [POINTER(PairMlpArgs), c_void_p]),
+    'rsa_pair_mlp_backward': (c_int, [POINTER(PairMlpArgs), c_void_p]),
     'rsa_attention': (c_int, [POINTER(AttentionArgs), c_void_p]),
     'rsa_attention_backward': (c_int, [POINTER(AttentionArgs), c_void_p]),
     'rsa_gru': (c_int, [POINTER(GruArgs), c_void_p]),

@@ -1643,6 +1643,149 @@ def bi_combine_backward(x, m, w1, w2, b1, b2, *, g_h=None, g_out=None, col=0, ne
     return dx, dm, dw[0], dw[1], db[0], db[1]
 
 
+# ------------------------------------------------------------------ NCF's pair scorers (MLPScorer, FusionMFMLPScorer)
+PAIR_MLP_WIDTHS = (32, 64, 128)        # d and every hidden width (rsa_pairmlp.hip, "WEIGHTS IN LDS")
+PAIR_MLP_LDS_BYTES = 160 << 10
+
+
+def pair_mlp_lds_bytes(d, hidden):
+    """LDS bytes of the padded weights of a pair scorer over ``d``-wide embeddings with the hidden widths ``hidden``."""
+    h1, h2 = hidden[0], (hidden[1] if len(hidden) > 1 else 0)
+    return 4 * (h1 * (2 * d + 4) + h2 * (h1 + 4) + h1 + h2 + d + (h2 or h1) + 4)
+
+
+def pair_mlp_masked_columns(d, hidden, mode):
+    """C of the dropout's ``torch.rand([M, C])``: the 2d input columns, every hidden layer another layer reads, and in 'mlp' mode
+    the last one too."""
+    return 2 * d + sum(hidden[:-1]) + (hidden[-1] if mode == 'mlp' else 0)
+
+
+def pair_mlp_kernel_ok(query, table, hidden, activation='relu'):
+    """Whether ``pair_mlp`` serves these tensors: fp32 on the GPU, relu, one or two hidden layers, d and the hidden widths in
+    32 / 64 / 128 with the padded weights inside the 160 KB of LDS (d = 64, [128, 64]: 102 KB)."""
+    if not (isinstance(query, torch.Tensor) and isinstance(table, torch.Tensor) and query.is_cuda and table.is_cuda):
+        return False
+    if query.dtype != torch.float32 or table.dtype != torch.float32 or table.dim() != 2 or query.shape[-1] != table.shape[1]:
+        return False
+    hidden = list(hidden)
+    if str(activation).lower() != 'relu' or len(hidden) not in (1, 2):
+        return False
+    if table.shape[1] not in PAIR_MLP_WIDTHS or any(h not in PAIR_MLP_WIDTHS for h in hidden):
+        return False
+    return pair_mlp_lds_bytes(table.shape[1], hidden) <= PAIR_MLP_LDS_BYTES
+
+
+def _pair_mlp_args(who, query, table, ids, item_range, w1, b1, w2, b2, w_h, w_mf, b_out, p, philox, mask_slot0):
+    """Every check of the pair scorer's arguments (before any HIP call), then the argument block."""
+    for name, t in (('query', query), ('table', table), ('w1', w1), ('b1', b1), ('w_h', w_h)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{who}: {name} must be a tensor, got {type(t)}')
+    if query.dim() != 2 or table.dim() != 2 or query.shape[1] != table.shape[1]:
+        raise ValueError(f'{who}: query [B, d] and table [N, d] must share d, got {tuple(query.shape)} and {tuple(table.shape)}')
+    (B, d), N = query.shape, table.shape[0]
+    if (w_mf is None) == (b_out is None):
+        raise ValueError(f'{who}: give w_mf (fusion scorer) or b_out (mlp scorer), not both or neither')
+    mode = 'fusion' if w_mf is not None else 'mlp'
+    if w1.dim() != 2 or w1.shape[1] != 2 * d or tuple(b1.shape) != (w1.shape[0],):
+        raise ValueError(f'{who}: w1 must be [H1, {2 * d}] with b1 [H1], got {tuple(w1.shape)} and {tuple(b1.shape)}')
+    hidden = [w1.shape[0]]
+    if (w2 is None) != (b2 is None):
+        raise ValueError(f'{who}: w2 and b2 come together')
+    if w2 is not None:
+        if w2.dim() != 2 or w2.shape[1] != hidden[0] or tuple(b2.shape) != (w2.shape[0],):
+            raise ValueError(f'{who}: w2 must be [H2, {hidden[0]}] with b2 [H2], got {tuple(w2.shape)} and {tuple(b2.shape)}')
+        hidden.append(w2.shape[0])
+    if d not in PAIR_MLP_WIDTHS or any(h not in PAIR_MLP_WIDTHS for h in hidden):
+        raise ValueError(f'{who}: d and the hidden widths must be in {PAIR_MLP_WIDTHS}, got d = {d}, hidden = {hidden}')
+    if pair_mlp_lds_bytes(d, hidden) > PAIR_MLP_LDS_BYTES:
+        raise ValueError(f'{who}: d = {d}, hidden = {hidden}: the padded weights need {pair_mlp_lds_bytes(d, hidden)} bytes of LDS, '
+                         f'{PAIR_MLP_LDS_BYTES} are there')
+    if w_h.numel() != hidden[-1] or (w_mf is not None and w_mf.numel() != d) or (b_out is not None and b_out.numel() != 1):
+        raise ValueError(f'{who}: w_h must hold {hidden[-1]} weights, w_mf {d}, b_out 1')
+    if (ids is None) == (item_range is None):
+        raise ValueError(f'{who}: give ids [B, S] or item_range (c0, count), not both or neither')
+    if ids is not None:
+        if ids.dim() != 2 or ids.shape[0] != B or ids.dtype != torch.int64:
+            raise ValueError(f'{who}: ids must be int64 [{B}, S], got {ids.dtype} {tuple(ids.shape)}')
+        S, c0 = ids.shape[1], 0
+    else:
+        c0, S = int(item_range[0]), int(item_range[1])
+        if c0 < 0 or S < 0 or c0 + S > N:
+            raise ValueError(f'{who}: item_range [{c0}, {c0 + S}) leaves the table of {N} rows')
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'{who}: the dropout probability must lie in [0, 1), got {p}')
+    if p != 0.0 and not isinstance(philox, rng.PhiloxCall):
+        raise TypeError(f'{who}: dropout needs philox, a rng.PhiloxCall (rng.reserve(M * C, 4, device), C = pair_mlp_masked_columns)')
+    if p == 0.0 and philox is not None:
+        raise ValueError(f'{who}: philox without dropout (p = 0 draws nothing)')
+    query, table = _need(query, torch.float32, 'query'), _need(table, torch.float32, 'table')
+    keep = [query, table] + [None if t is None else _need(t, torch.float32, n) for n, t in
+                             (('w1', w1), ('b1', b1), ('w2', w2), ('b2', b2), ('w_mf', w_mf), ('w_h', w_h), ('b_out', b_out))]
+    ids = _need_opt(ids, torch.int64, 'ids')
+    a = nat.PairMlpArgs()
+    a.query, a.table, a.ids = ptr(query), ptr(table), ptr(ids)
+    a.n_query, a.n_slots, a.n_items, a.c0 = B, S, N, c0
+    a.d, a.h1, a.h2, a.mode, a.mask_slot0 = d, hidden[0], hidden[1] if len(hidden) > 1 else 0, int(mode == 'mlp'), int(bool(mask_slot0))
+    a.w1, a.b1, a.w2, a.b2, a.w_mf, a.w_h, a.b_out = (ptr(t) for t in keep[2:])
+    a.p = p
+    if p != 0.0:
+        a.seed, a.offset, a.grid_threads, a.elem_base = philox.seed, philox.offset, philox.grid_threads, philox.elem_base
+    return a, keep + [ids], (B, S, d, hidden, mode)
+
+
+@_on_device
+def pair_mlp(query, table, ids, w1, b1, w2, b2, w_h, *, w_mf=None, b_out=None, p=0.0, philox=None, mask_slot0=False,
+             item_range=None):
+    """rsa_pair_mlp: NCF's pair scorers in one launch.  ``query`` fp32 [B, d]; ``table`` fp32 [N, d], read in place; ``ids`` int64
+    [B, S] -- or None with ``item_range = (c0, S)``: the ids of every query are c0 .. c0 + S - 1.  ``w1`` [H1, 2d], ``b1``, optional
+    ``w2`` [H2, H1], ``b2`` (``nn.Linear`` layout); ``w_h`` the H_K output weights.  With ``w_mf`` [d] the FusionMFMLPScorer
+    ``relu(w_mf . (u * x) + w_h . h_K)``, with ``b_out`` the MLPScorer ``relu(w_h . drop(h_K) + b_out)``.  -> scores fp32 [B, S].
+    ``mask_slot0``: a pair of column 0 whose id is 0 scores -inf.  Dropout ``p``: element (m, c) of the masked columns (the input's
+    2d, then the hidden layers that are dropped, ``pair_mlp_masked_columns``) is kept iff ``u[m, c] < fp32(1 - p)`` and divided by
+    it, ``u = torch.rand(B * S, C)`` in the generator state ``philox`` was reserved in.  ``p == 0`` takes no ``philox``."""
+    a, keep, (B, S, d, hidden, mode) = _pair_mlp_args('pair_mlp', query, table, ids, item_range, w1, b1, w2, b2, w_h, w_mf, b_out,
+                                                      p, philox, mask_slot0)
+    scores = torch.empty(B, S, dtype=torch.float32, device=keep[0].device)
+    a.scores = ptr(scores)
+    _launch('rsa_pair_mlp', ctypes.byref(a))
+    return scores
+
+
+@_on_device
+def pair_mlp_backward(query, table, ids, w1, b1, w2, b2, w_h, g, *, w_mf=None, b_out=None, p=0.0, philox=None, mask_slot0=False,
+                      item_range=None):
+    """rsa_pair_mlp_backward: the gradients of ``pair_mlp`` from ``g`` (fp32 [B, S], the gradient of the scores).  Every layer is
+    recomputed and the mask regenerated from ``philox`` (the state the forward was given).  -> ``(dq [B, d], drows [B, S, d],
+    grads)``: ``drows`` is the gradient of each pair's item row (whatever its id: the row scatter drops the padding row), ``grads`` a dict with ``w1, b1, (w2, b2,)
+    w_h`` and ``w_mf`` or ``b_out``.  No float atomics; bit-equal from run to run.  (How ``drows`` then reaches a table is the caller's:
+    ``scorer._PairMlpFn``.)"""
+    a, keep, (B, S, d, hidden, mode) = _pair_mlp_args('pair_mlp_backward', query, table, ids, item_range, w1, b1, w2, b2, w_h, w_mf,
+                                                      b_out, p, philox, mask_slot0)
+    if not isinstance(g, torch.Tensor) or tuple(g.shape) != (B, S):
+        raise ValueError(f'pair_mlp_backward: g must be [{B}, {S}]')
+    g = _need(g, torch.float32, 'g')
+    dev = keep[0].device
+    h1, h2 = hidden[0], hidden[1] if len(hidden) > 1 else 0
+    sizes = [('w1', (h1, 2 * d)), ('w2', (h2, h1)), ('b1', (h1,)), ('b2', (h2,)), ('w_h', (hidden[-1],)),
+             ('w_mf', (d,)) if mode == 'fusion' else ('b_out', (1,))]
+    total = sum(math.prod(s) for _, s in sizes)
+    alloc = torch.empty if B * S > 0 else torch.zeros            # (the kernels write every element when there is a pair)
+    dq, drows = alloc(B, d, dtype=torch.float32, device=dev), alloc(B, S, d, dtype=torch.float32, device=dev)
+    flat = alloc(total, dtype=torch.float32, device=dev)
+    if B * S > 0:
+        ws, a.workspace_bytes = _workspace(dev, 'rsa_pair_mlp_workspace_bytes', B * S, d, h1, h2)
+        a.workspace, a.g, a.dq, a.drows, a.dparams = ptr(ws), ptr(g), ptr(dq), ptr(drows), ptr(flat)
+        _launch('rsa_pair_mlp_backward', ctypes.byref(a))
+    grads, at = {}, 0
+    for name, shape in sizes:
+        n = math.prod(shape)
+        if n:
+            grads[name] = flat[at:at + n].view(shape)
+        at += n
+    return dq, drows, grads
+
+
 # ------------------------------------------------------------------ the attention core of the sequence towers
 SEQ_ATTENTION_MAX_LEN = 64             # one tile holds the sequence (rsa_attention.hip, "TILE")
 SEQ_ATTENTION_HEAD_DIMS = (16, 32, 64)

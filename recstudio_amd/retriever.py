@@ -28,7 +28,7 @@ from .dataset import SeqDataset, TripletDataset
 from .fused import BPRAdagradStep, BPRAdamStep, BPRSGDStep, fused_bpr_loss, fused_ssm_loss, retriever_scores
 from .loss_func import BPRLoss, FullScoreLoss, PairwiseLoss, PointwiseLoss, SampledSoftmaxLoss, SoftmaxLoss
 from .sampler import PopularSamplerModel, Sampler, UniformSampler
-from .scorer import CosineScorer, EuclideanScorer, InnerProductScorer, full_lse
+from .scorer import CosineScorer, EuclideanScorer, FusionMFMLPScorer, InnerProductScorer, MLPScorer, full_lse
 
 __all__ = ['BaseRetriever', 'TwoTowerRecommender', 'ItemTowerRecommender', 'BPR', 'SASRec', 'CL4SRec', 'GRU4Rec', 'NARM', 'STAMP', 'HGN', 'MultiDAE', 'MultiVAE', 'LightGCN', 'SGL',
            'SimGCL', 'default_config', 'seed_everything']
@@ -418,6 +418,10 @@ class BaseRetriever(torch.nn.Module):
                     sparse_grad=self.config['train'].get('sparse_grad', False))
                 pos_score = score['pos_score'].view(pos_items.shape)
                 neg_score = score['neg_score'].view(*pos_items.shape, n)
+            elif (pair := self._pair_scores(query, pos_items, neg_item_idx, return_neg_item)) is not None:
+                # MLPScorer / FusionMFMLPScorer over an nn.Embedding catalog: the positive's and the negatives' ids go to the pair
+                # kernel as given ids [M, 1 + n] -- no [B, n, d] tensor, no [B, n, 2d] concatenation, one mask call
+                pos_score, neg_score = pair
             else:
                 pos_item_vec = self.item_encoder(pos_items)
                 pos_score = self.score_func(query, pos_item_vec)
@@ -445,6 +449,44 @@ class BaseRetriever(torch.nn.Module):
         if return_item:
             output['item'] = pos_item_vec if pos_item_vec is not None else self.item_encoder(pos_items)
         return output
+
+    def _pair_scores(self, query, pos_items, neg_ids, return_neg_item):
+        """(pos_score, neg_score) of a pair scorer through ``score_ids``; None when that path does not serve this step (another
+        scorer or item tower, one query for several positives, the kernel off or not covering the tensors)."""
+        if not (isinstance(self.score_func, (MLPScorer, FusionMFMLPScorer)) and self.score_func.fused
+                and isinstance(self.item_encoder, torch.nn.Embedding) and len(self.item_fields) == 1 and isinstance(pos_items, torch.Tensor) and isinstance(neg_ids, torch.Tensor)
+                and neg_ids.shape[:-1] == pos_items.shape and query.shape[:-1] == pos_items.shape and not return_neg_item
+                and query.is_cuda):
+            return None
+        n = neg_ids.shape[-1]
+        ids = torch.cat([pos_items.reshape(-1, 1), neg_ids.reshape(-1, n)], dim=1)
+        s = self.score_func.score_ids(query.reshape(-1, query.shape[-1]), self.item_encoder.weight, ids,
+                                      mask_slot0=pos_items.dim() > 1, sparse_grad=self.config['train'].get('sparse_grad', False))
+        if s is None:
+            return None
+        return s[:, 0].reshape(pos_items.shape), s[:, 1:].reshape(*pos_items.shape, n)
+
+    def _topk_pair_scorer(self, query, k, user_h, chunk=None):
+        """``topk`` of a pair scorer: the catalog in chunks through the kernel's range mode, a running ``torch.topk`` merge, peak
+        memory [B, chunk] scores; then the history exclusion of the existing path."""
+        table = self.item_encoder.weight.detach()
+        n_items = table.shape[0]
+        more = user_h.size(1) if user_h is not None else 0
+        kc = min(k + more, n_items - 1)
+        chunk = int(chunk or self.config['eval'].get('pair_chunk', 8192))
+        q = query.detach().contiguous()
+        best_s = best_i = None
+        for c0 in range(1, n_items, chunk):                       # (row 0 is the padding row)
+            c = min(chunk, n_items - c0)
+            s = self.score_func.score_range(q, table, c0, c)
+            i = torch.arange(c0, c0 + c, device=s.device).expand_as(s)
+            if best_s is not None:
+                s, i = torch.cat([best_s, s], dim=1), torch.cat([best_i, i], dim=1)
+            best_s, pick = torch.topk(s, min(kc, s.shape[1]), dim=1)
+            best_i = torch.gather(i, 1, pick)
+        if user_h is not None:
+            best_s, best_i = ops.topk_mask_history(best_s.contiguous(), best_i.contiguous(), user_h, min(k, best_s.shape[1]))
+        return best_s, best_i
 
     def _sample(self, batch, neg: int = 1, excluding_hist: bool = False, return_query: bool = True):
         query = self.query_encoder(self._get_query_feat(batch))
@@ -574,6 +616,11 @@ class BaseRetriever(torch.nn.Module):
             return self._topk_sharded(query, k, user_h, return_query)
         more = user_h.size(1) if user_h is not None else 0
         n_items = self._fullscore_catalog()
+        if (isinstance(self.score_func, (MLPScorer, FusionMFMLPScorer)) and isinstance(self.item_encoder, torch.nn.Embedding)
+                and not self.score_func.training and query.dim() == 2
+                and self.score_func._kernel_parts(query, self.item_encoder.weight) is not None):
+            score, topk_items = self._topk_pair_scorer(query, k, user_h)
+            return (score, topk_items, query) if return_query else (score, topk_items)
         if n_items is not None:
             # the MFMA kernel: scores + exact top-(k + more) without the [B, N] matrix (cosine / Euclidean: the tile
             # epilogue applies the norms, scorer.py:19-34); embed_dim > 128 or k + more > 1024 (a user whose history
@@ -1192,4 +1239,5 @@ from .models_graph import LightGCN, NGCF, SGL, SimGCL                           
 from .models_seq import (CL4SRec, CaserQueryEncoder, GRU4Rec, GRU4RecQueryEncoder, HGN, HGNQueryEncoder, NARM,   # noqa: E402, F401
                          NARMQueryEncoder, SASRec, SASRecQueryEncoder, STAMP, STAMPQueryEncoder, FUSED_ATTENTION_POOL_DEFAULT,
                          FUSED_GATING_DEFAULT, FUSED_INFONCE_DEFAULT)
+from .models_mf import NCF, FUSED_SCORER_DEFAULT                                                        # noqa: E402, F401
 from .models_ae import MultiDAE, MultiDAEQueryEncoder, MultiVAE, MultiVAEQueryEncoder, FUSED_BAG_DEFAULT   # noqa: E402, F401
