@@ -1277,6 +1277,51 @@ int64_t rsa_bag_pool_workspace_bytes(int64_t n_bags, int32_t bag_len, int64_t n_
 int rsa_bag_pool(const rsa_bag_args* args, rsa_stream_t stream);
 int rsa_bag_pool_backward(const rsa_bag_args* args, rsa_stream_t stream);
 
+/* The alternating-least-squares row solve of WRMF (recstudio/model/mf/wrmf.py: padded gather, two bmm, torch.linalg.solve and a
+ * second pass for the loss) without anything of size B Lmax d or B d d in memory.  For every requested row r of a CSR matrix
+ * (indptr int64 [n_csr_rows + 1], indices int32 [nnz], ids in [0, n_table); duplicates count twice; row 0 of the table is a row
+ * like any other), with y_e = table[indices[e]] over the row's edges e:
+ *   A = alpha * sum_e y_e y_e^T + gram + lam * I      b = (1 + alpha) * sum_e rated_e y_e      x = A^-1 b
+ *   loss_r = (1 + alpha) * sum_e (rated_e - <x, y_e>)^2 - sum_e <x, y_e>^2 + x^T gram x          (when loss is given)
+ * table fp32 [n_table, d], d in {32, 64, 128}; gram fp32 [d, d] = table^T table, the caller's; rated fp32 [nnz] or NULL (all
+ * ones); rows int64 [n_solve] (any order, repeats allowed) or NULL = every row, n_solve = n_csr_rows.  Element offsets are 64-bit.
+ * x [n_solve, d] by Cholesky A = R^T R (fp32, in LDS) and two triangular solves; status [n_solve]: 0, k + 1 when pivot k was the
+ * first that is not positive, -1 when the row's parts did not fit max_parts; a row whose status is not 0 writes NaN, nothing
+ * traps.  A row without edges gives x = 0, loss 0.  loss is computed in the direct per-position form by a second pass.
+ * loss_only != 0: nothing is solved; x is READ and loss written (the caller has changed x; status is not touched).
+ * The Gram sums run on the fp32 matrix cores.  A row of more than 1024 edges is cut into parts of 1024, summed by a workgroup each
+ * into `workspace` and added in part order by the workgroup that solves the row: max_parts bounds the parts of ALL rows of the
+ * matrix (2 nnz / 1024 always does; 0 when no row is that long: no workspace is needed then).  No float atomics, no host
+ * synchronisation; a row's bits depend on that row alone, not on the batch it is solved in.
+ * d outside the set, sizes out of range, null pointers, a misaligned table (16 bytes), a workspace that is too small:
+ * RSA_ERR_ARG before the first HIP call.  n_solve == 0 returns 0 and launches nothing.  Nothing is allocated.
+ * Appended without a new RSA_ABI_VERSION. */
+typedef struct rsa_als_args {
+  int64_t size;                /* sizeof(rsa_als_args) */
+  const int64_t* indptr;       /* [n_csr_rows + 1] */
+  const int32_t* indices;      /* [nnz] */
+  const float* rated;          /* [nnz] or NULL */
+  const int64_t* rows;         /* [n_solve] or NULL */
+  const float* table;          /* [n_table, d] */
+  const float* gram;           /* [d, d] */
+  int64_t n_csr_rows;
+  int64_t n_solve;
+  int64_t nnz;
+  int64_t n_table;
+  int64_t max_parts;           /* slots for the parts of rows longer than 1024 edges */
+  int32_t d;
+  int32_t loss_only;
+  float alpha;
+  float lam;
+  float* x;                    /* [n_solve, d]: out (loss_only: in) */
+  float* loss;                 /* [n_solve] out, or NULL */
+  int32_t* status;             /* [n_solve] out */
+  void* workspace;             /* max_parts > 0 */
+  int64_t workspace_bytes;     /* >= rsa_als_workspace_bytes(n_csr_rows, n_solve, max_parts, d) */
+} rsa_als_args;
+int64_t rsa_als_workspace_bytes(int64_t n_csr_rows, int64_t n_solve, int64_t max_parts, int32_t d);
+int rsa_als_solve(const rsa_als_args* args, rsa_stream_t stream);
+
 /* One augmented view of a batch of histories for the contrastive sequence retrievers (CL4SRec: recstudio/model/seq/cl4srec.py;
  * Item_Crop / Item_Mask / Item_Reorder, recstudio/model/module/data_augmentation.py:22-87), one launch.  The random choices are
  * the elements of ONE torch.rand([n_seq, seq_len + 1]) call for the given Philox state: U[b, 0] draws the start, U[b, 1 + p] is

@@ -368,6 +368,17 @@ class BagArgs(_Sized):
     ]
 
 
+class AlsArgs(_Sized):
+    """struct rsa_als_args."""
+    _fields_ = [
+        ('size', c_int64), ('indptr', c_void_p), ('indices', c_void_p), ('rated', c_void_p), ('rows', c_void_p),
+        ('table', c_void_p), ('gram', c_void_p), ('n_csr_rows', c_int64), ('n_solve', c_int64), ('nnz', c_int64),
+        ('n_table', c_int64), ('max_parts', c_int64), ('d', c_int32), ('loss_only', c_int32), ('alpha', c_float),
+        ('lam', c_float), ('x', c_void_p), ('loss', c_void_p), ('status', c_void_p), ('workspace', c_void_p),
+        ('workspace_bytes', c_int64),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -381,7 +392,7 @@ STRUCTS = {
     'rsa_graph_dropout_args': GraphDropoutArgs, 'rsa_bi_combine_args': BiCombineArgs, 'rsa_pair_mlp_args': PairMlpArgs,
     'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs, 'rsa_ff_attention_args': FfAttentionArgs,
     'rsa_hgn_gating_args': HgnGatingArgs, 'rsa_seq_augment_args': SeqAugmentArgs,
-    'rsa_batch_infonce_args': BatchInfoNceArgs, 'rsa_bag_args': BagArgs,
+    'rsa_batch_infonce_args': BatchInfoNceArgs, 'rsa_bag_args': BagArgs, 'rsa_als_args': AlsArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -492,6 +503,8 @@ SIGNATURES = {
     'rsa_bag_pool_workspace_bytes': (c_int64, [c_int64, c_int32, c_int64]),
     'rsa_bag_pool': (c_int, [POINTER(BagArgs), c_void_p]),
     'rsa_bag_pool_backward': (c_int, [POINTER(BagArgs), c_void_p]),
+    'rsa_als_workspace_bytes': (c_int64, [c_int64, c_int64, c_int64, c_int32]),
+    'rsa_als_solve': (c_int, [POINTER(AlsArgs), c_void_p]),
 }
 
 _lib = None

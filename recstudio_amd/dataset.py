@@ -750,6 +750,50 @@ class UserDataset(TripletDataset):
         raise NotImplementedError('UserDataset batches are assembled on the host: use train_loader(..., device=...)')
 
 
+class ALSDataset(TripletDataset):
+    """recstudio/data/advance_dataset.py:7-53: the data of the alternating-least-squares models, ``<u, I_u>`` and, transposed,
+    ``<i, U_i>``.  The reference's ``build`` calls ``_build`` with a signature its base class no longer has; this class is pinned to
+    what its source spells out: the training split is grouped per user (``data_index`` rows ``[user, start, end)``), and
+    ``transpose()`` regroups the same split per item over the TRAIN subset only.  Batches are right-padded with 0.
+    ``csr()`` gives the two CSRs of the train split that the fused path uploads once."""
+
+    def build(self, *args, **kwargs):
+        datasets = super().build(*args, **kwargs)
+        idx = datasets[0].data_index
+        users, counts = torch.unique_consecutive(self.inter_feat[self.fuid][idx], return_counts=True)
+        ends = torch.cumsum(counts, 0)
+        datasets[0].data_index = torch.stack([users, idx[ends - counts], idx[ends - 1] + 1], dim=1)
+        return datasets
+
+    def transpose(self):
+        """The same split seen as ``<i, U_i>``: a copy with the interactions sorted by item, an item's train interactions first,
+        ``data_index`` rows ``[item, start, start + train count)`` and the user / item fields exchanged."""
+        out = copy.copy(self)
+        items, sub = self.inter_feat[self.fiid], self.inter_feat_subset
+        in_train = torch.zeros_like(items, dtype=torch.bool).scatter(0, sub, True)
+        order = torch.sort(items * 2 + (~in_train).long(), stable=True).indices
+        out.inter_feat = {k: v[order] for k, v in self.inter_feat.items()}
+        uniq, total = torch.unique_consecutive(items[order], return_counts=True)
+        train = torch.bincount(items[in_train], minlength=int(items.max()) + 1)[uniq]
+        start = torch.cumsum(total, 0) - total
+        keep = train > 0
+        out.data_index = torch.stack([uniq, start, start + train], dim=1)[keep]
+        out.fuid, out.fiid = self.fiid, self.fuid
+        return out
+
+    def csr(self):
+        """``(user_indptr, user_items, user_ratings), (item_indptr, item_users, item_ratings)`` of this split, from ``get_graph([0])``:
+        indptr int64, ids int32, ratings fp32, every interaction once in each, in stable order."""
+        (rows, cols, _, shape), _ = self.get_graph([0])
+        ratings = self.inter_feat[self.frating][self.inter_feat_subset].float()
+
+        def one(key, val, n):
+            order = torch.sort(key, stable=True).indices
+            indptr = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(torch.bincount(key, minlength=n), 0)])
+            return indptr, val[order].to(torch.int32), ratings[order]
+        return one(rows, cols, shape[0]), one(cols, rows, shape[1])
+
+
 def synthetic_interactions(n_users, n_items, n_inter, alpha=1.0, seed=1):
     """Seeded synthetic interaction stream: users uniform, items Zipf(alpha) over a permuted id space
     (SURVEY.md section 8d).  Returns (user_ids, item_ids) int64 arrays with ids starting at 1."""

@@ -2274,3 +2274,74 @@ def bag_pool_backward(ids, cnt, g, n_rows, scale='sum', out=None):
     a.cnt, a.g, a.dw, a.workspace = ptr(cnt), ptr(g), ptr(out), ptr(ws)
     _launch('rsa_bag_pool_backward', ctypes.byref(a))
     return out
+
+
+# ------------------------------------------------------------------ ALS row solve (WRMF)
+ALS_DIMS = (32, 64, 128)
+ALS_CHUNK = 1024                  # a longer row is cut into parts of this many positions (rsa_als.hip)
+
+
+def als_max_parts(indptr_or_nnz):
+    """Slots for the parts of the long rows of a CSR matrix: the exact count from a HOST ``indptr`` (once per matrix), or the bound
+    ``2 nnz / ALS_CHUNK`` that holds for every matrix of ``nnz`` edges (a row of K > C edges has ceil(K / C) <= 2 K / C parts)."""
+    if isinstance(indptr_or_nnz, torch.Tensor):
+        deg = indptr_or_nnz[1:] - indptr_or_nnz[:-1]
+        return int((torch.div(deg + ALS_CHUNK - 1, ALS_CHUNK, rounding_mode='floor') * (deg > ALS_CHUNK)).sum())
+    return 2 * int(indptr_or_nnz) // ALS_CHUNK
+
+
+@_on_device
+def als_solve(indptr, indices, table, gram, alpha, lam, *, rows=None, rated=None, want_loss=False, x=None, max_parts=None):
+    """rsa_als_solve: one alternating-least-squares half step.  For every requested row r of the CSR matrix (``indptr`` int64
+    [R + 1], ``indices`` int32 [nnz], ids in [0, N), duplicates count twice), with ``y_e = table[indices[e]]`` over its edges:
+    ``A = alpha * sum_e y_e y_e^T + gram + lam * I``, ``b = (1 + alpha) * sum_e rated_e y_e``, ``x = A^-1 b`` (fp32 Cholesky), and with
+    ``want_loss`` ``loss_r = (1 + alpha) sum_e (rated_e - <x, y_e>)^2 - sum_e <x, y_e>^2 + x^T gram x`` in the direct form.
+    ``table`` fp32 [N, d], d in {32, 64, 128}; ``gram`` fp32 [d, d] (``table.T @ table``, the caller's); ``rated`` fp32 [nnz] or None
+    (all ones); ``rows`` int64 [B] (any order, repeats allowed) or None (all R rows).
+    -> ``(x [B, d], loss [B] | None, status int32 [B])``: status 0, k + 1 for a first non-positive pivot k, -1 for a long row whose
+    parts did not fit ``max_parts``; such rows hold NaN.  An empty row gives x = 0.
+    ``x`` given: nothing is solved, the loss of THAT x is returned (``(x, loss, None)``).
+    ``max_parts``: slots for the parts of rows longer than ``ALS_CHUNK``.  PASS IT (``als_max_parts(host indptr)``, once per matrix):
+    None falls back to the bound ``2 nnz / ALS_CHUNK`` and allocates ``(d d + d) 4`` bytes for each of those slots on every call --
+    about 13 GB at nnz = 1e8, d = 128 -- even when no row is that long.  With any ``max_parts > 0`` a one-workgroup scan of all R
+    rows (and of ``rows``) runs in front of the solve.
+    Nothing of size B Lmax d or B d d is allocated; no float atomics, no host synchronisation; two runs are bit-equal and a row's
+    bits do not depend on the other rows of the call."""
+    indptr = _need(indptr, torch.int64, 'indptr')
+    indices = _need(indices, torch.int32, 'indices')
+    table = _need(table, torch.float32, 'table')
+    gram = _need(gram, torch.float32, 'gram')
+    rows = _need_opt(rows, torch.int64, 'rows')
+    rated = _need_opt(rated, torch.float32, 'rated')
+    if table.dim() != 2 or table.shape[1] not in ALS_DIMS:
+        raise ValueError(f'als_solve: table must be [N, d] with d in {ALS_DIMS}, got {tuple(table.shape)}')
+    N, d = table.shape
+    R, nnz = indptr.numel() - 1, indices.numel()
+    if tuple(gram.shape) != (d, d):
+        raise ValueError(f'als_solve: gram must be [{d}, {d}], got {tuple(gram.shape)}')
+    if rated is not None and rated.numel() != nnz:
+        raise ValueError('als_solve: rated must hold one value per edge')
+    B = R if rows is None else rows.numel()
+    dev = table.device
+    loss_only = x is not None
+    if loss_only:
+        x = _need(x, torch.float32, 'x')
+        if tuple(x.shape) != (B, d):
+            raise ValueError(f'als_solve: x must be [{B}, {d}], got {tuple(x.shape)}')
+    else:
+        x = torch.empty(B, d, dtype=torch.float32, device=dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev) if want_loss or loss_only else None
+    status = None if loss_only else torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x, loss, status
+    a = nat.AlsArgs()
+    a.indptr, a.indices, a.rated, a.rows, a.table, a.gram = ptr(indptr), ptr(indices), ptr(rated), ptr(rows), ptr(table), ptr(gram)
+    a.n_csr_rows, a.n_solve, a.nnz, a.n_table, a.d, a.loss_only = R, B, nnz, N, d, int(loss_only)
+    a.alpha, a.lam = float(alpha), float(lam)
+    a.max_parts = 0 if loss_only else (als_max_parts(nnz) if max_parts is None else int(max_parts))
+    ws = None
+    if a.max_parts > 0:
+        ws, a.workspace_bytes = _workspace(dev, 'rsa_als_workspace_bytes', R, B, a.max_parts, d)
+    a.x, a.loss, a.status, a.workspace = ptr(x), ptr(loss), ptr(status), ptr(ws)
+    _launch('rsa_als_solve', ctypes.byref(a))
+    return x, loss, status
