@@ -1322,6 +1322,76 @@ typedef struct rsa_als_args {
 int64_t rsa_als_workspace_bytes(int64_t n_csr_rows, int64_t n_solve, int64_t max_parts, int32_t d);
 int rsa_als_solve(const rsa_als_args* args, rsa_stream_t stream);
 
+/* ItemKNN (recstudio/model/mf/itemknn.py): the knn largest entries of every column of the item-item similarity of R^T R, without the
+ * matrix.  R is the unit-valued, duplicate-free interaction graph, given as its two CSRs: users -> items (u_indptr int64
+ * [n_users + 1], u_items int32 [nnz], ASCENDING within a row) and items -> users (i_indptr int64 [n_items + 1], i_users int32 [nnz]).
+ * For a target item i and every j != i with c = |users(i) & users(j)| > 0, with n_x the length of item x's row:
+ *   RSA_KNN_COSINE    s = c / (sqrt(n_j) * sqrt(n_i) + 1e-6)           RSA_KNN_JACCARD    s = c / ((n_j + n_i - c) + 1e-6)
+ * in fp32 with correctly rounded sqrt and divide.  The column keeps its min(knn, nnz) largest s; among equal s the lower id wins.
+ * nbr_id int32 [n_items, knn], nbr_sim fp32 [n_items, knn], nbr_cnt int32 [n_items]: descending s, then ascending id; unused
+ * slots hold id -1 and sim +0.  ONLY the rows of the items in `order` (int32 [n_order], distinct, the launch order: heaviest
+ * first) are written; the caller fills the others (-1, 0, count 0).
+ * One workgroup owns one (target item, tile) pair: it walks users(i) and each such user's row and counts into `tile` 32-bit LDS
+ * counters with integer atomics (exact, order-free: two runs are bit-equal), computes s per non-zero count, finds the knn-th
+ * largest (s, lower id first) by a radix search over the LDS tile and sorts the winners.  tile: a power of two up to 32768, 0 = the
+ * default 32768 (the largest whose counters fit the LDS of a gfx950 workgroup next to the search's scratch).  n_items > tile: every
+ * tile writes its best candidates to the workspace and a second launch merges an item's tiles under the same order.
+ * max_degree is the caller's statement of the longest item row; it must stay below 2^24 (counts are converted to fp32 exactly).
+ * knn outside 1 .. 1024, tile not a power of two, sizes out of range, null pointers, a workspace that is too small: RSA_ERR_ARG
+ * before the first HIP call.  n_order == 0 returns 0 and launches nothing.  Appended without a new RSA_ABI_VERSION. */
+#define RSA_KNN_COSINE 0
+#define RSA_KNN_JACCARD 1
+#define RSA_KNN_MAX_K 1024
+#define RSA_KNN_MAX_TILE 32768
+typedef struct rsa_knn_build_args {
+  int64_t size;                /* sizeof(rsa_knn_build_args) */
+  const int64_t* u_indptr;     /* [n_users + 1] */
+  const int32_t* u_items;      /* [nnz], ascending within a row */
+  const int64_t* i_indptr;     /* [n_items + 1] */
+  const int32_t* i_users;      /* [nnz] */
+  const int32_t* order;        /* [n_order] target items in launch order */
+  int64_t n_users;
+  int64_t n_items;
+  int64_t nnz;
+  int64_t n_order;
+  int64_t max_degree;          /* the longest item row, < 2^24 */
+  int32_t knn;                 /* 1 .. RSA_KNN_MAX_K */
+  int32_t tile;                /* power of two <= RSA_KNN_MAX_TILE, 0 = default */
+  int32_t similarity;          /* RSA_KNN_COSINE / RSA_KNN_JACCARD */
+  int32_t reserved;
+  int32_t* nbr_id;             /* [n_items, knn] out */
+  float* nbr_sim;              /* [n_items, knn] out */
+  int32_t* nbr_cnt;            /* [n_items] out */
+  void* workspace;             /* n_items > tile */
+  int64_t workspace_bytes;     /* >= rsa_knn_build_workspace_bytes(n_items, n_order, knn, tile) */
+} rsa_knn_build_args;
+int64_t rsa_knn_build_workspace_bytes(int64_t n_items, int64_t n_order, int32_t knn, int32_t tile);
+int rsa_knn_build(const rsa_knn_build_args* args, rsa_stream_t stream);
+
+/* ItemKNN scores: out[b, c] = sum over j in hist(users[b]) of sim(j -> item c + 1), fp32 [n_batch, n_items - 1] (column c is item
+ * c + 1).  hist(u) is row u of the users -> items CSR; the similarities are the TRANSPOSED neighbour lists, a CSR by neighbour j
+ * (t_indptr int64 [n_items + 1], t_items int32 targets ASCENDING within a row, t_sim fp32).  One workgroup owns one (user, tile of
+ * `tile` target items) pair with the fp32 tile in LDS; the history is walked one j at a time in row order (ascending j), the
+ * threads spread over row j's entries inside the tile (distinct targets: plain read-modify-write), a barrier between two j.  No
+ * float atomics: a user's row has the same bits alone, in any batch, with any tile and on any run.  A user without history, or an
+ * id outside [0, n_users), gets zeros.  tile: a power of two up to 32768, 0 = the default 8192.  Nothing is allocated. */
+typedef struct rsa_knn_score_args {
+  int64_t size;                /* sizeof(rsa_knn_score_args) */
+  const int64_t* users;        /* [n_batch] */
+  const int64_t* u_indptr;     /* [n_users + 1] */
+  const int32_t* u_items;
+  const int64_t* t_indptr;     /* [n_items + 1] */
+  const int32_t* t_items;
+  const float* t_sim;
+  int64_t n_batch;
+  int64_t n_users;
+  int64_t n_items;
+  int32_t tile;
+  int32_t reserved;
+  float* out;                  /* [n_batch, n_items - 1] */
+} rsa_knn_score_args;
+int rsa_knn_score(const rsa_knn_score_args* args, rsa_stream_t stream);
+
 /* One augmented view of a batch of histories for the contrastive sequence retrievers (CL4SRec: recstudio/model/seq/cl4srec.py;
  * Item_Crop / Item_Mask / Item_Reorder, recstudio/model/module/data_augmentation.py:22-87), one launch.  The random choices are
  * the elements of ONE torch.rand([n_seq, seq_len + 1]) call for the given Philox state: U[b, 0] draws the start, U[b, 1 + p] is

@@ -379,6 +379,25 @@ class AlsArgs(_Sized):
     ]
 
 
+class KnnBuildArgs(_Sized):
+    """struct rsa_knn_build_args."""
+    _fields_ = [
+        ('size', c_int64), ('u_indptr', c_void_p), ('u_items', c_void_p), ('i_indptr', c_void_p), ('i_users', c_void_p),
+        ('order', c_void_p), ('n_users', c_int64), ('n_items', c_int64), ('nnz', c_int64), ('n_order', c_int64),
+        ('max_degree', c_int64), ('knn', c_int32), ('tile', c_int32), ('similarity', c_int32), ('reserved', c_int32),
+        ('nbr_id', c_void_p), ('nbr_sim', c_void_p), ('nbr_cnt', c_void_p), ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
+class KnnScoreArgs(_Sized):
+    """struct rsa_knn_score_args."""
+    _fields_ = [
+        ('size', c_int64), ('users', c_void_p), ('u_indptr', c_void_p), ('u_items', c_void_p), ('t_indptr', c_void_p),
+        ('t_items', c_void_p), ('t_sim', c_void_p), ('n_batch', c_int64), ('n_users', c_int64), ('n_items', c_int64),
+        ('tile', c_int32), ('reserved', c_int32), ('out', c_void_p),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -393,6 +412,7 @@ STRUCTS = {
     'rsa_attention_args': AttentionArgs, 'rsa_gru_args': GruArgs, 'rsa_ff_attention_args': FfAttentionArgs,
     'rsa_hgn_gating_args': HgnGatingArgs, 'rsa_seq_augment_args': SeqAugmentArgs,
     'rsa_batch_infonce_args': BatchInfoNceArgs, 'rsa_bag_args': BagArgs, 'rsa_als_args': AlsArgs,
+    'rsa_knn_build_args': KnnBuildArgs, 'rsa_knn_score_args': KnnScoreArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -505,6 +525,9 @@ SIGNATURES = {
     'rsa_bag_pool_backward': (c_int, [POINTER(BagArgs), c_void_p]),
     'rsa_als_workspace_bytes': (c_int64, [c_int64, c_int64, c_int64, c_int32]),
     'rsa_als_solve': (c_int, [POINTER(AlsArgs), c_void_p]),
+    'rsa_knn_build_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    'rsa_knn_build': (c_int, [POINTER(KnnBuildArgs), c_void_p]),
+    'rsa_knn_score': (c_int, [POINTER(KnnScoreArgs), c_void_p]),
 }
 
 _lib = None

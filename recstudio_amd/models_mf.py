@@ -1,4 +1,4 @@
-"""The matrix-factorisation family beyond BPR: NCF, WRMF."""
+"""The matrix-factorisation family beyond BPR: NCF, WRMF, ItemKNN."""
 import time
 
 import torch
@@ -12,7 +12,8 @@ from .sampler import UniformSampler
 from .scorer import FusionMFMLPScorer, GMFScorer, InnerProductScorer, MLPScorer
 from .seqmodule import MLPModule
 
-__all__ = ['NCF', 'FUSED_SCORER_DEFAULT', 'WRMF', 'FUSED_ALS_DEFAULT', 'als_step_torch']
+__all__ = ['NCF', 'FUSED_SCORER_DEFAULT', 'WRMF', 'FUSED_ALS_DEFAULT', 'als_step_torch', 'ItemKNN', 'FUSED_KNN_DEFAULT',
+           'itemknn_torch', 'itemknn_score_torch']
 
 # model.fused_scorer: the pair scorers run in rsa_pair_mlp (forward, backward, range-mode top-k) instead of torch ops.  Off:
 # tools/bench_ncf.py (profiles/ncf_bench.json) has the kernel ahead in every forward and behind in every forward + backward.
@@ -178,3 +179,155 @@ class WRMF(BaseRetriever):
             return dict(metrics, valid_time=time.time() - t1)
 
         return self._run_epochs(train_epoch, None, validate if val_data is not None else None, log=self.logger.info)
+
+
+# model.fused_knn: the neighbour build and the scores run in rsa_knn_build / rsa_knn_score instead of itemknn_torch /
+# itemknn_score_torch.  On: tools/bench_itemknn.py (profiles/itemknn_bench.json) at about ml-20m's shape has the build at 10.9 ms
+# against 1856 ms and a top-k batch (B = 512, k = 100) at 1.03 ms against 56.7 ms; at about ml-1m's 0.34 / 2.12 and 0.28 / 11.2 ms.
+FUSED_KNN_DEFAULT = True
+_KNN_BUFFERS = ('nbr_id', 'nbr_sim', 'nbr_cnt', 't_indptr', 't_items', 't_sim', 'user_indptr', 'user_items')
+
+
+def itemknn_torch(users, items, n_users, n_items, knn, similarity, dtype=torch.float32, chunk=2048):
+    """The torch-op twin of ``ops.knn_build`` (recstudio/model/mf/itemknn.py:12-41): the dense ``R^T R`` in column chunks, the same
+    formula in ``dtype``, and the ``min(knn, nnz)`` largest of each column.  ``users`` / ``items``: the interactions, one id pair each,
+    no duplicates.  A stable descending sort stands where the reference has ``argpartition``: it is what decides ties by the lower
+    id.  -> ``(nbr_id int32 [N, knn], nbr_sim dtype [N, knn], nbr_cnt int32 [N])`` as the kernel lays them out."""
+    if similarity not in ops.KNN_SIMILARITIES:
+        raise ValueError('unsupported similarity metric')
+    dev = users.device
+    R = torch.zeros(n_users, n_items, dtype=dtype, device=dev)
+    R[users.long(), items.long()] = 1
+    n = R.sum(0)
+    root = torch.sqrt(n)
+    width = min(int(knn), n_items)
+    nbr_id = torch.full((n_items, knn), -1, dtype=torch.int32, device=dev)
+    nbr_sim = torch.zeros(n_items, knn, dtype=dtype, device=dev)
+    nbr_cnt = torch.zeros(n_items, dtype=torch.int32, device=dev)
+    for s in range(0, n_items, chunk):
+        e = min(s + chunk, n_items)
+        c = R[:, s:e].T @ R                                            # [C, N]: row r is column s + r of the Gram matrix
+        c[torch.arange(e - s, device=dev), torch.arange(s, e, device=dev)] = 0
+        if similarity == 'cosine':
+            sim = c / (root[None] * root[s:e, None] + 1e-6)
+        else:
+            sim = c / (n[None] + n[s:e, None] - c + 1e-6)
+        val, idx = torch.sort(sim, dim=1, descending=True, stable=True)
+        val, idx = val[:, :width], idx[:, :width]
+        live = val > 0
+        nbr_cnt[s:e] = live.sum(1).to(torch.int32)
+        nbr_id[s:e, :width] = torch.where(live, idx, -1).to(torch.int32)
+        nbr_sim[s:e, :width] = val
+    nbr_cnt[0], nbr_id[0], nbr_sim[0] = 0, -1, 0                       # the padding item is nobody's target
+    return nbr_id, nbr_sim, nbr_cnt
+
+
+def itemknn_score_torch(users, indptr, items, t_indptr, t_items, t_sim, n_items):
+    """The torch-op twin of ``ops.knn_score``: every (user, history item j, target of row j) triple is expanded and summed with
+    ``index_put_(accumulate=True)``.  Same values up to the order of the sums."""
+    users = users.long()
+    start, deg = indptr[users], indptr[users + 1] - indptr[users]
+    b = torch.repeat_interleave(torch.arange(users.numel(), device=users.device), deg)
+    pos = torch.arange(b.numel(), device=users.device) - torch.repeat_interleave(torch.cumsum(deg, 0) - deg, deg)
+    j = items[start[b] + pos].long()
+    t_start, t_deg = t_indptr[j], t_indptr[j + 1] - t_indptr[j]
+    bb = torch.repeat_interleave(b, t_deg)
+    at = torch.repeat_interleave(t_start, t_deg) + (torch.arange(bb.numel(), device=users.device)
+                                                    - torch.repeat_interleave(torch.cumsum(t_deg, 0) - t_deg, t_deg))
+    out = torch.zeros(users.numel(), n_items, dtype=t_sim.dtype, device=users.device)
+    out.index_put_((bb, t_items[at].long()), t_sim[at], accumulate=True)
+    return out[:, 1:]
+
+
+class ItemKNN(BaseRetriever):
+    """recstudio/model/mf/itemknn.py, recstudio/model/mf/config/itemknn.yaml (knn 100, similarity cosine | jaccard): the item-based
+    neighbourhood baseline.  There is nothing to learn: ``fit`` builds, once, the ``knn`` most similar items of every item from the
+    co-occurrence counts of the train split, and a user's score of item i is the sum of sim(j -> i) over the user's train items j
+    that are among i's neighbours.  No sampler, loss, optimizer or encoder; the neighbour lists, their transpose and the user-side
+    CSR are buffers, so ``state_dict`` carries the fitted model.  ``model.fused_knn``: ``ops.knn_build`` / ``ops.knn_score``; off,
+    ``itemknn_torch`` / ``itemknn_score_torch``.  Where the reference's ``argpartition`` leaves ties open, the lower item id wins."""
+
+    config_defaults = {'model': {'fused_knn': FUSED_KNN_DEFAULT}, 'train': {'knn': 100, 'similarity': 'cosine', 'epochs': 1}}
+
+    def _get_item_encoder(self, train_data):
+        return None
+
+    def _get_query_encoder(self, train_data):
+        return None
+
+    def _get_loss_func(self):
+        return None
+
+    def _get_sampler(self, train_data):
+        return None
+
+    def _update_item_vector(self):
+        pass                                                              # the "item vector" is the sparse neighbour matrix
+
+    def _knn_build(self, train_data, device):
+        tr = self.config['train']
+        if tr['similarity'] not in ops.KNN_SIMILARITIES:
+            raise ValueError('unsupported similarity metric')
+        if not train_data.drop_dup:
+            raise ValueError('ItemKNN: the interaction graph is unit-valued; drop_dup: False (repeated pairs) is not covered')
+        (users, items, _, (n_users, n_items)), _ = train_data.get_graph([0])
+        users, items = users.to(device), items.to(device)
+
+        def csr(key, val, n):                                            # ids ascending within a row
+            order = torch.sort(key * (int(val.max()) + 1 if val.numel() else 1) + val).indices
+            return torch.cat([key.new_zeros(1), torch.cumsum(torch.bincount(key, minlength=n), 0)]), val[order].to(torch.int32)
+        (u_indptr, u_items), (i_indptr, i_users) = csr(users, items, n_users), csr(items, users, n_items)
+        if self.config['model']['fused_knn']:
+            nbr = ops.knn_build(u_indptr, u_items, i_indptr, i_users, tr['knn'], tr['similarity'])
+        else:
+            nbr = itemknn_torch(users, items, n_users, n_items, tr['knn'], tr['similarity'])
+        for name, t in zip(_KNN_BUFFERS, nbr + ops.knn_transpose(*nbr) + (u_indptr, u_items)):
+            self.register_buffer(name, t)
+
+    def load_state_dict(self, state_dict, strict=True):
+        for name in _KNN_BUFFERS:                                        # a fresh model has no lists yet: take their shapes from the state
+            if name in state_dict:
+                self.register_buffer(name, torch.empty_like(state_dict[name]))
+        return super().load_state_dict(state_dict, strict)
+
+    def topk(self, batch, k, user_h=None, return_query=False):
+        """baseretriever.py:374-397 over the neighbour scores: top (k + |hist|), ids + 1, the history dropped, top k."""
+        users = (batch[self.fuid] if isinstance(batch, dict) else batch).to(self.nbr_cnt.device)
+        n_items = self.nbr_cnt.numel()
+        score_fn = ops.knn_score if self.config['model']['fused_knn'] else itemknn_score_torch
+        scores = score_fn(users, self.user_indptr, self.user_items, self.t_indptr, self.t_items, self.t_sim, n_items)
+        kc = min(k + (user_h.size(1) if user_h is not None else 0), n_items - 1)
+        score, topk_items = ops.row_topk(scores, kc) if kc <= ops.FULLSCORE_MAX_K else torch.topk(scores, kc)
+        topk_items = topk_items + 1
+        if user_h is not None:
+            score, topk_items = ops.topk_mask_history(score, topk_items, user_h, min(k, kc))
+        return (score, topk_items, scores) if return_query else (score, topk_items)
+
+    def fit(self, train_data, val_data=None, run_mode='light', config=None, **kwargs):
+        if config is not None:
+            self.config.update(config)
+        if self._dist_context(kwargs) is not None:
+            raise NotImplementedError('ItemKNN: the sharded fit is not covered (the build needs both CSRs of the whole split on one device)')
+        self._init_model(train_data)
+        device = self._device()
+        self.to(device)
+        if val_data is not None:
+            val_data.use_field = train_data.use_field
+
+        def train_epoch():
+            self._knn_build(train_data, device)
+            return 0.0                                                   # itemknn.py:46
+
+        def validate():
+            t1 = time.time()
+            metrics = self._eval_epoch(val_data, self.validation_step, device)
+            return dict(metrics, valid_time=time.time() - t1)
+
+        return self._run_epochs(train_epoch, None, validate if val_data is not None else None, log=self.logger.info)
+
+    def evaluate(self, test_data, verbose=True, **kwargs):
+        test_data.use_field = self.fields
+        out = self._eval_epoch(test_data, self.test_step, self.nbr_cnt.device)
+        if verbose:
+            self.logger.info(str(out))
+        return out

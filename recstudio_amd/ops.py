@@ -2345,3 +2345,119 @@ def als_solve(indptr, indices, table, gram, alpha, lam, *, rows=None, rated=None
     a.x, a.loss, a.status, a.workspace = ptr(x), ptr(loss), ptr(status), ptr(ws)
     _launch('rsa_als_solve', ctypes.byref(a))
     return x, loss, status
+
+
+# ------------------------------------------------------------------ ItemKNN: neighbour build and scoring
+KNN_MAX_K = 1024
+KNN_MAX_TILE = 32768              # 32-bit counters of one (item, tile) workgroup in LDS (rsa_knn.hip)
+KNN_MAX_DEGREE = 1 << 24          # counts are converted to fp32 exactly below this
+KNN_SIMILARITIES = {'cosine': 0, 'jaccard': 1}
+KNN_WORKSPACE_BYTES = 1 << 30     # a multi-tile catalog is built in parts of the order whose candidates fit this
+
+
+class KnnPlan:
+    """The launch order of ``knn_build`` for one interaction graph (``knn_plan`` builds it, once per fit): ``order`` int32, the
+    items with interactions (never item 0), heaviest first; ``weight`` int64 [N], an item's work sum_{u in users(i)} deg(u);
+    ``max_degree``, the longest item row."""
+
+    def __init__(self, order, weight, max_degree):
+        self.order, self.weight, self.max_degree = order, weight, max_degree
+
+    def heaviest_share(self):
+        """The heaviest item's share of all work: it is ONE workgroup per tile, so this bounds what the schedule can hide."""
+        total = int(self.weight.sum())
+        return float(self.weight.max()) / total if total else 0.0
+
+
+def knn_plan(u_indptr, i_indptr, i_users):
+    """The plan of ``knn_build`` from the two row pointers and the item-side ids (where they live, the plan lives): the role
+    ``spmm_plan`` plays for the propagation kernel.  Refuses an item held by 2^24 users or more."""
+    for name, t in (('u_indptr', u_indptr), ('i_indptr', i_indptr)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 2:
+            raise TypeError(f'knn_plan: {name} must be an int64 tensor [R + 1]')
+    deg_u, deg_i = u_indptr[1:] - u_indptr[:-1], i_indptr[1:] - i_indptr[:-1]
+    max_degree = int(deg_i.max())
+    if max_degree >= KNN_MAX_DEGREE:
+        raise ValueError(f'knn_plan: an item is held by {max_degree} users; counts stay exact in fp32 below 2^24 only')
+    run = torch.cat([deg_u.new_zeros(1), torch.cumsum(deg_u[i_users.long()], 0)])
+    weight = run[i_indptr[1:]] - run[i_indptr[:-1]]
+    weight[0] = 0                                                 # the padding item is nobody's target
+    order = torch.sort(weight, descending=True, stable=True).indices
+    return KnnPlan(order[:int((weight > 0).sum())].to(torch.int32).contiguous(), weight, max_degree)
+
+
+@_on_device
+def knn_build(u_indptr, u_items, i_indptr, i_users, knn, similarity, tile=None, plan=None):
+    """rsa_knn_build: for every item i the ``min(knn, nnz)`` largest similarities of column i of R^T R, R the unit-valued graph of
+    the two CSRs (users -> items with ascending ids in a row, items -> users; int64 row pointers, int32 ids, no duplicates):
+    ``cosine`` s = c / (sqrt(n_j) sqrt(n_i) + 1e-6), ``jaccard`` s = c / (n_j + n_i - c + 1e-6), c = |users(i) & users(j)|, j != i.
+    -> ``(nbr_id int32 [N, knn], nbr_sim fp32 [N, knn], nbr_cnt int32 [N])``: descending s, ties by ascending id; unused slots
+    hold (-1, 0).  ``tile``: item ids per LDS tile (a power of two, default 32768); a catalog of several tiles is merged by a second
+    launch and gives the same bits.  Counts are integer LDS atomics: two runs are bit-equal."""
+    u_indptr, i_indptr = _need(u_indptr, torch.int64, 'u_indptr'), _need(i_indptr, torch.int64, 'i_indptr')
+    u_items, i_users = _need(u_items, torch.int32, 'u_items'), _need(i_users, torch.int32, 'i_users')
+    if similarity not in KNN_SIMILARITIES:
+        raise ValueError('unsupported similarity metric')
+    knn, tile = int(knn), int(tile or KNN_MAX_TILE)
+    if not 1 <= knn <= KNN_MAX_K:
+        raise ValueError(f'knn_build: knn must be in 1 .. {KNN_MAX_K}, got {knn}')
+    if tile < 1 or tile > KNN_MAX_TILE or tile & (tile - 1):
+        raise ValueError(f'knn_build: tile must be a power of two up to {KNN_MAX_TILE}, got {tile}')
+    if u_items.numel() != i_users.numel():
+        raise ValueError('knn_build: the two CSRs must hold the same interactions')
+    plan = plan or knn_plan(u_indptr, i_indptr, i_users)
+    U, N, dev = u_indptr.numel() - 1, i_indptr.numel() - 1, u_indptr.device
+    nbr_id = torch.full((N, knn), -1, dtype=torch.int32, device=dev)
+    nbr_sim = torch.zeros(N, knn, dtype=torch.float32, device=dev)
+    nbr_cnt = torch.zeros(N, dtype=torch.int32, device=dev)
+    order = plan.order.to(dev)
+    n_tiles = -(-N // tile)
+    part = max(1, order.numel()) if n_tiles == 1 else max(1, min(KNN_WORKSPACE_BYTES // (n_tiles * knn * 8), ((1 << 31) - 1) // n_tiles))
+    a = nat.KnnBuildArgs()
+    a.u_indptr, a.u_items, a.i_indptr, a.i_users = ptr(u_indptr), ptr(u_items), ptr(i_indptr), ptr(i_users)
+    a.n_users, a.n_items, a.nnz, a.max_degree = U, N, u_items.numel(), plan.max_degree
+    a.knn, a.tile, a.similarity = knn, tile, KNN_SIMILARITIES[similarity]
+    a.nbr_id, a.nbr_sim, a.nbr_cnt = ptr(nbr_id), ptr(nbr_sim), ptr(nbr_cnt)
+    ws = None
+    for s in range(0, order.numel(), part):
+        piece = order[s:s + part]
+        a.order, a.n_order = ptr(piece), piece.numel()
+        if n_tiles > 1 and ws is None:                            # the first part is the largest
+            ws, a.workspace_bytes = _workspace(dev, 'rsa_knn_build_workspace_bytes', N, piece.numel(), knn, tile)
+            a.workspace = ptr(ws)
+        _launch('rsa_knn_build', ctypes.byref(a))
+    return nbr_id, nbr_sim, nbr_cnt
+
+
+def knn_transpose(nbr_id, nbr_sim, nbr_cnt):
+    """The neighbour lists by NEIGHBOUR: ``(t_indptr int64 [N + 1], t_items int32, t_sim fp32)``, row j holding the targets i (ascending)
+    whose list names j, with sim(j -> i).  Torch ops, once per fit: one stable sort of the N * knn keys."""
+    N, knn = nbr_id.shape
+    live = torch.arange(knn, device=nbr_id.device)[None] < nbr_cnt[:, None]
+    target = torch.arange(N, device=nbr_id.device)[:, None].expand(N, knn)[live]
+    j, sim = nbr_id[live].long(), nbr_sim[live]
+    pos = torch.sort(j, stable=True).indices                      # row-major input: targets stay ascending within a j
+    t_indptr = torch.cat([j.new_zeros(1), torch.cumsum(torch.bincount(j, minlength=N), 0)])
+    return t_indptr, target[pos].to(torch.int32).contiguous(), sim[pos].contiguous()
+
+
+@_on_device
+def knn_score(users, indptr, items, t_indptr, t_items, t_sim, n_items, tile=None):
+    """rsa_knn_score: ``out[b, c] = sum_{j in hist(users[b])} sim(j -> item c + 1)``, fp32 [B, n_items - 1], the history being row
+    ``users[b]`` of the users -> items CSR and ``t_*`` the lists of ``knn_transpose``.  Every sum runs in ascending j without
+    atomics: a user's row is bit-equal alone, in any batch, with any ``tile`` (target items per workgroup, default 8192) and on
+    any run.  A user without history gets zeros."""
+    users = _need(users, torch.int64, 'users')
+    indptr, t_indptr = _need(indptr, torch.int64, 'indptr'), _need(t_indptr, torch.int64, 't_indptr')
+    items, t_items = _need(items, torch.int32, 'items'), _need(t_items, torch.int32, 't_items')
+    t_sim = _need(t_sim, torch.float32, 't_sim')
+    n_items = int(n_items)
+    if t_indptr.numel() != n_items + 1 or t_items.numel() != t_sim.numel():
+        raise ValueError('knn_score: t_indptr must be [n_items + 1] and t_items / t_sim of one length')
+    out = torch.empty(users.numel(), n_items - 1, dtype=torch.float32, device=users.device)
+    a = nat.KnnScoreArgs()
+    a.users, a.u_indptr, a.u_items, a.t_indptr, a.t_items, a.t_sim = (ptr(users), ptr(indptr), ptr(items), ptr(t_indptr), ptr(t_items),
+                                                                      ptr(t_sim))
+    a.n_batch, a.n_users, a.n_items, a.tile, a.out = users.numel(), indptr.numel() - 1, n_items, int(tile or 0), ptr(out)
+    _launch('rsa_knn_score', ctypes.byref(a))
+    return out

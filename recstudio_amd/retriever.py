@@ -1239,5 +1239,6 @@ from .models_graph import LightGCN, NGCF, SGL, SimGCL                           
 from .models_seq import (CL4SRec, CaserQueryEncoder, GRU4Rec, GRU4RecQueryEncoder, HGN, HGNQueryEncoder, NARM,   # noqa: E402, F401
                          NARMQueryEncoder, SASRec, SASRecQueryEncoder, STAMP, STAMPQueryEncoder, FUSED_ATTENTION_POOL_DEFAULT,
                          FUSED_GATING_DEFAULT, FUSED_INFONCE_DEFAULT)
-from .models_mf import NCF, FUSED_SCORER_DEFAULT, WRMF, FUSED_ALS_DEFAULT, als_step_torch                  # noqa: E402, F401
+from .models_mf import (NCF, FUSED_SCORER_DEFAULT, WRMF, FUSED_ALS_DEFAULT, als_step_torch, ItemKNN,      # noqa: E402, F401
+                        FUSED_KNN_DEFAULT, itemknn_torch, itemknn_score_torch)
 from .models_ae import MultiDAE, MultiDAEQueryEncoder, MultiVAE, MultiVAEQueryEncoder, FUSED_BAG_DEFAULT   # noqa: E402, F401
