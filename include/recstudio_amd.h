@@ -1392,6 +1392,99 @@ typedef struct rsa_knn_score_args {
 } rsa_knn_score_args;
 int rsa_knn_score(const rsa_knn_score_args* args, rsa_stream_t stream);
 
+/* EASE (recstudio/model/mf/ease.py): B = P / (-diag P) with a zero diagonal, P = (R^T R + lambda I)^-1, all in float64 with 64-bit
+ * indexing (N^2 passes 2^31 at N = 46341), no float atomics: two runs are bit-equal.  Four entry points, in the order of a fit.
+ *
+ * rsa_ease_gram: G[i, j] = #{u : i, j in hist(u)} + lambda [i == j], dense float64 [n_items, n_items] with row stride ld, from the
+ * two CSRs of rsa_knn_build (users -> items ASCENDING within a row, items -> users).  One workgroup owns one (row i, tile of `tile`
+ * columns) pair: waves stride over users(i), lanes walk the user's row from the tile's lower bound and count into 32-bit LDS counters
+ * with integer atomics (exact, order-free); every counter is then stored as a double.  An item without users (the padding item 0
+ * among them) gets lambda e_i.  tile: 1 .. 16384, 0 = the default 8192.
+ *
+ * rsa_spd_inverse_f64: P = A^-1 of a symmetric positive-definite A (float64 [n, n], row stride ld; only the lower triangle is
+ * read), blocked by 64 and host-driven: every launch goes to `stream`, nothing synchronises.  (1) left-looking Cholesky: block
+ * column k becomes A[k:, k] - L[k:, :k] L[k, :k]^T, its diagonal block is factored and the factor inverted by ONE workgroup in LDS
+ * (a ragged last block is padded with the identity; L_kk^-1 goes to the workspace), and the rest of the panel is multiplied by
+ * L_kk^-T; (2) W = L^-1 by block rows, W[i, :i] = -L_ii^-1 (L[i, :i] W[:i, :i]) through a [64, n] row panel in the workspace,
+ * W[i, i] = L_ii^-1; (3) P = W^T W over the lower block triangle, every off-diagonal tile also stored transposed: P is
+ * bit-symmetric.  All products run as 64 x 64 tiles on v_mfma_f64_16x16x4_f64 over exactly the blocks the triangular structure
+ * leaves.  A is CONSUMED: it holds W afterwards (lower triangle, blocks above the diagonal untouched).  P [n, n] with row stride
+ * ldp must not overlap A.  status (one int32 on the device): 0, or c + 1 for the first column c whose pivot is not positive (or is
+ * NaN); then that block and everything derived from it is NaN, so P is NaN throughout.  Nothing traps.  16-byte loads are used
+ * when ld is even and A is 16-byte aligned, 8-byte loads otherwise; the values are the same.
+ *
+ * rsa_ease_weights: one pass over P [n, n] (row stride ld): B[j, i] = -P[j, i] / P[i, i], B[i, i] = +0, and
+ * loss[0] = sqrt(sum_i (1 / P_ii - lambda sum_j P_ji^2 / P_ii^2)) = ||R - R B||_F (I - B = P diag(P)^-1 and R^T R = G - lambda I),
+ * every sum in a fixed order: one workgroup per tile of 64 columns, rows ascending in four interleaved chains, then the columns
+ * ascending.  b may be p (in place); otherwise it has row stride ldb.  terms: float64 [n] scratch of the caller (the summands of the loss).
+ *
+ * rsa_ease_score: out[b, i - 1] = fp32(sum over j in hist(users[b]) of B[j, i]), i = 1 .. n_items - 1, fp32 [n_batch, n_items - 1].
+ * One workgroup owns one (user, tile of 512 columns) pair, two columns per thread with float64 sums in registers; the history (row
+ * users[b] of the users -> items CSR) is walked in STORED order: a user's bits do not depend on the batch.  A user without
+ * history, or an id outside [0, n_users), gets zeros.  16-byte loads when ld is even and b is 16-byte aligned.
+ *
+ * Null pointers, n < 1, ld < n, lambda not finite, a tile out of range, a workspace that is too small: RSA_ERR_ARG before the
+ * first HIP call.  Appended without a new RSA_ABI_VERSION. */
+#define RSA_SPD_BLOCK 64
+#define RSA_EASE_MAX_TILE 16384
+typedef struct rsa_ease_gram_args {
+  int64_t size;                /* sizeof(rsa_ease_gram_args) */
+  const int64_t* u_indptr;     /* [n_users + 1] */
+  const int32_t* u_items;      /* [nnz], ascending within a row */
+  const int64_t* i_indptr;     /* [n_items + 1] */
+  const int32_t* i_users;      /* [nnz] */
+  int64_t n_users;
+  int64_t n_items;
+  int64_t nnz;
+  int64_t ld;                  /* row stride of g, >= n_items */
+  double lam;                  /* lambda */
+  int32_t tile;                /* columns per workgroup, 0 = default */
+  int32_t reserved;
+  double* g;                   /* [n_items, ld] out */
+} rsa_ease_gram_args;
+int rsa_ease_gram(const rsa_ease_gram_args* args, rsa_stream_t stream);
+
+typedef struct rsa_spd_inverse_args {
+  int64_t size;                /* sizeof(rsa_spd_inverse_args) */
+  double* a;                   /* [n, ld] in: SPD (lower triangle read); out: W = L^-1 */
+  double* p;                   /* [n, ldp] out */
+  int32_t* status;             /* one word, out */
+  int64_t n;
+  int64_t ld;
+  int64_t ldp;
+  void* workspace;
+  int64_t workspace_bytes;     /* >= rsa_spd_inverse_f64_workspace_bytes(n) */
+} rsa_spd_inverse_args;
+int64_t rsa_spd_inverse_f64_workspace_bytes(int64_t n);
+int rsa_spd_inverse_f64(const rsa_spd_inverse_args* args, rsa_stream_t stream);
+
+typedef struct rsa_ease_weights_args {
+  int64_t size;                /* sizeof(rsa_ease_weights_args) */
+  const double* p;             /* [n, ld] */
+  double* b;                   /* [n, ldb] out; may be p */
+  double* terms;               /* [n] scratch: the per-column terms of the loss */
+  double* loss;                /* [1] out */
+  int64_t n;
+  int64_t ld;
+  int64_t ldb;
+  double lam;                  /* lambda */
+} rsa_ease_weights_args;
+int rsa_ease_weights(const rsa_ease_weights_args* args, rsa_stream_t stream);
+
+typedef struct rsa_ease_score_args {
+  int64_t size;                /* sizeof(rsa_ease_score_args) */
+  const int64_t* users;        /* [n_batch] */
+  const int64_t* u_indptr;     /* [n_users + 1] */
+  const int32_t* u_items;
+  const double* b;             /* [n_items, ld] */
+  int64_t n_batch;
+  int64_t n_users;
+  int64_t n_items;
+  int64_t ld;
+  float* out;                  /* [n_batch, n_items - 1] */
+} rsa_ease_score_args;
+int rsa_ease_score(const rsa_ease_score_args* args, rsa_stream_t stream);
+
 /* One augmented view of a batch of histories for the contrastive sequence retrievers (CL4SRec: recstudio/model/seq/cl4srec.py;
  * Item_Crop / Item_Mask / Item_Reorder, recstudio/model/module/data_augmentation.py:22-87), one launch.  The random choices are
  * the elements of ONE torch.rand([n_seq, seq_len + 1]) call for the given Philox state: U[b, 0] draws the start, U[b, 1 + p] is

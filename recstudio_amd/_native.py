@@ -398,6 +398,39 @@ class KnnScoreArgs(_Sized):
     ]
 
 
+class EaseGramArgs(_Sized):
+    """struct rsa_ease_gram_args."""
+    _fields_ = [
+        ('size', c_int64), ('u_indptr', c_void_p), ('u_items', c_void_p), ('i_indptr', c_void_p), ('i_users', c_void_p),
+        ('n_users', c_int64), ('n_items', c_int64), ('nnz', c_int64), ('ld', c_int64), ('lam', c_double), ('tile', c_int32),
+        ('reserved', c_int32), ('g', c_void_p),
+    ]
+
+
+class SpdInverseArgs(_Sized):
+    """struct rsa_spd_inverse_args."""
+    _fields_ = [
+        ('size', c_int64), ('a', c_void_p), ('p', c_void_p), ('status', c_void_p), ('n', c_int64), ('ld', c_int64), ('ldp', c_int64),
+        ('workspace', c_void_p), ('workspace_bytes', c_int64),
+    ]
+
+
+class EaseWeightsArgs(_Sized):
+    """struct rsa_ease_weights_args."""
+    _fields_ = [
+        ('size', c_int64), ('p', c_void_p), ('b', c_void_p), ('terms', c_void_p), ('loss', c_void_p), ('n', c_int64), ('ld', c_int64),
+        ('ldb', c_int64), ('lam', c_double),
+    ]
+
+
+class EaseScoreArgs(_Sized):
+    """struct rsa_ease_score_args."""
+    _fields_ = [
+        ('size', c_int64), ('users', c_void_p), ('u_indptr', c_void_p), ('u_items', c_void_p), ('b', c_void_p), ('n_batch', c_int64),
+        ('n_users', c_int64), ('n_items', c_int64), ('ld', c_int64), ('out', c_void_p),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -413,6 +446,8 @@ STRUCTS = {
     'rsa_hgn_gating_args': HgnGatingArgs, 'rsa_seq_augment_args': SeqAugmentArgs,
     'rsa_batch_infonce_args': BatchInfoNceArgs, 'rsa_bag_args': BagArgs, 'rsa_als_args': AlsArgs,
     'rsa_knn_build_args': KnnBuildArgs, 'rsa_knn_score_args': KnnScoreArgs,
+    'rsa_ease_gram_args': EaseGramArgs, 'rsa_spd_inverse_args': SpdInverseArgs, 'rsa_ease_weights_args': EaseWeightsArgs,
+    'rsa_ease_score_args': EaseScoreArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -528,6 +563,11 @@ SIGNATURES = {
     'rsa_knn_build_workspace_bytes': (c_int64, [c_int64, c_int64, c_int32, c_int32]),
     'rsa_knn_build': (c_int, [POINTER(KnnBuildArgs), c_void_p]),
     'rsa_knn_score': (c_int, [POINTER(KnnScoreArgs), c_void_p]),
+    'rsa_ease_gram': (c_int, [POINTER(EaseGramArgs), c_void_p]),
+    'rsa_spd_inverse_f64_workspace_bytes': (c_int64, [c_int64]),
+    'rsa_spd_inverse_f64': (c_int, [POINTER(SpdInverseArgs), c_void_p]),
+    'rsa_ease_weights': (c_int, [POINTER(EaseWeightsArgs), c_void_p]),
+    'rsa_ease_score': (c_int, [POINTER(EaseScoreArgs), c_void_p]),
 }
 
 _lib = None

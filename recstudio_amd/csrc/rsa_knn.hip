@@ -15,6 +15,7 @@
 //   emit     a one-tile catalog writes the neighbour lists; otherwise the sorted keys go to the workspace and knn_merge_kernel
 //            ranks every candidate of an item among its tiles' lists (binary searches; the keys are distinct) and writes the first knn.
 // SCORE.  One workgroup of 256 threads owns one (user, tile of target items) pair with the fp32 sums in LDS; see the header.
+#include "rsa_csr.hpp"
 #include "rsa_launch.hpp"
 #include "rsa_lds.hpp"
 
@@ -50,15 +51,6 @@ __device__ __forceinline__ float knn_sim(int32_t c, int32_t nj, int32_t ni, bool
 }
 
 __device__ __forceinline__ uint64_t knn_sort_key(uint32_t bits, int32_t id) { return ((uint64_t)(~bits) << 32) | (uint32_t)id; }
-
-// first position in [a, b) of the ascending ids whose value is >= v
-__device__ __forceinline__ int64_t knn_lower_bound(const int32_t* __restrict__ ids, int64_t a, int64_t b, int32_t v) {
-  while (a < b) {
-    const int64_t mid = a + ((b - a) >> 1);
-    if (ids[mid] < v) a = mid + 1; else b = mid;
-  }
-  return a;
-}
 
 __device__ __forceinline__ void knn_emit(const KnnBuildParams& p, int32_t item, int r, bool live, uint64_t key) {
   const size_t at = (size_t)item * (size_t)p.knn + (size_t)r;

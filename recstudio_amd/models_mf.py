@@ -1,4 +1,4 @@
-"""The matrix-factorisation family beyond BPR: NCF, WRMF, ItemKNN."""
+"""The matrix-factorisation family beyond BPR: NCF, WRMF, ItemKNN, EASE."""
 import time
 
 import torch
@@ -13,7 +13,7 @@ from .scorer import FusionMFMLPScorer, GMFScorer, InnerProductScorer, MLPScorer
 from .seqmodule import MLPModule
 
 __all__ = ['NCF', 'FUSED_SCORER_DEFAULT', 'WRMF', 'FUSED_ALS_DEFAULT', 'als_step_torch', 'ItemKNN', 'FUSED_KNN_DEFAULT',
-           'itemknn_torch', 'itemknn_score_torch']
+           'itemknn_torch', 'itemknn_score_torch', 'EASE', 'FUSED_EASE_DEFAULT', 'ease_torch', 'ease_score_torch']
 
 # model.fused_scorer: the pair scorers run in rsa_pair_mlp (forward, backward, range-mode top-k) instead of torch ops.  Off:
 # tools/bench_ncf.py (profiles/ncf_bench.json) has the kernel ahead in every forward and behind in every forward + backward.
@@ -188,6 +188,20 @@ FUSED_KNN_DEFAULT = True
 _KNN_BUFFERS = ('nbr_id', 'nbr_sim', 'nbr_cnt', 't_indptr', 't_items', 't_sim', 'user_indptr', 'user_items')
 
 
+def _interaction_csrs(train_data, device, who):
+    """The unit-valued interaction graph of a train split on ``device``: ``(users, items, n_users, n_items, (u_indptr, u_items),
+    (i_indptr, i_users))``, both CSRs with int64 row pointers and int32 ids ascending within a row."""
+    if not train_data.drop_dup:
+        raise ValueError(f'{who}: the interaction graph is unit-valued; drop_dup: False (repeated pairs) is not covered')
+    (users, items, _, (n_users, n_items)), _ = train_data.get_graph([0])
+    users, items = users.to(device), items.to(device)
+
+    def csr(key, val, n):                                            # ids ascending within a row
+        order = torch.sort(key * (int(val.max()) + 1 if val.numel() else 1) + val).indices
+        return torch.cat([key.new_zeros(1), torch.cumsum(torch.bincount(key, minlength=n), 0)]), val[order].to(torch.int32)
+    return users, items, n_users, n_items, csr(users, items, n_users), csr(items, users, n_items)
+
+
 def itemknn_torch(users, items, n_users, n_items, knn, similarity, dtype=torch.float32, chunk=2048):
     """The torch-op twin of ``ops.knn_build`` (recstudio/model/mf/itemknn.py:12-41): the dense ``R^T R`` in column chunks, the same
     formula in ``dtype``, and the ``min(knn, nnz)`` largest of each column.  ``users`` / ``items``: the interactions, one id pair each,
@@ -268,15 +282,7 @@ class ItemKNN(BaseRetriever):
         tr = self.config['train']
         if tr['similarity'] not in ops.KNN_SIMILARITIES:
             raise ValueError('unsupported similarity metric')
-        if not train_data.drop_dup:
-            raise ValueError('ItemKNN: the interaction graph is unit-valued; drop_dup: False (repeated pairs) is not covered')
-        (users, items, _, (n_users, n_items)), _ = train_data.get_graph([0])
-        users, items = users.to(device), items.to(device)
-
-        def csr(key, val, n):                                            # ids ascending within a row
-            order = torch.sort(key * (int(val.max()) + 1 if val.numel() else 1) + val).indices
-            return torch.cat([key.new_zeros(1), torch.cumsum(torch.bincount(key, minlength=n), 0)]), val[order].to(torch.int32)
-        (u_indptr, u_items), (i_indptr, i_users) = csr(users, items, n_users), csr(items, users, n_items)
+        users, items, n_users, n_items, (u_indptr, u_items), (i_indptr, i_users) = _interaction_csrs(train_data, device, 'ItemKNN')
         if self.config['model']['fused_knn']:
             nbr = ops.knn_build(u_indptr, u_items, i_indptr, i_users, tr['knn'], tr['similarity'])
         else:
@@ -328,6 +334,135 @@ class ItemKNN(BaseRetriever):
     def evaluate(self, test_data, verbose=True, **kwargs):
         test_data.use_field = self.fields
         out = self._eval_epoch(test_data, self.test_step, self.nbr_cnt.device)
+        if verbose:
+            self.logger.info(str(out))
+        return out
+
+
+# model.fused_ease: the fit and the scores run in rsa_ease_gram / rsa_spd_inverse_f64 / rsa_ease_weights / rsa_ease_score instead of
+# ease_torch / ease_score_torch.  Off: tools/bench_ease.py (profiles/ease_bench.json, medians of 3) at about ml-1m's shape has the fused
+# fit at 19.8 ms against 15.6 ms for torch.linalg.cholesky + cholesky_inverse (torch.linalg.inv 40.5 ms); at about ml-20m's
+# (N = 20001) the fused fit takes 545 ms (37 % of the fp64 matrix floor) and BOTH torch arms fail inside hipBLAS / hipSOLVER, so
+# there is no second win to count; a score batch (B = 512) is ahead at both, 0.15 / 0.30 ms and 1.07 / 6.64 ms.
+FUSED_EASE_DEFAULT = False
+_EASE_BUFFERS = ('ease_B', 'user_indptr', 'user_items')
+
+
+def ease_torch(users, items, n_users, n_items, lam):
+    """The reference's op sequence (recstudio/model/mf/ease.py) in torch ops on the device of ``users``: dense float64 ``R``,
+    ``G = R^T R + lam I``, ``P = inv(G)``, ``B = P / (-diag P)`` with a zero diagonal, and the loss ``||R - R B||_F``.
+    -> ``(B float64 [N, N], loss float64 scalar tensor)``."""
+    R = torch.zeros(n_users, n_items, dtype=torch.float64, device=users.device)
+    R[users.long(), items.long()] = 1
+    G = R.T @ R
+    G.diagonal().add_(lam)
+    P = torch.linalg.inv(G)
+    B = P / (-P.diagonal())
+    B.diagonal().zero_()
+    return B, torch.linalg.norm(R - R @ B)
+
+
+def ease_score_torch(users, indptr, items, B):
+    """The torch-op twin of ``ops.ease_score``: the dense float64 rows ``R[users]`` times ``B[:, 1:]``, as fp32."""
+    users = users.long()
+    deg = indptr[users + 1] - indptr[users]
+    b = torch.repeat_interleave(torch.arange(users.numel(), device=users.device), deg)
+    pos = torch.arange(b.numel(), device=users.device) - torch.repeat_interleave(torch.cumsum(deg, 0) - deg, deg)
+    R = torch.zeros(users.numel(), B.size(0), dtype=torch.float64, device=users.device)
+    R[b, items[indptr[users][b] + pos].long()] = 1
+    return (R @ B[:, 1:]).float()
+
+
+class EASE(BaseRetriever):
+    """recstudio/model/mf/ease.py, recstudio/model/mf/config/ease.yaml (lambda 250): Embarrassingly Shallow Autoencoders.  There is
+    nothing to iterate: ``fit`` computes, once, ``B = P / (-diag P)`` with a zero diagonal from ``P = (R^T R + lambda I)^-1`` in
+    float64, and a user's score of item i is the sum of ``B[j, i]`` over the user's train items j.  No sampler, loss function,
+    optimizer or encoder; ``ease_B`` [N, N] float64 and the user-side CSR are buffers, so ``state_dict`` carries the fitted model.
+    ``model.fused_ease``: ``ops.ease_gram`` / ``spd_inverse`` / ``ease_weights`` / ``ease_score``; off, ``ease_torch`` /
+    ``ease_score_torch``.  The epoch loss is the reference's ``||R - R B||_F`` (with the flag on, its closed form from ``P``).
+    Two deviations from the reference: it sets ``config['train']['gpu']`` to None (its only path is numpy on the host); this
+    model leaves the config alone and runs on the configured device.  Its ``state_dict`` carries the whole dense ``R``
+    (``user_item_matrix``); this one carries the CSR of R."""
+
+    config_defaults = {'model': {'fused_ease': FUSED_EASE_DEFAULT}, 'train': {'lambda': 250, 'epochs': 1}}
+
+    def _get_item_encoder(self, train_data):
+        return None
+
+    def _get_query_encoder(self, train_data):
+        return None
+
+    def _get_loss_func(self):
+        return None
+
+    def _get_sampler(self, train_data):
+        return None
+
+    def _update_item_vector(self):
+        pass                                                              # the "item vector" is ease_B itself
+
+    def _get_item_vector(self):
+        return self.ease_B[:, 1:]                                         # ease.py: item_vector = B[:, 1:]
+
+    def _ease_build(self, train_data, device):
+        lam = self.config['train']['lambda']
+        users, items, n_users, n_items, (u_indptr, u_items), (i_indptr, i_users) = _interaction_csrs(train_data, device, 'EASE')
+        if self.config['model']['fused_ease']:
+            P, status = ops.spd_inverse(ops.ease_gram(u_indptr, u_items, i_indptr, i_users, lam), overwrite=True)
+            if int(status) != 0:
+                raise ValueError(f'EASE: R^T R + lambda I is not positive definite at item {int(status) - 1} (lambda = {lam}; it must be > 0)')
+            B, loss = ops.ease_weights(P, lam, overwrite=True)
+        else:
+            if not lam > 0:
+                raise ValueError(f'EASE: lambda = {lam} must be > 0 (item 0 has no interactions: its column is singular)')
+            B, loss = ease_torch(users, items, n_users, n_items, lam)
+        for name, t in zip(_EASE_BUFFERS, (B, u_indptr, u_items)):
+            self.register_buffer(name, t)
+        return float(loss)
+
+    def load_state_dict(self, state_dict, strict=True):
+        for name in _EASE_BUFFERS:                                       # a fresh model has no weights yet: take their shapes from the state
+            if name in state_dict:
+                self.register_buffer(name, torch.empty_like(state_dict[name]))
+        return super().load_state_dict(state_dict, strict)
+
+    def topk(self, batch, k, user_h=None, return_query=False):
+        """baseretriever.py:374-397 over the EASE scores: top (k + |hist|), ids + 1, the history dropped, top k."""
+        users = (batch[self.fuid] if isinstance(batch, dict) else batch).to(self.ease_B.device)
+        n_items = self.ease_B.size(0)
+        score_fn = ops.ease_score if self.config['model']['fused_ease'] else ease_score_torch
+        scores = score_fn(users, self.user_indptr, self.user_items, self.ease_B)
+        kc = min(k + (user_h.size(1) if user_h is not None else 0), n_items - 1)
+        score, topk_items = ops.row_topk(scores, kc) if kc <= ops.FULLSCORE_MAX_K else torch.topk(scores, kc)
+        topk_items = topk_items + 1
+        if user_h is not None:
+            score, topk_items = ops.topk_mask_history(score, topk_items, user_h, min(k, kc))
+        return (score, topk_items, scores) if return_query else (score, topk_items)
+
+    def fit(self, train_data, val_data=None, run_mode='light', config=None, **kwargs):
+        if config is not None:
+            self.config.update(config)
+        if self._dist_context(kwargs) is not None:
+            raise NotImplementedError('EASE: the sharded fit is not covered (the dense N x N inverse lives on one device)')
+        self._init_model(train_data)
+        device = self._device()
+        self.to(device)
+        if val_data is not None:
+            val_data.use_field = train_data.use_field
+
+        def train_epoch():
+            return self._ease_build(train_data, device)
+
+        def validate():
+            t1 = time.time()
+            metrics = self._eval_epoch(val_data, self.validation_step, device)
+            return dict(metrics, valid_time=time.time() - t1)
+
+        return self._run_epochs(train_epoch, None, validate if val_data is not None else None, log=self.logger.info)
+
+    def evaluate(self, test_data, verbose=True, **kwargs):
+        test_data.use_field = self.fields
+        out = self._eval_epoch(test_data, self.test_step, self.ease_B.device)
         if verbose:
             self.logger.info(str(out))
         return out

@@ -2461,3 +2461,94 @@ def knn_score(users, indptr, items, t_indptr, t_items, t_sim, n_items, tile=None
     a.n_batch, a.n_users, a.n_items, a.tile, a.out = users.numel(), indptr.numel() - 1, n_items, int(tile or 0), ptr(out)
     _launch('rsa_knn_score', ctypes.byref(a))
     return out
+
+
+# ------------------------------------------------------------------ EASE: Gram matrix, SPD inverse, weights, scoring (all float64)
+EASE_MAX_TILE = 16384             # 32-bit counters of one (item, column tile) workgroup in LDS (rsa_ease.hip)
+
+
+def _f64_matrix(t, name):
+    """A float64 [n, m] device matrix with unit column stride, read in place through its row stride."""
+    t = _need_view(t, torch.float64, name)
+    if t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.size(1):
+        raise ValueError(f'{name}: expected a 2-D matrix with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}')
+    return t
+
+
+def _even_rows(n, dev):
+    """An uninitialised float64 [n, n] whose row stride is even: every row starts on a 16-byte boundary."""
+    return torch.empty(n, n + (n & 1), dtype=torch.float64, device=dev)[:, :n]
+
+
+@_on_device
+def ease_gram(u_indptr, u_items, i_indptr, i_users, lam, tile=None):
+    """rsa_ease_gram: ``G = R^T R + lam I``, float64 [N, N] (a view with an even row stride), R the unit-valued graph of the two CSRs
+    of ``knn_build``.  Counts are integer LDS atomics: exact, two runs bit-equal.  ``tile``: columns per workgroup (default 8192)."""
+    u_indptr, i_indptr = _need(u_indptr, torch.int64, 'u_indptr'), _need(i_indptr, torch.int64, 'i_indptr')
+    u_items, i_users = _need(u_items, torch.int32, 'u_items'), _need(i_users, torch.int32, 'i_users')
+    if u_items.numel() != i_users.numel():
+        raise ValueError('ease_gram: the two CSRs must hold the same interactions')
+    U, N = u_indptr.numel() - 1, i_indptr.numel() - 1
+    G = _even_rows(N, u_indptr.device)
+    a = nat.EaseGramArgs()
+    a.u_indptr, a.u_items, a.i_indptr, a.i_users = ptr(u_indptr), ptr(u_items), ptr(i_indptr), ptr(i_users)
+    a.n_users, a.n_items, a.nnz, a.ld, a.lam, a.tile, a.g = U, N, u_items.numel(), G.stride(0), float(lam), int(tile or 0), ptr(G)
+    _launch('rsa_ease_gram', ctypes.byref(a))
+    return G
+
+
+@_on_device
+def spd_inverse(A, overwrite=False):
+    """rsa_spd_inverse_f64: ``(P, status)`` with ``P = A^-1`` for a symmetric positive-definite float64 ``A`` [n, n] (only the
+    lower triangle is read): blocked Cholesky, triangular inverse and ``W^T W`` on the fp64 matrix cores, enqueued without a host
+    synchronisation.  ``P`` is bit-symmetric and two runs are bit-equal.  ``status`` (int32 [1], on the device): 0, or c + 1 for
+    the first column c with a non-positive pivot; ``P`` is NaN then.  ``overwrite``: ``A`` itself is the scratch (it holds
+    ``L^-1`` afterwards) instead of a copy."""
+    A = _f64_matrix(A, 'A')
+    n = A.size(0)
+    if A.size(1) != n or n < 1:
+        raise ValueError(f'spd_inverse: A must be square and non-empty, got {tuple(A.shape)}')
+    if not overwrite:
+        A = _even_rows(n, A.device).copy_(A)
+    P = torch.empty(n, n, dtype=torch.float64, device=A.device)
+    status = torch.empty(1, dtype=torch.int32, device=A.device)
+    a = nat.SpdInverseArgs()
+    ws, a.workspace_bytes = _workspace(A.device, 'rsa_spd_inverse_f64_workspace_bytes', n)
+    a.a, a.p, a.status, a.n, a.ld, a.ldp, a.workspace = ptr(A), ptr(P), ptr(status), n, A.stride(0), n, ptr(ws)
+    _launch('rsa_spd_inverse_f64', ctypes.byref(a))
+    return P, status
+
+
+@_on_device
+def ease_weights(P, lam, overwrite=False):
+    """rsa_ease_weights: ``(B, loss)`` with ``B[j, i] = -P[j, i] / P[i, i]``, a +0 diagonal, and ``loss`` (float64 [1]) the
+    closed form of ``||R - R B||_F`` for ``P = (R^T R + lam I)^-1``, every sum in a fixed order.  ``overwrite``: ``B`` is ``P``."""
+    P = _f64_matrix(P, 'P')
+    n = P.size(0)
+    if P.size(1) != n or n < 1:
+        raise ValueError(f'ease_weights: P must be square and non-empty, got {tuple(P.shape)}')
+    B = P if overwrite else torch.empty(n, n, dtype=torch.float64, device=P.device)
+    terms = torch.empty(n, dtype=torch.float64, device=P.device)
+    loss = torch.empty(1, dtype=torch.float64, device=P.device)
+    a = nat.EaseWeightsArgs()
+    a.p, a.b, a.terms, a.loss, a.n, a.ld, a.ldb, a.lam = ptr(P), ptr(B), ptr(terms), ptr(loss), n, P.stride(0), B.stride(0), float(lam)
+    _launch('rsa_ease_weights', ctypes.byref(a))
+    return B, loss
+
+
+@_on_device
+def ease_score(users, u_indptr, u_items, B):
+    """rsa_ease_score: ``out[b, i - 1] = fp32(sum_{j in hist(users[b])} B[j, i])``, fp32 [len(users), N - 1], the history being row
+    ``users[b]`` of the users -> items CSR, walked in stored order with float64 sums: a user's row is bit-equal alone and in any
+    batch.  A user without history gets zeros."""
+    users, u_indptr = _need(users, torch.int64, 'users'), _need(u_indptr, torch.int64, 'u_indptr')
+    u_items, B = _need(u_items, torch.int32, 'u_items'), _f64_matrix(B, 'B')
+    N = B.size(0)
+    if B.size(1) != N:
+        raise ValueError(f'ease_score: B must be square, got {tuple(B.shape)}')
+    out = torch.empty(users.numel(), N - 1, dtype=torch.float32, device=users.device)
+    a = nat.EaseScoreArgs()
+    a.users, a.u_indptr, a.u_items, a.b, a.out = ptr(users), ptr(u_indptr), ptr(u_items), ptr(B), ptr(out)
+    a.n_batch, a.n_users, a.n_items, a.ld = users.numel(), u_indptr.numel() - 1, N, B.stride(0)
+    _launch('rsa_ease_score', ctypes.byref(a))
+    return out
