@@ -1485,6 +1485,43 @@ typedef struct rsa_ease_score_args {
 } rsa_ease_score_args;
 int rsa_ease_score(const rsa_ease_score_args* args, rsa_stream_t stream);
 
+/* SLIM (recstudio/model/mf/slim.py): for every target item j the elastic-net problem sklearn's Gram solver
+ * (enet_coordinate_descent_gram, positive = True) is given by the reference, all in float64:
+ *   minimise 1/2 w^T Q w - q^T w + l1 |w|_1 + l2 / 2 |w|^2,   Q = G with row and column j zeroed, q_k = G[k, j] (q_j = 0), y.y = G[j, j]
+ * on the symmetric Gram matrix G = R^T R (float64 [n_items, n_items], row stride ld, read in place), l1 = alpha l1_ratio U,
+ * l2 = alpha (1 - l1_ratio) U.  The solver's rule is kept whole -- the coordinate update with the positive clamp, the skip of
+ * coordinates with a zero diagonal, d_w_max / w_max < tol gating the duality gap, gap < tol y.y as the stop, n_iter -- except the
+ * order of a sweep, which is CYCLIC, ascending k (the reference draws it from sklearn's private stream).  Only the candidates
+ * C_j = {k != j, k >= 1 : G[k, j] > l1} are held: every other coordinate stays 0 and adds nothing to the stop tests.
+ * A target's candidates are found by the kernel; cap bounds them (the caller passes max_j |C_j|, at least 1).
+ * order_wave lists the targets one wave solves (|C_j| <= 64: candidates in registers, the sub-Gram as fp32 in LDS), order_group those
+ * one 256-thread workgroup solves (state in LDS, at most RSA_SLIM_MAX_CANDIDATES).  A target in neither list is left alone.
+ * Outputs, row j: nbr_id / nbr_w [n_items, cap] the non-zero weights by ascending id (slots behind nbr_cnt[j] are not written:
+ * the caller presets them), n_iter[j] the sweeps taken.  No atomics, fixed-order reductions: two runs are bit-equal.
+ * Null pointers, n_items < 2, ld < n_items, cap < 1, l1 < 0, l2 <= 0, tol < 0, max_iter < 1, a cap above the limit with a non-empty
+ * order_group: RSA_ERR_ARG before the first HIP call.  Appended without a new RSA_ABI_VERSION. */
+#define RSA_SLIM_MAX_CANDIDATES 6784
+typedef struct rsa_slim_fit_args {
+  int64_t size;                /* sizeof(rsa_slim_fit_args) */
+  const double* g;             /* [n_items, ld] symmetric */
+  const int32_t* order_wave;   /* [n_wave] targets with at most 64 candidates */
+  const int32_t* order_group;  /* [n_group] the other targets, heaviest first */
+  int64_t n_items;
+  int64_t ld;
+  int64_t n_wave;
+  int64_t n_group;
+  double l1;                   /* alpha * l1_ratio * U */
+  double l2;                   /* alpha * (1 - l1_ratio) * U, > 0 */
+  double tol;
+  int32_t max_iter;
+  int32_t cap;                 /* row stride of nbr_id / nbr_w, >= every |C_j| */
+  int32_t* nbr_id;             /* [n_items, cap] out */
+  double* nbr_w;               /* [n_items, cap] out */
+  int32_t* nbr_cnt;            /* [n_items] out */
+  int32_t* n_iter;             /* [n_items] out */
+} rsa_slim_fit_args;
+int rsa_slim_fit(const rsa_slim_fit_args* args, rsa_stream_t stream);
+
 /* One augmented view of a batch of histories for the contrastive sequence retrievers (CL4SRec: recstudio/model/seq/cl4srec.py;
  * Item_Crop / Item_Mask / Item_Reorder, recstudio/model/module/data_augmentation.py:22-87), one launch.  The random choices are
  * the elements of ONE torch.rand([n_seq, seq_len + 1]) call for the given Philox state: U[b, 0] draws the start, U[b, 1 + p] is

@@ -20,7 +20,7 @@ from .dataset import TripletDataset, SeqDataset, UserDataset, ALSDataset, DataSa
 from .retriever import (BaseRetriever, TwoTowerRecommender, ItemTowerRecommender, BPR, NCF, SASRec, LightGCN,   # noqa: F401
                         SGL, SimGCL, NGCF, CL4SRec, GRU4Rec, NARM, STAMP, HGN, HGNQueryEncoder, MultiDAE, MultiVAE, MultiDAEQueryEncoder,
                         MultiVAEQueryEncoder, WRMF, als_step_torch, ItemKNN, itemknn_torch, itemknn_score_torch, EASE, ease_torch,
-                        ease_score_torch, default_config, seed_everything)
+                        ease_score_torch, SLIM, slim_torch, default_config, seed_everything)
 from . import graphmodule                                         # noqa: F401
 from . import seqmodule                                           # noqa: F401
 from .seqmodule import FusedTransformerEncoder, seq_attention_torch, FusedGRU, gru_sequence_torch   # noqa: F401

@@ -431,6 +431,15 @@ class EaseScoreArgs(_Sized):
     ]
 
 
+class SlimFitArgs(_Sized):
+    """struct rsa_slim_fit_args."""
+    _fields_ = [
+        ('size', c_int64), ('g', c_void_p), ('order_wave', c_void_p), ('order_group', c_void_p), ('n_items', c_int64), ('ld', c_int64),
+        ('n_wave', c_int64), ('n_group', c_int64), ('l1', c_double), ('l2', c_double), ('tol', c_double), ('max_iter', c_int32),
+        ('cap', c_int32), ('nbr_id', c_void_p), ('nbr_w', c_void_p), ('nbr_cnt', c_void_p), ('n_iter', c_void_p),
+    ]
+
+
 # every `typedef struct rsa_* {...}` of the header and its ctypes mirror (tests/test_native_abi.py checks the list against the
 # header and every field offset against the C compiler)
 STRUCTS = {
@@ -447,7 +456,7 @@ STRUCTS = {
     'rsa_batch_infonce_args': BatchInfoNceArgs, 'rsa_bag_args': BagArgs, 'rsa_als_args': AlsArgs,
     'rsa_knn_build_args': KnnBuildArgs, 'rsa_knn_score_args': KnnScoreArgs,
     'rsa_ease_gram_args': EaseGramArgs, 'rsa_spd_inverse_args': SpdInverseArgs, 'rsa_ease_weights_args': EaseWeightsArgs,
-    'rsa_ease_score_args': EaseScoreArgs,
+    'rsa_ease_score_args': EaseScoreArgs, 'rsa_slim_fit_args': SlimFitArgs,
 }
 
 # name -> (restype, argtypes); must list every symbol the header declares.
@@ -568,6 +577,7 @@ SIGNATURES = {
     'rsa_spd_inverse_f64': (c_int, [POINTER(SpdInverseArgs), c_void_p]),
     'rsa_ease_weights': (c_int, [POINTER(EaseWeightsArgs), c_void_p]),
     'rsa_ease_score': (c_int, [POINTER(EaseScoreArgs), c_void_p]),
+    'rsa_slim_fit': (c_int, [POINTER(SlimFitArgs), c_void_p]),
 }
 
 _lib = None

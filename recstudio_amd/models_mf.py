@@ -466,3 +466,159 @@ class EASE(BaseRetriever):
         if verbose:
             self.logger.info(str(out))
         return out
+
+
+# model.fused_slim: the fit runs in rsa_slim_fit instead of slim_torch (scores: rsa_knn_score instead of itemknn_score_torch).
+# On: tools/bench_slim.py (profiles/slim_bench.json, medians of 3) at about ml-1m's shape (6041 x 3707) and the reference's alpha 1,
+# l1_ratio 0.1 has the fused fit, Gram included, at 2.0 ms against 1035 ms for slim_torch (same n_iter on every target, weights
+# within 1.5e-15); sklearn's host loop took 1.65 s for 64 sampled targets, about 96 s scaled to all.  At alpha 0.1 (up to 1892
+# candidates, 467 targets in the workgroup kernel) the fused fit takes 6.7 ms.
+FUSED_SLIM_DEFAULT = True
+_SLIM_BUFFERS = ('slim_indptr', 'slim_items', 'slim_w', 'user_indptr', 'user_items')
+
+
+def slim_torch(G, n_rows, alpha, l1_ratio, positive=True, max_iter=100, tol=1e-4):
+    """The torch-op twin of ``ops.slim_fit`` and the only path for ``positive_only: False``: sklearn's Gram coordinate descent in
+    cyclic order for ALL targets at once in float64, one coordinate per step across all columns.  Column j of ``g`` is target j's
+    ``q - Q w`` and of ``W`` its weights; a column that met its stop test is frozen by a ``done`` mask.
+    -> ``(B float64 [N, N] with B[:, j] = w of target j (column 0 zero), n_iter int64 [N])``."""
+    N = G.size(0)
+    a, b = alpha * l1_ratio * int(n_rows), alpha * (1.0 - l1_ratio) * int(n_rows)
+    G = G.contiguous()
+    diag = G.diagonal().clone()
+    eye = torch.eye(N, dtype=torch.bool, device=G.device)
+    g = G.masked_fill(eye, 0.0)                                       # q: column j of G without its own entry
+    W = torch.zeros_like(g)
+    done = torch.zeros(N, dtype=torch.bool, device=G.device)
+    done[0] = True                                                    # the padding item is nobody's target
+    n_iter = torch.full((N,), int(max_iter), dtype=torch.int64, device=G.device)
+    n_iter[0] = 0
+    live = diag != 0                                                  # a zero diagonal is skipped (item 0, empty items)
+    if positive:
+        live &= (g > a).any(1)                                        # G[k, j] <= a for every j: coordinate k never leaves 0 (DESIGN.md 4.24)
+    coords = torch.nonzero(live).flatten().tolist()
+    for it in range(int(max_iter)):
+        d_w_max = torch.zeros(N, dtype=torch.float64, device=G.device)
+        for k in coords:
+            tmp = g[k] + W[k] * diag[k]
+            if positive:
+                wn = torch.where(tmp < 0, torch.zeros_like(tmp), (tmp - a).clamp_min(0.0) / (diag[k] + b))
+            else:
+                wn = torch.sign(tmp) * (tmp.abs() - a).clamp_min(0.0) / (diag[k] + b)
+            delta = torch.where(done | eye[k], torch.zeros_like(tmp), wn - W[k])        # target k has no coordinate k
+            W[k] += delta
+            g.addr_(G[:, k], delta, alpha=-1.0)
+            d_w_max = torch.maximum(d_w_max, delta.abs())
+        w_max = W.abs().amax(0)
+        check = (w_max == 0) | (d_w_max / w_max < tol)
+        if it == max_iter - 1:
+            check = torch.ones_like(check)
+        gm = g.masked_fill(eye, 0.0)                                  # row j of target j belongs to the zeroed row of Q
+        q = G.masked_fill(eye, 0.0)
+        q_dot_w, w_h = (W * q).sum(0), (W * (q - gm)).sum(0)
+        xta = gm - b * W
+        dual = xta.amax(0) if positive else xta.abs().amax(0)
+        r2 = diag + w_h - 2.0 * q_dot_w
+        c = torch.where(dual > a, a / dual, torch.ones_like(dual))
+        gap = torch.where(dual > a, 0.5 * (r2 + r2 * c * c), r2)
+        gap = gap + (a * W.abs().sum(0) - c * diag + c * q_dot_w + 0.5 * b * (1.0 + c * c) * (W * W).sum(0))
+        stop = check & (gap < tol * diag) & ~done
+        n_iter[stop] = it + 1
+        done |= stop
+        if bool(done.all()):
+            break
+    W[:, 0] = 0.0
+    return W, n_iter
+
+
+class SLIM(EASE):
+    """recstudio/model/mf/slim.py, recstudio/model/mf/config/slim.yaml (alpha 1, l1_ratio 0.1, positive_only True, knn 100): Sparse
+    Linear Methods.  ``fit`` solves, once, one elastic-net problem per target item on the float64 Gram matrix of the train split --
+    sklearn's ``ElasticNet(precompute=True, fit_intercept=False, max_iter=100, tol=1e-4)`` rule, ``a = alpha l1_ratio U`` and
+    ``b = alpha (1 - l1_ratio) U`` with U the rows of R, the padding user included -- and keeps the non-zero weights as a sparse
+    item-item matrix; a user's score of item i is the sum of ``B[j, i]`` over the user's train items j.  The sparse matrix (by
+    neighbour: ``slim_indptr`` / ``slim_items`` / ``slim_w``) and the user-side CSR are buffers, so ``state_dict`` carries the fitted
+    model.  ``model.fused_slim``: ``ops.slim_fit`` / ``ops.knn_score``; off, ``slim_torch`` / ``itemknn_score_torch``.
+    ``train.knn`` is accepted and unused, as in the reference.  ONE deviation from the reference: a sweep visits the coordinates
+    in cyclic ascending order, where the reference asks for ``selection='random'`` driven by sklearn's private ``rand_r`` stream,
+    which cannot be followed; for b > 0 both orders converge to the same unique minimiser.  The weights are kept in fp32 for
+    scoring, as ItemKNN's similarities are."""
+
+    config_defaults = {'model': {'fused_slim': FUSED_SLIM_DEFAULT},
+                       'train': {'alpha': 1, 'l1_ratio': 0.1, 'positive_only': True, 'knn': 100, 'epochs': 1}}
+
+    def _update_item_vector(self):
+        pass                                                              # the "item vector" is the sparse weight matrix
+
+    def _get_item_vector(self):
+        raise NotImplementedError('SLIM: the item vector is the sparse matrix slim_indptr / slim_items / slim_w, not a dense one')
+
+    def _slim_build(self, train_data, device):
+        tr, fused = self.config['train'], self.config['model']['fused_slim']
+        if fused and not tr['positive_only']:
+            raise NotImplementedError('SLIM: model.fused_slim covers positive_only: True only (the candidate bound of rsa_slim_fit '
+                                      'rests on w >= 0); set fused_slim: False')
+        _, _, n_users, n_items, (u_indptr, u_items), (i_indptr, i_users) = _interaction_csrs(train_data, device, 'SLIM')
+        G = ops.ease_gram(u_indptr, u_items, i_indptr, i_users, 0.0)
+        if fused:
+            nbr_id, nbr_w, nbr_cnt, _ = ops.slim_fit(G, n_users, tr['alpha'], tr['l1_ratio'])
+        else:
+            B, _ = slim_torch(G, n_users, tr['alpha'], tr['l1_ratio'], tr['positive_only'])
+            live = (B != 0).T                                            # row j: the neighbours of target j, ascending
+            nbr_cnt = live.sum(1).to(torch.int32)
+            cap = max(1, int(nbr_cnt.max()))
+            rank = torch.cumsum(live, 1) - 1
+            tgt, nb = torch.nonzero(live, as_tuple=True)
+            nbr_id = torch.full((n_items, cap), -1, dtype=torch.int32, device=device)
+            nbr_w = torch.zeros(n_items, cap, dtype=torch.float64, device=device)
+            nbr_id[tgt, rank[tgt, nb]], nbr_w[tgt, rank[tgt, nb]] = nb.to(torch.int32), B[nb, tgt]
+        for name, t in zip(_SLIM_BUFFERS, ops.knn_transpose(nbr_id, nbr_w.float(), nbr_cnt) + (u_indptr, u_items)):
+            self.register_buffer(name, t)
+        return 0.0                                                        # slim.py: training_epoch returns 0
+
+    def load_state_dict(self, state_dict, strict=True):
+        for name in _SLIM_BUFFERS:                                       # a fresh model has no weights yet: take their shapes from the state
+            if name in state_dict:
+                self.register_buffer(name, torch.empty_like(state_dict[name]))
+        return BaseRetriever.load_state_dict(self, state_dict, strict)
+
+    def topk(self, batch, k, user_h=None, return_query=False):
+        """baseretriever.py:374-397 over the SLIM scores: top (k + |hist|), ids + 1, the history dropped, top k."""
+        users = (batch[self.fuid] if isinstance(batch, dict) else batch).to(self.slim_w.device)
+        n_items = self.slim_indptr.numel() - 1
+        score_fn = ops.knn_score if self.config['model']['fused_slim'] else itemknn_score_torch
+        scores = score_fn(users, self.user_indptr, self.user_items, self.slim_indptr, self.slim_items, self.slim_w, n_items)
+        kc = min(k + (user_h.size(1) if user_h is not None else 0), n_items - 1)
+        score, topk_items = ops.row_topk(scores, kc) if kc <= ops.FULLSCORE_MAX_K else torch.topk(scores, kc)
+        topk_items = topk_items + 1
+        if user_h is not None:
+            score, topk_items = ops.topk_mask_history(score, topk_items, user_h, min(k, kc))
+        return (score, topk_items, scores) if return_query else (score, topk_items)
+
+    def fit(self, train_data, val_data=None, run_mode='light', config=None, **kwargs):
+        if config is not None:
+            self.config.update(config)
+        if self._dist_context(kwargs) is not None:
+            raise NotImplementedError('SLIM: the sharded fit is not covered (the dense N x N Gram matrix lives on one device)')
+        self._init_model(train_data)
+        device = self._device()
+        self.to(device)
+        if val_data is not None:
+            val_data.use_field = train_data.use_field
+
+        def train_epoch():
+            return self._slim_build(train_data, device)
+
+        def validate():
+            t1 = time.time()
+            metrics = self._eval_epoch(val_data, self.validation_step, device)
+            return dict(metrics, valid_time=time.time() - t1)
+
+        return self._run_epochs(train_epoch, None, validate if val_data is not None else None, log=self.logger.info)
+
+    def evaluate(self, test_data, verbose=True, **kwargs):
+        test_data.use_field = self.fields
+        out = self._eval_epoch(test_data, self.test_step, self.slim_w.device)
+        if verbose:
+            self.logger.info(str(out))
+        return out

@@ -2552,3 +2552,55 @@ def ease_score(users, u_indptr, u_items, B):
     a.n_batch, a.n_users, a.n_items, a.ld = users.numel(), u_indptr.numel() - 1, N, B.stride(0)
     _launch('rsa_ease_score', ctypes.byref(a))
     return out
+
+
+# ------------------------------------------------------------------ SLIM: per-item elastic-net coordinate descent (float64)
+SLIM_WAVE_MAX = 64                # candidates one wave holds, one per lane (rsa_slim.hip)
+SLIM_MAX_CANDIDATES = 6784        # candidates the LDS of one workgroup holds at 24 bytes each (RSA_SLIM_MAX_CANDIDATES)
+
+
+@_on_device
+def slim_fit(G, n_rows, alpha, l1_ratio, *, max_iter=100, tol=1e-4, wave_max=None):
+    """rsa_slim_fit: the SLIM weights from the float64 Gram matrix ``G = R^T R`` [N, N] (``ease_gram(..., lam=0)``, read in place as
+    a symmetric matrix), ``n_rows`` the number of rows of R.  For every target item j >= 1, sklearn's Gram coordinate descent with
+    ``positive=True`` on ``1/2 w^T Q w - q^T w + a |w|_1 + b / 2 |w|^2`` (Q = G without row and column j, q = G[:, j] without j,
+    a = alpha l1_ratio n_rows, b = alpha (1 - l1_ratio) n_rows), in CYCLIC order, over the candidates ``G[k, j] > a`` (the rest
+    stays 0).  -> ``(nbr_id int32 [N, cap], nbr_w float64 [N, cap], nbr_cnt int32 [N], n_iter int32 [N])``: the non-zero weights of
+    column j by ascending id, unused slots (-1, 0); ``cap`` is the largest candidate count (at least 1).  ``wave_max``: the most
+    candidates of a target that one wave solves (default 64; 0: every target goes to the workgroup kernel).  Two runs are bit-equal."""
+    alpha, l1_ratio = float(alpha), float(l1_ratio)
+    if not (alpha > 0 and 0 <= l1_ratio < 1):
+        raise ValueError(f'slim_fit: alpha = {alpha} must be > 0 and l1_ratio = {l1_ratio} in [0, 1): at l1_ratio = 1 the quadratic '
+                         'term vanishes and the minimiser is not unique')
+    G = _f64_matrix(G, 'G')
+    N = G.size(0)
+    if G.size(1) != N or N < 2:
+        raise ValueError(f'slim_fit: G must be square with at least two items, got {tuple(G.shape)}')
+    wave_max = SLIM_WAVE_MAX if wave_max is None else int(wave_max)
+    if not 0 <= wave_max <= SLIM_WAVE_MAX:
+        raise ValueError(f'slim_fit: wave_max must be in 0 .. {SLIM_WAVE_MAX}, got {wave_max}')
+    a_, b_ = alpha * l1_ratio * int(n_rows), alpha * (1.0 - l1_ratio) * int(n_rows)
+    cand = G > a_
+    cand.fill_diagonal_(False)
+    cand[0], cand[:, 0] = False, False                            # the padding item is neither a target nor a neighbour
+    count = cand.sum(0)
+    cap = max(1, int(count.max()))
+    order = torch.sort(count[1:], descending=True, stable=True).indices + 1         # heaviest first, item 0 left out
+    n_group = int((count[1:] > wave_max).sum()) if wave_max > 0 else N - 1
+    if n_group and cap > SLIM_MAX_CANDIDATES:
+        raise ValueError(f'slim_fit: an item has {cap} candidates (G[k, j] > alpha * l1_ratio * U = {a_}); one workgroup holds at '
+                         f'most {SLIM_MAX_CANDIDATES}: raise alpha * l1_ratio * U')
+    order = order.to(torch.int32)
+    order_group, order_wave = order[:n_group].contiguous(), order[n_group:].contiguous()
+    dev = G.device
+    nbr_id = torch.full((N, cap), -1, dtype=torch.int32, device=dev)
+    nbr_w = torch.zeros(N, cap, dtype=torch.float64, device=dev)
+    nbr_cnt = torch.zeros(N, dtype=torch.int32, device=dev)
+    n_iter = torch.zeros(N, dtype=torch.int32, device=dev)
+    a = nat.SlimFitArgs()
+    a.g, a.order_wave, a.order_group = ptr(G), ptr(order_wave), ptr(order_group)
+    a.n_items, a.ld, a.n_wave, a.n_group = N, G.stride(0), order_wave.numel(), order_group.numel()
+    a.l1, a.l2, a.tol, a.max_iter, a.cap = a_, b_, float(tol), int(max_iter), cap
+    a.nbr_id, a.nbr_w, a.nbr_cnt, a.n_iter = ptr(nbr_id), ptr(nbr_w), ptr(nbr_cnt), ptr(n_iter)
+    _launch('rsa_slim_fit', ctypes.byref(a))
+    return nbr_id, nbr_w, nbr_cnt, n_iter

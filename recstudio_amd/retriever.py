@@ -1241,5 +1241,5 @@ from .models_seq import (CL4SRec, CaserQueryEncoder, GRU4Rec, GRU4RecQueryEncode
                          FUSED_GATING_DEFAULT, FUSED_INFONCE_DEFAULT)
 from .models_mf import (NCF, FUSED_SCORER_DEFAULT, WRMF, FUSED_ALS_DEFAULT, als_step_torch, ItemKNN,      # noqa: E402, F401
                         FUSED_KNN_DEFAULT, itemknn_torch, itemknn_score_torch, EASE, FUSED_EASE_DEFAULT, ease_torch,
-                        ease_score_torch)
+                        ease_score_torch, SLIM, FUSED_SLIM_DEFAULT, slim_torch)
 from .models_ae import MultiDAE, MultiDAEQueryEncoder, MultiVAE, MultiVAEQueryEncoder, FUSED_BAG_DEFAULT   # noqa: E402, F401
