@@ -1095,6 +1095,17 @@ typedef struct rsa_attention_args {
 } rsa_attention_args;
 int rsa_attention(const rsa_attention_args* args, rsa_stream_t stream);
 int rsa_attention_backward(const rsa_attention_args* args, rsa_stream_t stream);
+/* The same rule, argument block, masks, dropout indices and results for seq_len in [1, 1024] (head_dim 16, 32 or 64): blocks of
+ * 64 rows are streamed through LDS instead of one tile holding the sequence.  rsa_attention_stream is one launch of one workgroup
+ * per (sequence, head, block of 64 queries) that walks the key blocks with a running softmax (maximum, sum and the output
+ * accumulators rescaled block by block; out = o / l and lse = m + log l at the end), so out and lse differ from rsa_attention's in
+ * the last bits where both accept the length.  rsa_attention_stream_backward is two launches on the stream: one workgroup per
+ * block of 64 queries writes dq, one per block of 64 keys writes dk and dv; both recompute S and the mask from lse.  Causal calls
+ * skip the blocks above the diagonal (with `keep` asked for the forward visits them to write it).  No atomics, no workspace,
+ * nothing of size seq_len^2, two runs are bit-equal, every element of dqkv is written.  The refusals are rsa_attention's, with
+ * seq_len outside [1, 1024] and n_seq * n_head * ceil(seq_len / 64) >= 2^24 in place of its seq_len limit. */
+int rsa_attention_stream(const rsa_attention_args* args, rsa_stream_t stream);
+int rsa_attention_stream_backward(const rsa_attention_args* args, rsa_stream_t stream);
 
 /* The GRU recurrence of the sequence towers (GRU4Rec, NARM), fused: the SEQUENTIAL part of torch.nn.GRU (one layer, one
  * direction, batch_first) as the reference's module.GRULayer runs it (recstudio/model/seq/gru4rec.py).  Gate order r, z, n:

@@ -553,6 +553,8 @@ SIGNATURES = {
     'rsa_pair_mlp_backward': (c_int, [POINTER(PairMlpArgs), c_void_p]),
     'rsa_attention': (c_int, [POINTER(AttentionArgs), c_void_p]),
     'rsa_attention_backward': (c_int, [POINTER(AttentionArgs), c_void_p]),
+    'rsa_attention_stream': (c_int, [POINTER(AttentionArgs), c_void_p]),
+    'rsa_attention_stream_backward': (c_int, [POINTER(AttentionArgs), c_void_p]),
     'rsa_gru': (c_int, [POINTER(GruArgs), c_void_p]),
     'rsa_gru_backward': (c_int, [POINTER(GruArgs), c_void_p]),
     'rsa_ff_attention_workspace_bytes': (c_int64, [c_int64, c_int32, c_int32, c_int32]),

@@ -10,6 +10,9 @@
 // head h in columns h dh .. (h + 1) dh of each.  No head-major copy, and nothing of size L x L ever reaches memory (the test-only
 // `keep` aside).
 //
+// rsa_attention_stream / rsa_attention_stream_backward : the same rule for L up to 1024, 64-row blocks streamed through LDS ("THE
+//                                          STREAMING KERNELS" below); everything up to there describes the one-tile pair
+//
 // TILE.  L <= 64 fits one tile: LT = 16, 32 or 64 (the smallest that holds L) x dh = 16, 32 or 64 are template arguments.  A wave
 // owns a block of 16 queries (and, in the second pass of the backward, 16 keys); a (b, h) problem is LT / 16 waves and a
 // 256-thread workgroup holds 4, 2 or 1 problems -- an L = 9 batch pays for a 16 x 16 tile, not a 64 x 64 one.  One workgroup per
@@ -337,13 +340,334 @@ __global__ __launch_bounds__(256) void sa_backward_kernel(const SaParams p) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ THE STREAMING KERNELS
+// rsa_attention_stream / rsa_attention_stream_backward: the same rule for L up to SAS_MAX_L, in blocks of 64 rows.  One 256-thread
+// workgroup per (problem, block): blockIdx.x = pr * nblk + block.  The block the workgroup owns is staged once; the blocks it
+// meets pass through ONE LDS buffer: `sas_load` takes the next block from memory into registers (DH / 16 float4 per thread and
+// matrix) BEFORE the products of the current one, `sas_store` puts it down between the two barriers that follow them.
+//   forward   owns 64 queries (wave w: 16 of them), streams K and V.  Running softmax per query, the state (m, l) replicated over
+//             the four lanes of the query: m' = max(m, block max), alpha = exp(m - m') (0 while m = -inf), l = l alpha + sum e,
+//             o = o alpha + V^T (keep e / q)^T; at the end out = o / l, lse = m + log l.  alpha is one scalar per lane.
+//   dq grid   owns 64 queries with G, lse and D, streams K and V: pass 1 of the one-tile backward per block, dq in registers.
+//   dkv grid  owns 64 keys (K and V), streams Q, G (with D computed from `out` on the way down) and lse: pass 2 per block.
+// Causal: a query block meets key blocks 0 .. its own, a key block the query blocks from its own on; in the diagonal block the
+// waves skip the 16-row sub-blocks above the diagonal.  With `keep` asked for (tests) the forward visits every block, so that
+// every element of `keep` is written.  LDS: forward 3 tiles of 64 (dh + 4) floats = 15 / 27 / 51 KB, both backward grids 4 tiles
+// + 128 floats = 20.5 / 36.5 / 68.5 KB.
+constexpr int SAS_MAX_L = 1024;
+
+template <int DH>
+__device__ __forceinline__ void sas_load(const float* src, int64_t stride, int row0, int L, float4 (&v)[DH / 16]) {
+  constexpr int P4 = DH / 4;
+#pragma unroll
+  for (int t = 0; t < DH / 16; ++t) {
+    const int idx = (int)threadIdx.x + t * 256, row = row0 + idx / P4, c = (idx % P4) * 4;
+    v[t] = row < L ? *reinterpret_cast<const float4*>(src + (int64_t)row * stride + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+template <int DH>
+__device__ __forceinline__ void sas_store(float* dst, const float4 (&v)[DH / 16]) {
+  constexpr int P4 = DH / 4, LD = DH + 4;
+#pragma unroll
+  for (int t = 0; t < DH / 16; ++t) {
+    const int idx = (int)threadIdx.x + t * 256;
+    *reinterpret_cast<float4*>(dst + (idx / P4) * LD + (idx % P4) * 4) = v[t];
+  }
+}
+
+// whether key 64 blk + lane of sequence b exists and is not padded (the lane's bit of the block's ballot)
+__device__ __forceinline__ bool sas_key_ok(const SaParams& p, int64_t b, int blk, int lane) {
+  const int j = blk * 64 + lane;
+  return j < p.L && !(p.key_pad && p.key_pad[b * p.L + j]);
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void sas_forward_kernel(const SaParams p, const int nblk) {
+  constexpr int NCB = DH / 16, LD = DH + 4, TILE = 64 * LD;
+  const int lane = lane_id(), wave = threadIdx.x >> 6, j16 = lane & 15, g = lane >> 4;
+  const int64_t pr = blockIdx.x / nblk;
+  const int qb = nblk - 1 - (int)(blockIdx.x - pr * nblk);      // (causal: the long query blocks start first)
+  const int64_t b = pr / p.H;
+  const int h = (int)(pr - b * p.H);
+  float* qs = sa_smem;
+  float* ks = qs + TILE;
+  float* vs = ks + TILE;
+  const int64_t ld3 = 3 * (int64_t)p.D;
+  const float* src = p.qkv + b * p.L * ld3 + h * DH;
+  const int kb_end = p.causal && !p.keep ? qb + 1 : nblk;
+  float4 kr[DH / 16], vr[DH / 16];
+  sa_stage<64, DH>(src + (int64_t)qb * 64 * ld3, ld3, p.L - qb * 64, qs, threadIdx.x, 256);
+  sas_load<DH>(src + p.D, ld3, 0, p.L, kr);
+  sas_load<DH>(src + 2 * p.D, ld3, 0, p.L, vr);
+  bool ok_next = sas_key_ok(p, b, 0, lane);
+  const int il = wave * 16 + j16, i = qb * 64 + il;
+  const bool i_ok = i < p.L;
+  float m = -INFINITY, l = 0.f;
+  f32x4 o[NCB];
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) o[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kb = 0; kb < kb_end; ++kb) {
+    if (kb) __syncthreads();                                    // every wave is done with block kb - 1
+    sas_store<DH>(ks, kr);
+    sas_store<DH>(vs, vr);
+    const uint64_t kmask = __ballot(ok_next);
+    __syncthreads();
+    if (kb + 1 < kb_end) {
+      sas_load<DH>(src + p.D, ld3, (kb + 1) * 64, p.L, kr);
+      sas_load<DH>(src + 2 * p.D, ld3, (kb + 1) * 64, p.L, vr);
+      ok_next = sas_key_ok(p, b, kb + 1, lane);
+    }
+    const int jb_end = !p.causal || kb < qb ? 4 : (kb == qb ? wave + 1 : 0);
+    f32x4 s[4];
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+      if (jb < jb_end) s[jb] = sa_dot<DH>(ks + (jb * 16 + j16) * LD, qs + il * LD, g);
+    float bm = -INFINITY;
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int jl = jb * 16 + 4 * g + r;
+        const bool ok = jb < jb_end && ((kmask >> jl) & 1) && (!p.causal || kb * 64 + jl <= i);
+        const float sv = ok ? s[jb][r] * p.scale : -INFINITY;
+        s[jb][r] = sv;
+        bm = fmaxf(bm, sv);
+      }
+    bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    const float m_new = fmaxf(m, bm);
+    const float alpha = m == -INFINITY ? 0.f : expf(m - m_new);
+    float sum = 0.f;
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = s[jb][r] == -INFINITY ? 0.f : expf(s[jb][r] - m_new);
+        s[jb][r] = e;
+        sum += e;
+      }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    l = l * alpha + sum;
+    m = m_new;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) o[cb] *= alpha;
+    // ---- keep e / q, in place
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = kb * 64 + jb * 16 + 4 * g + r;
+        float e = s[jb][r];
+        if (i_ok && j < p.L && (e != 0.f || p.keep)) {
+          const bool kept = sa_kept(p, pr, i, j);
+          if (p.drop) e = kept ? e / p.q : 0.f;
+          if (p.keep) p.keep[(pr * p.L + i) * p.L + j] = kept ? 1 : 0;
+        }
+        s[jb][r] = e;
+      }
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+      if (jb < jb_end) sa_acc<DH>(vs + jb * 16 * LD, s[jb], o, j16, g);
+  }
+  if (i_ok) {
+    float* dst = p.out + (b * p.L + i) * (int64_t)p.D + h * DH + 4 * g;
+    const bool some = l > 0.f;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+      *reinterpret_cast<float4*>(dst + cb * 16) =
+          some ? make_float4(o[cb][0] / l, o[cb][1] / l, o[cb][2] / l, o[cb][3] / l) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g == 0) p.lse[pr * p.L + i] = some ? m + logf(l) : -INFINITY;
+  }
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void sas_dq_kernel(const SaParams p, const int nblk) {
+  constexpr int NCB = DH / 16, LD = DH + 4, TILE = 64 * LD, P4 = DH / 4;
+  const int lane = lane_id(), wave = threadIdx.x >> 6, j16 = lane & 15, g = lane >> 4;
+  const int64_t pr = blockIdx.x / nblk;
+  const int qb = nblk - 1 - (int)(blockIdx.x - pr * nblk);
+  const int64_t b = pr / p.H;
+  const int h = (int)(pr - b * p.H);
+  float* qs = sa_smem;
+  float* gs = qs + TILE;
+  float* ks = gs + TILE;
+  float* vs = ks + TILE;
+  float* lse_s = vs + TILE;
+  float* d_s = lse_s + 64;
+  const int64_t ld3 = 3 * (int64_t)p.D;
+  const float* src = p.qkv + b * p.L * ld3 + h * DH;
+  const int kb_end = p.causal ? qb + 1 : nblk;
+  float4 kr[DH / 16], vr[DH / 16];
+  sa_stage<64, DH>(src + (int64_t)qb * 64 * ld3, ld3, p.L - qb * 64, qs, threadIdx.x, 256);
+  {
+    // G, and D_i = <g_i, out_i>: a row is P4 consecutive lanes (every lane makes every trip)
+    float4 gr[DH / 16], orr[DH / 16];
+    sas_load<DH>(p.g + b * p.L * (int64_t)p.D + h * DH, p.D, qb * 64, p.L, gr);
+    sas_load<DH>(p.out + b * p.L * (int64_t)p.D + h * DH, p.D, qb * 64, p.L, orr);
+    sas_store<DH>(gs, gr);
+#pragma unroll
+    for (int t = 0; t < DH / 16; ++t) {
+      const int idx = (int)threadIdx.x + t * 256;
+      const float di = group_sum<P4>((gr[t].x * orr[t].x + gr[t].y * orr[t].y) + (gr[t].z * orr[t].z + gr[t].w * orr[t].w));
+      if (idx % P4 == 0) d_s[idx / P4] = di;
+    }
+    if (threadIdx.x < 64) lse_s[threadIdx.x] = qb * 64 + (int)threadIdx.x < p.L ? p.lse[pr * p.L + qb * 64 + threadIdx.x] : INFINITY;
+  }
+  sas_load<DH>(src + p.D, ld3, 0, p.L, kr);
+  sas_load<DH>(src + 2 * p.D, ld3, 0, p.L, vr);
+  bool ok_next = sas_key_ok(p, b, 0, lane);
+  const int il = wave * 16 + j16, i = qb * 64 + il;
+  const bool i_ok = i < p.L;
+  f32x4 dq[NCB];
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) dq[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kb = 0; kb < kb_end; ++kb) {
+    if (kb) __syncthreads();
+    sas_store<DH>(ks, kr);
+    sas_store<DH>(vs, vr);
+    const uint64_t kmask = __ballot(ok_next);
+    __syncthreads();
+    if (kb + 1 < kb_end) {
+      sas_load<DH>(src + p.D, ld3, (kb + 1) * 64, p.L, kr);
+      sas_load<DH>(src + 2 * p.D, ld3, (kb + 1) * 64, p.L, vr);
+      ok_next = sas_key_ok(p, b, kb + 1, lane);
+    }
+    const float lse_i = lse_s[il], d_i = d_s[il];
+    const int jb_end = !p.causal || kb < qb ? 4 : wave + 1;
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+      if (jb >= jb_end) continue;
+      const f32x4 sv = sa_dot<DH>(ks + (jb * 16 + j16) * LD, qs + il * LD, g);
+      const f32x4 dp = sa_dot<DH>(vs + (jb * 16 + j16) * LD, gs + il * LD, g);
+      f32x4 ds;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int jl = jb * 16 + 4 * g + r, j = kb * 64 + jl;
+        const bool ok = i_ok && ((kmask >> jl) & 1) && (!p.causal || j <= i);
+        float v = 0.f;
+        if (ok) {
+          const float pv = expf(sv[r] * p.scale - lse_i);
+          float dpv = dp[r];
+          if (p.drop) dpv = sa_kept(p, pr, i, j) ? dpv / p.q : 0.f;
+          v = pv * (dpv - d_i);
+        }
+        ds[r] = v;
+      }
+      sa_acc<DH>(ks + jb * 16 * LD, ds, dq, j16, g);
+    }
+  }
+  if (i_ok) {
+    float* dst = p.dqkv + (b * p.L + i) * ld3 + h * DH + 4 * g;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+      *reinterpret_cast<float4*>(dst + cb * 16) =
+          make_float4(dq[cb][0] * p.scale, dq[cb][1] * p.scale, dq[cb][2] * p.scale, dq[cb][3] * p.scale);
+  }
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void sas_dkv_kernel(const SaParams p, const int nblk) {
+  constexpr int NCB = DH / 16, LD = DH + 4, TILE = 64 * LD, P4 = DH / 4;
+  const int lane = lane_id(), wave = threadIdx.x >> 6, j16 = lane & 15, g = lane >> 4;
+  const int64_t pr = blockIdx.x / nblk;
+  const int kb = (int)(blockIdx.x - pr * nblk);                 // (causal: the key blocks that meet most queries start first)
+  const int64_t b = pr / p.H;
+  const int h = (int)(pr - b * p.H);
+  float* ks = sa_smem;
+  float* vs = ks + TILE;
+  float* qs = vs + TILE;
+  float* gs = qs + TILE;
+  float* lse_s = gs + TILE;
+  float* d_s = lse_s + 64;
+  const int64_t ld3 = 3 * (int64_t)p.D;
+  const float* src = p.qkv + b * p.L * ld3 + h * DH;
+  const float* gsrc = p.g + b * p.L * (int64_t)p.D + h * DH;
+  const float* osrc = p.out + b * p.L * (int64_t)p.D + h * DH;
+  const int ib0 = p.causal ? kb : 0;
+  float4 qr[DH / 16], gr[DH / 16], orr[DH / 16];
+  float lse_next = INFINITY;
+  const auto fetch = [&](int ib) {
+    sas_load<DH>(src, ld3, ib * 64, p.L, qr);
+    sas_load<DH>(gsrc, p.D, ib * 64, p.L, gr);
+    sas_load<DH>(osrc, p.D, ib * 64, p.L, orr);
+    const int row = ib * 64 + lane;                             // (wave 0 puts it down)
+    lse_next = row < p.L ? p.lse[pr * p.L + row] : INFINITY;
+  };
+  sa_stage<64, DH>(src + p.D + (int64_t)kb * 64 * ld3, ld3, p.L - kb * 64, ks, threadIdx.x, 256);
+  sa_stage<64, DH>(src + 2 * p.D + (int64_t)kb * 64 * ld3, ld3, p.L - kb * 64, vs, threadIdx.x, 256);
+  const uint64_t kmask = __ballot(sas_key_ok(p, b, kb, lane));
+  fetch(ib0);
+  const int jl = wave * 16 + j16, j = kb * 64 + jl;
+  const bool j_ok = (kmask >> jl) & 1;
+  f32x4 dk[NCB], dv[NCB];
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) dk[cb] = dv[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ib = ib0; ib < nblk; ++ib) {
+    if (ib > ib0) __syncthreads();
+    sas_store<DH>(qs, qr);
+    sas_store<DH>(gs, gr);
+#pragma unroll
+    for (int t = 0; t < DH / 16; ++t) {
+      const int idx = (int)threadIdx.x + t * 256;
+      const float di = group_sum<P4>((gr[t].x * orr[t].x + gr[t].y * orr[t].y) + (gr[t].z * orr[t].z + gr[t].w * orr[t].w));
+      if (idx % P4 == 0) d_s[idx / P4] = di;
+    }
+    if (wave == 0) lse_s[lane] = lse_next;
+    __syncthreads();
+    if (ib + 1 < nblk) fetch(ib + 1);
+    const int sb0 = p.causal && ib == kb ? wave : 0;
+#pragma unroll
+    for (int sb = 0; sb < 4; ++sb) {
+      if (sb < sb0) continue;
+      const f32x4 sv = sa_dot<DH>(qs + (sb * 16 + j16) * LD, ks + jl * LD, g);
+      const f32x4 dp = sa_dot<DH>(gs + (sb * 16 + j16) * LD, vs + jl * LD, g);
+      const float4 lse4 = *reinterpret_cast<const float4*>(lse_s + sb * 16 + 4 * g);
+      const float4 d4 = *reinterpret_cast<const float4*>(d_s + sb * 16 + 4 * g);
+      const float lse_r[4] = {lse4.x, lse4.y, lse4.z, lse4.w}, d_r[4] = {d4.x, d4.y, d4.z, d4.w};
+      f32x4 ds, pt;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = ib * 64 + sb * 16 + 4 * g + r;
+        const bool ok = j_ok && i < p.L && (!p.causal || j <= i);
+        float v = 0.f, w = 0.f;
+        if (ok) {
+          const float pv = expf(sv[r] * p.scale - lse_r[r]);
+          float dpv = dp[r];
+          w = pv;
+          if (p.drop) {
+            const bool kept = sa_kept(p, pr, i, j);
+            dpv = kept ? dpv / p.q : 0.f;
+            w = kept ? pv / p.q : 0.f;
+          }
+          v = pv * (dpv - d_r[r]);
+        }
+        ds[r] = v;
+        pt[r] = w;
+      }
+      sa_acc<DH>(qs + sb * 16 * LD, ds, dk, j16, g);
+      sa_acc<DH>(gs + sb * 16 * LD, pt, dv, j16, g);
+    }
+  }
+  if (j < p.L) {
+    float* dst = p.dqkv + (b * p.L + j) * ld3 + p.D + h * DH + 4 * g;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      *reinterpret_cast<float4*>(dst + cb * 16) =
+          make_float4(dk[cb][0] * p.scale, dk[cb][1] * p.scale, dk[cb][2] * p.scale, dk[cb][3] * p.scale);
+      *reinterpret_cast<float4*>(dst + p.D + cb * 16) = make_float4(dv[cb][0], dv[cb][1], dv[cb][2], dv[cb][3]);
+    }
+  }
+}
+
 static inline int sa_tile(int L) { return L <= 16 ? 16 : (L <= 32 ? 32 : 64); }
 
 // the checks both entry points share; fills the shared part of `p`
-static int sa_check(const rsa_attention_args& a, const char* fn, SaParams& p) {
+static int sa_check(const rsa_attention_args& a, const char* fn, SaParams& p, int max_l = SA_MAX_L,
+                    const char* why = "one tile holds the sequence") {
   RSA_CHECK_ARG(a.n_seq >= 0, "%s: negative n_seq %lld", fn, (long long)a.n_seq);
-  RSA_CHECK_ARG(a.seq_len >= 1 && a.seq_len <= SA_MAX_L, "%s: seq_len must lie in [1, %d] (one tile holds the sequence), got %d", fn,
-                SA_MAX_L, a.seq_len);
+  RSA_CHECK_ARG(a.seq_len >= 1 && a.seq_len <= max_l, "%s: seq_len must lie in [1, %d] (%s), got %d", fn, max_l, why, a.seq_len);
   RSA_CHECK_ARG(a.head_dim == 16 || a.head_dim == 32 || a.head_dim == 64, "%s: head_dim must be 16, 32 or 64, got %d", fn, a.head_dim);
   RSA_CHECK_ARG(a.n_head >= 1 && (int64_t)a.n_head * a.head_dim < (1ll << 29), "%s: bad n_head %d", fn, a.n_head);
   RSA_CHECK_ARG(std::isfinite(a.scale), "%s: scale must be finite", fn);
@@ -422,6 +746,59 @@ extern "C" int rsa_attention_backward(const rsa_attention_args* args, rsa_stream
     if (rc == RSA_OK)
       hipLaunchKernelGGL((sa_backward_kernel<LT(), DH()>), dim3((unsigned)((p.n_prob + ppw - 1) / ppw)), dim3(256), (size_t)lds,
                          (hipStream_t)stream, p);
+  });
+  if (rc) return rc;
+  RSA_CHECK_LAUNCH(fn);
+  return RSA_OK;
+}
+
+// the checks of the streaming pair: sa_check with the longer limit, and one workgroup per (problem, block of 64) in a 1-D grid
+static int sas_check(const rsa_attention_args& a, const char* fn, SaParams& p, int& nblk) {
+  if (int rc = sa_check(a, fn, p, SAS_MAX_L, "blocks of 64 are streamed")) return rc;
+  nblk = (a.seq_len + 63) / 64;
+  RSA_CHECK_ARG(a.n_seq * a.n_head * nblk < (1ll << 24),
+                "%s: n_seq * n_head * ceil(seq_len / 64) = %lld workgroups: one launch takes fewer than 2^24 (2^32 threads)", fn,
+                (long long)(a.n_seq * a.n_head * nblk));
+  return RSA_OK;
+}
+
+extern "C" int rsa_attention_stream(const rsa_attention_args* args, rsa_stream_t stream) {
+  const char* fn = "rsa_attention_stream";
+  rsa_attention_args a;
+  if (int rc = load_args(a, args, fn)) return rc;
+  SaParams p{};
+  int nblk = 0;
+  if (int rc = sas_check(a, fn, p, nblk)) return rc;
+  if (a.n_seq == 0) return RSA_OK;
+  p.keep = a.keep;
+  dispatch_dim<16, 32, 64>(a.head_dim, [&](auto DH) {
+    hipLaunchKernelGGL((sas_forward_kernel<DH()>), dim3((unsigned)(p.n_prob * nblk)), dim3(256), (size_t)(3 * 64 * (DH() + 4) * 4),
+                       (hipStream_t)stream, p, nblk);
+  });
+  RSA_CHECK_LAUNCH(fn);
+  return RSA_OK;
+}
+
+extern "C" int rsa_attention_stream_backward(const rsa_attention_args* args, rsa_stream_t stream) {
+  const char* fn = "rsa_attention_stream_backward";
+  rsa_attention_args a;
+  if (int rc = load_args(a, args, fn)) return rc;
+  SaParams p{};
+  int nblk = 0;
+  if (int rc = sas_check(a, fn, p, nblk)) return rc;
+  if (a.n_seq == 0) return RSA_OK;
+  RSA_CHECK_ARG(a.g_out && a.dqkv, "%s: g_out or dqkv is null", fn);
+  RSA_CHECK_ARG((((uintptr_t)a.g_out | (uintptr_t)a.dqkv) & 15) == 0, "%s: g_out and dqkv must be 16-byte aligned", fn);
+  p.g = a.g_out, p.dqkv = a.dqkv;
+  int rc = RSA_OK;
+  dispatch_dim<16, 32, 64>(a.head_dim, [&](auto DH) {
+    const int64_t lds = (4 * 64 * (DH() + 4) + 128) * 4;
+    const dim3 grid((unsigned)(p.n_prob * nblk));
+    rc = allow_lds<sas_dq_kernel<DH()>>(lds, fn);
+    if (rc == RSA_OK) rc = allow_lds<sas_dkv_kernel<DH()>>(lds, fn);
+    if (rc != RSA_OK) return;
+    hipLaunchKernelGGL((sas_dq_kernel<DH()>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, p, nblk);
+    hipLaunchKernelGGL((sas_dkv_kernel<DH()>), grid, dim3(256), (size_t)lds, (hipStream_t)stream, p, nblk);
   });
   if (rc) return rc;
   RSA_CHECK_LAUNCH(fn);

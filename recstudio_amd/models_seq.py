@@ -4,7 +4,7 @@ import math
 
 import torch
 
-from . import data_augmentation
+from . import data_augmentation, ops
 from .dataset import SeqDataset
 from .gather import _history_rows, _last_position
 from .loss_func import BinaryCrossEntropyLoss, BPRLoss, SoftmaxLoss
@@ -39,7 +39,8 @@ class SASRecQueryEncoder(torch.nn.Module):
     """recstudio/model/seq/sasrec.py:8-67: item-embedding gather of the history (HIP) + learned positions
     + nn.TransformerEncoder (causal unless ``bidirectional``) + last-position pooling.  The encoder is stock PyTorch-ROCm by
     default; with ``fused_attention`` its layers run through ``seqmodule.FusedTransformerEncoder`` (the attention core as one
-    HIP kernel) over the same parameters: ``state_dict`` is the same either way.
+    HIP kernel; ``max_seq_len`` above ``ops.SEQ_ATTENTION_MAX_LEN``, up to ``ops.SEQ_ATTENTION_STREAM_MAX_LEN``: the streaming
+    kernels) over the same parameters: ``state_dict`` is the same either way.
 
     ``need_pooling=False`` returns the tower's ``[B, L, D]`` (what CL4SRec's views are mean-pooled from).  With ``mask_id`` (CL4SRec:
     ``num_items``) the encoder owns ``mask_emb`` [1, D], the row of the mask token: the ids
@@ -65,7 +66,8 @@ class SASRecQueryEncoder(torch.nn.Module):
         self.transformer_layer = torch.nn.TransformerEncoder(layer, num_layers=n_layer)
         self.dropout = torch.nn.Dropout(p=dropout)
         # (no parameters of its own: it reads transformer_layer's at call time)
-        self._fused = FusedTransformerEncoder(self.transformer_layer, max_seq_len) if self.fused_attention else None
+        self._fused = FusedTransformerEncoder(self.transformer_layer, max_seq_len,
+                                              stream=max_seq_len > ops.SEQ_ATTENTION_MAX_LEN) if self.fused_attention else None
 
     def forward(self, batch, need_pooling=True):
         user_hist = batch['in_' + self.fiid]

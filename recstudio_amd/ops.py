@@ -1788,10 +1788,11 @@ def pair_mlp_backward(query, table, ids, w1, b1, w2, b2, w_h, g, *, w_mf=None, b
 
 # ------------------------------------------------------------------ the attention core of the sequence towers
 SEQ_ATTENTION_MAX_LEN = 64             # one tile holds the sequence (rsa_attention.hip, "TILE")
+SEQ_ATTENTION_STREAM_MAX_LEN = 1024    # blocks of 64 are streamed (rsa_attention.hip, "THE STREAMING KERNELS")
 SEQ_ATTENTION_HEAD_DIMS = (16, 32, 64)
 
 
-def _seq_attention_args(who, qkv, key_pad, n_head, causal, scale, p, philox):
+def _seq_attention_args(who, qkv, key_pad, n_head, causal, scale, p, philox, max_len=SEQ_ATTENTION_MAX_LEN):
     qkv = _need(qkv, torch.float32, 'qkv')
     n_head = int(n_head)
     if qkv.dim() != 3 or n_head < 1 or qkv.shape[2] % (3 * n_head):
@@ -1801,8 +1802,9 @@ def _seq_attention_args(who, qkv, key_pad, n_head, causal, scale, p, philox):
     dh = D // n_head
     if dh not in SEQ_ATTENTION_HEAD_DIMS:
         raise ValueError(f'{who}: head_dim must be one of {SEQ_ATTENTION_HEAD_DIMS}, got {dh}')
-    if not 1 <= L <= SEQ_ATTENTION_MAX_LEN:
-        raise ValueError(f'{who}: the sequence length must lie in [1, {SEQ_ATTENTION_MAX_LEN}] (one tile holds it), got {L}')
+    if not 1 <= L <= max_len:
+        why = 'one tile holds it' if max_len == SEQ_ATTENTION_MAX_LEN else 'blocks of 64 are streamed'
+        raise ValueError(f'{who}: the sequence length must lie in [1, {max_len}] ({why}), got {L}')
     if key_pad is not None:
         if key_pad.dtype == torch.bool:
             key_pad = key_pad.view(torch.uint8) if key_pad.is_contiguous() else key_pad.contiguous().view(torch.uint8)
@@ -1841,13 +1843,18 @@ def seq_attention(qkv, key_pad, n_head, *, causal=True, scale=None, p=0.0, philo
     Dropout with probability ``p``: with q = fp32(1 - p), element (b, h, i, j) is kept iff ``u[b, h, i, j] < q``, ``u`` =
     ``torch.rand(B, n_head, L, L)`` in the generator state ``philox`` (``rng.reserve(B * n_head * L * L, 4, device)``) was reserved
     in.  ``p == 0`` takes no ``philox``."""
-    a, keepalive, B, L, D = _seq_attention_args('seq_attention', qkv, key_pad, n_head, causal, scale, p, philox)
+    return _seq_attention_forward('rsa_attention', 'seq_attention', SEQ_ATTENTION_MAX_LEN, qkv, key_pad, n_head, causal, scale, p,
+                                  philox, want_keep)
+
+
+def _seq_attention_forward(entry, who, max_len, qkv, key_pad, n_head, causal, scale, p, philox, want_keep):
+    a, keepalive, B, L, D = _seq_attention_args(who, qkv, key_pad, n_head, causal, scale, p, philox, max_len)
     dev = keepalive[0].device
     out = torch.empty(B, L, D, dtype=torch.float32, device=dev)
     lse = torch.empty(B, a.n_head, L, dtype=torch.float32, device=dev)
     keep = torch.empty(B, a.n_head, L, L, dtype=torch.uint8, device=dev) if want_keep else None
     a.out, a.lse, a.keep = ptr(out), ptr(lse), ptr(keep)
-    _launch('rsa_attention', ctypes.byref(a))
+    _launch(entry, ctypes.byref(a))
     return (out, lse) + ((keep,) if want_keep else ())
 
 
@@ -1856,15 +1863,37 @@ def seq_attention_backward(qkv, key_pad, n_head, out, lse, g_out, *, causal=True
     """rsa_attention_backward: ``dqkv`` [B, L, 3 D] of ``seq_attention`` from ``g_out`` (the gradient of ``out``), the forward's
     ``out`` and ``lse`` and the Philox state the forward was given.  The scores and the mask are recomputed; every element is
     written (zeros where nothing flows).  No atomics; bit-equal from run to run."""
-    a, keepalive, B, L, D = _seq_attention_args('seq_attention_backward', qkv, key_pad, n_head, causal, scale, p, philox)
+    return _seq_attention_backward('rsa_attention_backward', 'seq_attention_backward', SEQ_ATTENTION_MAX_LEN, qkv, key_pad, n_head,
+                                   out, lse, g_out, causal, scale, p, philox)
+
+
+def _seq_attention_backward(entry, who, max_len, qkv, key_pad, n_head, out, lse, g_out, causal, scale, p, philox):
+    a, keepalive, B, L, D = _seq_attention_args(who, qkv, key_pad, n_head, causal, scale, p, philox, max_len)
     out, lse, g_out = _need(out, torch.float32, 'out'), _need(lse, torch.float32, 'lse'), _need(g_out, torch.float32, 'g_out')
     if tuple(out.shape) != (B, L, D) or tuple(g_out.shape) != (B, L, D) or tuple(lse.shape) != (B, a.n_head, L):
-        raise ValueError(f'seq_attention_backward: out and g_out must be [{B}, {L}, {D}] and lse [{B}, {a.n_head}, {L}], got '
+        raise ValueError(f'{who}: out and g_out must be [{B}, {L}, {D}] and lse [{B}, {a.n_head}, {L}], got '
                          f'{tuple(out.shape)}, {tuple(g_out.shape)}, {tuple(lse.shape)}')
     dqkv = torch.empty(B, L, 3 * D, dtype=torch.float32, device=out.device)
     a.out, a.lse, a.g_out, a.dqkv = ptr(out), ptr(lse), ptr(g_out), ptr(dqkv)
-    _launch('rsa_attention_backward', ctypes.byref(a))
+    _launch(entry, ctypes.byref(a))
     return dqkv
+
+
+@_on_device
+def seq_attention_stream(qkv, key_pad, n_head, *, causal=True, scale=None, p=0.0, philox=None, want_keep=False):
+    """rsa_attention_stream: ``seq_attention`` for L up to ``SEQ_ATTENTION_STREAM_MAX_LEN`` -- the same arguments, rule, dropout
+    indices and returns; blocks of 64 keys are streamed under a running softmax, so ``out`` and ``lse`` differ from
+    ``seq_attention`` 's in the last bits where both take the length."""
+    return _seq_attention_forward('rsa_attention_stream', 'seq_attention_stream', SEQ_ATTENTION_STREAM_MAX_LEN, qkv, key_pad, n_head,
+                                  causal, scale, p, philox, want_keep)
+
+
+@_on_device
+def seq_attention_stream_backward(qkv, key_pad, n_head, out, lse, g_out, *, causal=True, scale=None, p=0.0, philox=None):
+    """rsa_attention_stream_backward: ``dqkv`` [B, L, 3 D] of ``seq_attention_stream``, as ``seq_attention_backward`` returns it
+    (two launches: dq per block of 64 queries, dk and dv per block of 64 keys).  No atomics; bit-equal from run to run."""
+    return _seq_attention_backward('rsa_attention_stream_backward', 'seq_attention_stream_backward', SEQ_ATTENTION_STREAM_MAX_LEN, qkv,
+                                   key_pad, n_head, out, lse, g_out, causal, scale, p, philox)
 
 
 # ------------------------------------------------------------------ the GRU recurrence of the sequence towers

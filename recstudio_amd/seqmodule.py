@@ -5,7 +5,8 @@ recstudio/model/seq/sasrec.py:19-33 builds the tower from ``torch.nn.Transformer
 with a bool causal mask and a key-padding mask (:44-53).  ``FusedTransformerEncoder`` runs the same layers over the SAME
 parameters -- the ``nn.TransformerEncoder`` stays the parameter container, so ``state_dict`` keys are the reference's -- with what
 ``nn.MultiheadAttention`` does between ``in_proj`` and ``out_proj`` replaced by ``ops.seq_attention`` (``rsa_attention``,
-recstudio_amd/csrc/rsa_attention.hip): no head-major copies, no ``[B, H, L, L]`` tensor.  The Linears, LayerNorms, the
+recstudio_amd/csrc/rsa_attention.hip; histories longer than 64: ``ops.seq_attention_stream``, ``rsa_attention_stream``, which
+streams blocks of 64 keys under a running softmax): no head-major copies, no ``[B, H, L, L]`` tensor.  The Linears, LayerNorms, the
 activation and the three ``nn.Dropout`` s of a layer stay torch ops.
 
 THE MASK RULE.  Key j is allowed for query i iff ``(not causal or j <= i) and not key_pad[b, j]`` -- what torch's merged float
@@ -124,15 +125,16 @@ def seq_attention_torch(qkv, key_pad, causal, H, p=0.0, generator=None, want_kee
 
 
 class _SeqAttentionFn(torch.autograd.Function):
-    """``ops.seq_attention`` / ``ops.seq_attention_backward`` as one autograd node.  Saved: ``qkv``, ``out``, ``lse`` and the
-    Philox state -- nothing of size L x L."""
+    """``ops.seq_attention`` / ``ops.seq_attention_backward`` (L above ``ops.SEQ_ATTENTION_MAX_LEN``: the ``_stream`` pair) as
+    one autograd node.  Saved: ``qkv``, ``out``, ``lse`` and the Philox state -- nothing of size L x L."""
 
     @staticmethod
     def forward(ctx, qkv, key_pad, causal, n_head, p, generator):
         qkv = qkv.detach().contiguous()
         B, L, _ = qkv.shape
         pc = rng.reserve(B * n_head * L * L, 4, qkv.device, generator) if p > 0.0 else None
-        out, lse = ops.seq_attention(qkv, key_pad, n_head, causal=causal, p=p, philox=pc)
+        fwd = ops.seq_attention_stream if L > ops.SEQ_ATTENTION_MAX_LEN else ops.seq_attention
+        out, lse = fwd(qkv, key_pad, n_head, causal=causal, p=p, philox=pc)
         ctx.save_for_backward(qkv, out, lse)
         ctx.key_pad, ctx.causal, ctx.n_head, ctx.p, ctx.pc = key_pad, causal, n_head, p, pc
         return out
@@ -140,8 +142,8 @@ class _SeqAttentionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out):
         qkv, out, lse = ctx.saved_tensors
-        dqkv = ops.seq_attention_backward(qkv, ctx.key_pad, ctx.n_head, out, lse, g_out.contiguous(), causal=ctx.causal, p=ctx.p,
-                                          philox=ctx.pc)
+        bwd = ops.seq_attention_stream_backward if qkv.shape[1] > ops.SEQ_ATTENTION_MAX_LEN else ops.seq_attention_backward
+        dqkv = bwd(qkv, ctx.key_pad, ctx.n_head, out, lse, g_out.contiguous(), causal=ctx.causal, p=ctx.p, philox=ctx.pc)
         return dqkv, None, None, None, None, None
 
 
@@ -162,12 +164,20 @@ class FusedTransformerEncoder:
 
     Per layer:  ``a = attention(F.linear(x, in_proj_weight, in_proj_bias))``,  ``x = norm1(x + dropout1(out_proj(a)))``,
     ``x = norm2(x + dropout2(linear2(dropout(activation(linear1(x))))))``; ``encoder.norm`` (when there is one) closes the stack.
+
+    ``max_seq_len`` up to ``ops.SEQ_ATTENTION_MAX_LEN`` by default (one tile holds the sequence); with ``stream=True`` up to
+    ``ops.SEQ_ATTENTION_STREAM_MAX_LEN``: a call on a longer history than one tile holds runs the streaming kernel pair.
     """
 
-    def __init__(self, encoder, max_seq_len, generator=None):
+    def __init__(self, encoder, max_seq_len, generator=None, stream=False):
         if not isinstance(encoder, torch.nn.TransformerEncoder):
             raise TypeError(f'FusedTransformerEncoder: expected a torch.nn.TransformerEncoder, got {type(encoder)}')
-        if int(max_seq_len) > ops.SEQ_ATTENTION_MAX_LEN:
+        if stream:
+            if int(max_seq_len) > ops.SEQ_ATTENTION_STREAM_MAX_LEN:
+                raise ValueError(f'FusedTransformerEncoder: max_seq_len {max_seq_len} > {ops.SEQ_ATTENTION_STREAM_MAX_LEN} '
+                                 '(SEQ_ATTENTION_STREAM_MAX_LEN): the streaming attention kernels take no longer history '
+                                 '(fused_attention = False)')
+        elif int(max_seq_len) > ops.SEQ_ATTENTION_MAX_LEN:
             raise ValueError(f'FusedTransformerEncoder: max_seq_len {max_seq_len} > {ops.SEQ_ATTENTION_MAX_LEN}: one tile of the '
                              'fused attention holds the whole sequence (longer histories: fused_attention = False)')
         for k, layer in enumerate(encoder.layers):

@@ -4,6 +4,7 @@ warm-up calls first; a streaming copy of 1 GiB is timed at the start and at the 
 JSON object and writes it to profiles/seq_attention_bench.json.
 
     python tools/bench_seq_attention.py [--batch 8192 --reps 20 --warmup 5]
+    python tools/bench_seq_attention.py --stream          (group (4) alone, to profiles/seq_attention_stream_bench.json)
 
 Groups:
   (1) core            forward and forward + backward at configs[2] (B = 8192, H = 2, L = 50, dh = 64) and at L = 20, dh = 32, p = 0.5,
@@ -16,6 +17,9 @@ Groups:
                       out (a = the v columns of qkv): what the Linears, LayerNorms, GELU and dropouts cost by themselves.
   (3) training_step   SASRec.training_step + backward at configs[2] (tools/bench_fit.py's synthetic sequences), model.fused_attention
                       on and off.
+  (4) stream          (1) for the streaming kernels (ops.seq_attention_stream / _backward): L = 100 and 200, H = 2, dh = 32 and 64,
+                      p = 0.5, causal and not, B the largest with B H L L < 2^31 (one torch.rand call) that the sdpa arm takes (65535); with the flop model of the
+                      kernel's header (forward 4 L^2 dh, backward 14 L^2 dh per problem, halved when causal).
 Recorded: median / min / max in ms and the ratios."""
 import argparse
 import json
@@ -33,6 +37,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 from graph_bench import peak_above, row, timed      # noqa: E402
 
 PEAK_BYTES_PER_S = 8e12
+SDPA_MAX_BATCH = 65535       # F.scaled_dot_product_attention with dropout_p > 0 refuses a larger batch ("cannot produce valid seed")
 
 
 def copy_gbps(dev):
@@ -43,21 +48,22 @@ def copy_gbps(dev):
     return 2 * src.numel() * 4 / (statistics.median(ms) * 1e-3) / 1e9
 
 
-def sdpa_form(qkv, key_pad, H, p):
+def sdpa_form(qkv, key_pad, H, p, is_causal=True):
     """The attention core as nn.MultiheadAttention runs it (need_weights=False): head-major views of q, k, v, the bool causal mask
     and the key-padding mask merged into one float mask, F.scaled_dot_product_attention with dropout_p, heads concatenated."""
     B, L, D3 = qkv.shape
     D = D3 // 3
     q, k, v = (t.reshape(B, L, H, D // H).transpose(1, 2) for t in qkv.split(D, dim=2))
-    causal = torch.zeros(L, L, device=qkv.device).masked_fill(torch.triu(torch.ones(L, L, dtype=torch.bool, device=qkv.device), 1),
-                                                              float('-inf'))
+    causal = torch.zeros(L, L, device=qkv.device)
+    if is_causal:
+        causal = causal.masked_fill(torch.triu(torch.ones(L, L, dtype=torch.bool, device=qkv.device), 1), float('-inf'))
     pad = torch.zeros(B, L, device=qkv.device).masked_fill(key_pad, float('-inf'))
     mask = (causal.view(1, 1, L, L) + pad.view(B, 1, 1, L)).expand(B, H, L, L)
     out = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=p)
     return out.transpose(1, 2).reshape(B, L, D)
 
 
-def core(seqmodule, dev, B, H, L, dh, p, reps, warmup):
+def core(seqmodule, dev, B, H, L, dh, p, reps, warmup, causal=True):
     D = H * dh
     g = torch.Generator(device=dev).manual_seed(L)
     qkv = torch.empty(B, L, 3 * D, device=dev).normal_(generator=g)
@@ -65,9 +71,9 @@ def core(seqmodule, dev, B, H, L, dh, p, reps, warmup):
     seqlen = torch.randint(1, L + 1, (B,), device=dev, generator=g)
     key_pad = torch.arange(L, device=dev).view(1, L) >= seqlen.view(B, 1)
     leaf = qkv.clone().requires_grad_(True)
-    forms = {'fused': lambda x: seqmodule.seq_attention(x, key_pad, True, H, p),
-             'twin': lambda x: seqmodule.seq_attention_torch(x, key_pad, True, H, p),
-             'sdpa': lambda x: sdpa_form(x, key_pad, H, p)}
+    forms = {'fused': lambda x: seqmodule.seq_attention(x, key_pad, causal, H, p),
+             'twin': lambda x: seqmodule.seq_attention_torch(x, key_pad, causal, H, p),
+             'sdpa': lambda x: sdpa_form(x, key_pad, H, p, causal)}
 
     def fwd(f):
         def run():
@@ -83,7 +89,7 @@ def core(seqmodule, dev, B, H, L, dh, p, reps, warmup):
 
     names = list(forms)
     ms = timed([fwd(forms[n]) for n in names] + [both(forms[n]) for n in names], reps, warmup)
-    out = dict(B=B, H=H, L=L, head_dim=dh, p=p, forward={}, forward_backward={}, peak_bytes={})
+    out = dict(B=B, H=H, L=L, head_dim=dh, p=p, causal=causal, forward={}, forward_backward={}, peak_bytes={})
     bytes_f, bytes_b = B * L * 4 * D * 4, B * L * 8 * D * 4
     for i, n in enumerate(names):
         out['forward'][n] = row(ms[i])
@@ -91,6 +97,9 @@ def core(seqmodule, dev, B, H, L, dh, p, reps, warmup):
         out['peak_bytes'][n] = peak_above(both(forms[n]))
     mf, mb = (statistics.median(ms[0]), statistics.median(ms[len(names)]))
     out['model_bytes'] = dict(forward=bytes_f, backward=bytes_b)
+    flops = B * H * L * L * dh // (2 if causal else 1)
+    out['model_flops'] = dict(forward=4 * flops, backward=14 * flops)
+    out['fused_tflops'] = dict(forward=4 * flops / (mf * 1e-3) / 1e12, forward_backward=18 * flops / (mb * 1e-3) / 1e12)
     out['fused_fraction_of_peak'] = dict(forward=bytes_f / (mf * 1e-3) / PEAK_BYTES_PER_S,
                                          forward_backward=(bytes_f + bytes_b) / (mb * 1e-3) / PEAK_BYTES_PER_S)
     for n in names[1:]:
@@ -167,13 +176,23 @@ def training_step(ra, dev, B, L, d, n, reps, warmup):
     return dict(B=B, L=L, d=d, negative_count=n, fused_attention_on=row(ms[0]), fused_attention_off=row(ms[1]), off_over_on=med[1] / med[0])
 
 
+def write(path, res):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=8192)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'seq_attention_bench.json'))
+    ap.add_argument('--stream', action='store_true', help='group (4) alone')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'seq_attention_stream_bench.json' if a.stream else 'seq_attention_bench.json')
     if not torch.cuda.is_available():
         raise SystemExit('bench_seq_attention.py measures on the GPU: none found')
     import recstudio_amd as ra
@@ -182,6 +201,18 @@ def main():
     props = torch.cuda.get_device_properties(0)
     res = dict(device=props.name, compute_units=props.multi_processor_count, torch=torch.__version__, reps=a.reps, warmup=a.warmup,
                copy_gb_per_s_before=copy_gbps(dev))
+    if a.stream:
+        res['stream'] = []
+        for L in (100, 200):
+            for dh in (32, 64):
+                for causal in (True, False):
+                    B = min(((1 << 31) - 1) // (2 * L * L), SDPA_MAX_BATCH)
+                    res['stream'].append(core(seqmodule, dev, B, 2, L, dh, 0.5, a.reps, a.warmup, causal))
+                    print(json.dumps(res['stream'][-1]), file=sys.stderr, flush=True)
+                    torch.cuda.empty_cache()
+        res['copy_gb_per_s_after'] = copy_gbps(dev)
+        write(a.out, res)
+        return
     res['core'] = [core(seqmodule, dev, a.batch, 2, 50, 64, 0.5, a.reps, a.warmup), core(seqmodule, dev, a.batch, 2, 20, 32, 0.5, a.reps, a.warmup)]
     print(json.dumps(res['core']), file=sys.stderr, flush=True)
     torch.cuda.empty_cache()
@@ -190,11 +221,7 @@ def main():
     torch.cuda.empty_cache()
     res['training_step'] = training_step(ra, dev, a.batch, 50, 128, 256, a.reps, a.warmup)
     res['copy_gb_per_s_after'] = copy_gbps(dev)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        json.dump(res, f, indent=1)
-        f.write('\n')
-    print(json.dumps(res))
+    write(a.out, res)
 
 
 if __name__ == '__main__':
